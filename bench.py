@@ -20,8 +20,16 @@ For N>1 every rank runs its LPT shard (pipeline.distributed_synthesize: no
 data-path collective) and the step ends with the ragged point-to-point gather of
 mel+wav to rank 0 (RCCL over xGMI).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C4|C4S|C2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C4|C4S|C2] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`,
+`rtf`, `x_realtime`, `model_tflops`.  ``--full`` adds everything that takes runs of its own: the
+per-kernel table and `roofline` (untimed passes with HIP events around the launches), the
+one-job-at-a-time rate, `utilisation`, `cpu_baseline` and the timed `cpu_baseline_port`.
+``--dump-outputs DIR`` writes the last timed step's outputs (what a caller of the timed path
+receives) as DIR/<name>.npy, float32; inputs and draws are functions of the arguments alone, so
+two builds run with the same arguments can be compared output for output.
 
 Without torchrun, ``--gpus N`` (N>1) re-launches itself as N ranks under
 torch.distributed.run before anything touches the GPU.  ``--dry-run`` runs the
@@ -567,6 +575,31 @@ def stub_synth(cond, seed, utt_ids=None, lens=None):
 
 stub_synth.mel_bins = 80
 
+DUMP_MAX_BYTES = 48 << 20     # all of --dump-outputs' arrays together (float32), under the 64 MB bound
+
+
+def dump_outputs(path, out, vocoder, pitch):
+    """--dump-outputs: the last timed step's outputs as <path>/<name>.npy, float32.  The synthesis
+    configs return one mel [T_i, M] and one waveform [T_i * hop] per utterance: `mel` and `wav` hold
+    them concatenated along time in utterance order.  C2 returns `mel` [B, T, M], PITCH `pitch`
+    [B, T].  Where the arrays exceed DUMP_MAX_BYTES together, each is flattened and cut to its share
+    of the budget at sorted indices drawn from a fixed seed, the same for every run of these
+    arguments."""
+    if vocoder:
+        mels, wavs = out
+        arrays = {"mel": torch.cat([m.detach().float().cpu() for m in mels]).numpy(),
+                  "wav": torch.cat([w.detach().float().cpu() for w in wavs]).numpy()}
+    else:
+        arrays = {"pitch" if pitch else "mel": out.detach().float().cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for k, (name, a) in enumerate(sorted(arrays.items())):
+        if total > DUMP_MAX_BYTES:
+            n = max(1, int(a.size * (DUMP_MAX_BYTES / total)))
+            idx = np.sort(np.random.default_rng(20_000 + k).integers(0, a.size, n))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -580,8 +613,14 @@ def main():
     ap.add_argument("--lengths", default="fixed", choices=["fixed", "ds"],
                     help="ds: the reference song's 30 segment lengths (and phoneme counts) per GPU "
                          "(tests/golden/ds_lengths.json, from samples/00_*.ds), run as ragged batches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel table and roofline (HIP-event "
+                         "passes), the one-job-at-a-time rate, utilisation and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a fixed seeded sample "
+                         "of each array where they exceed 48 MB together)")
     ap.add_argument("--cpu-frames", type=int, default=-1,
-                    help="cpu_baseline_port sample: -1 = the workload's batch (at most 8 x 861 frames' worth), "
+                    help="(--full) cpu_baseline_port sample: -1 = the workload's batch (at most 8 x 861 frames' worth), "
                          "N > 0 = one utterance of N frames, 0 = skip")
     ap.add_argument("--overlap", type=int, default=None,
                     help="jobs in flight: step i runs on HIP stream i %% N, so consecutive jobs overlap "
@@ -592,9 +631,9 @@ def main():
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
                     help="compute dtype (default: the config's; fp32 is the exact parity path)")
     ap.add_argument("--no-graph", action="store_true", help="C2: launch eagerly instead of replaying a hipGraph")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) skip the HIP-event passes")
     ap.add_argument("--prof-steps", type=int, default=2,
-                    help="untimed steps with every launch bracketed by HIP events (the `kernels` table)")
+                    help="(--full) untimed steps with every launch bracketed by HIP events (the `kernels` table)")
     ap.add_argument("--traffic", default=None, help="PMC traffic summary (default: newest profiles/r*_v*_traffic.json)")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo launcher + sharding + gather check, no GPU")
     ap.add_argument("--fd-opt", action="append", default=[], metavar="NAME=VALUE",
@@ -779,7 +818,7 @@ def main():
         by = bytes_per_launch(Bl, Tl, dtype, M=cfg.get("mels", 80), cyc=cfg.get("cyc", 1))
     for i in range(args.warmup):
         step(i)
-    if ovl is not None:
+    if ovl is not None and args.full:
         # the isolated passes below run on the current stream, whose workspaces the overlapped
         # warm-up never touched: one untimed job there first (fresh allocations run cold)
         step(args.warmup, iso=True)
@@ -788,7 +827,8 @@ def main():
     # Kernel timing.  An event pair costs GPU time at every launch it brackets, so the
     # per-kernel table comes from an untimed pass with every launch recorded, and the
     # timed region records only the dominant kernel (the roofline's avg_launch_us).
-    timing = not (args.no_kernel_timing or dry or (cfg_name == "C2" and not args.no_graph))
+    # All of it belongs to --full: a plain run goes from the warm-up straight to the timed steps.
+    timing = args.full and not (args.no_kernel_timing or dry or (cfg_name == "C2" and not args.no_graph))
     kern_all, dom, nprof = {}, None, 0
     if timing:
         nprof = max(1, args.prof_steps)
@@ -817,6 +857,8 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, cfg["vocoder"], pitch)
     dt_iso = None
     if timing and ovl is not None:
         # jobs in flight share the GPU, so a kernel's launch time in the timed region is not its own:
@@ -834,7 +876,7 @@ def main():
     if timing:
         _lib.profile_enable(False)
         _lib.profile_filter(None)
-    graph_prof = (cfg_name == "C2" and not args.no_graph and not args.no_kernel_timing and not dry)
+    graph_prof = (args.full and cfg_name == "C2" and not args.no_graph and not args.no_kernel_timing and not dry)
     if graph_prof:
         # the timed steps replayed a hipGraph, whose kernels HIP events cannot bracket: take the
         # kernel table and the roofline's launch time from untimed EAGER runs of the same sampler
@@ -976,7 +1018,7 @@ def main():
         "x_realtime": round(audio_s / dt, 1),
         "model_tflops": round(step_fl * args.steps / dt / 1e12, 2),
         "roofline": roofline,
-        "utilisation": sq_utilisation(wl_name) if not dry else None,
+        "utilisation": sq_utilisation(wl_name) if (args.full and not dry) else None,
         "kernels": kernels,
         "phases": phases,
         "kernels_source": (f"untimed {'eager ' if graph_prof else ''}pass of {nprof} steps, every launch bracketed by "
@@ -985,8 +1027,9 @@ def main():
         "cpu_baseline_port": None,
         "build": None if dry else {"pd_build_config": _lib.lib().pd_build_config().decode(), "lib_sha16": lib_sha16()},
         "dry_run": dry,
+        "full": args.full,
     }
-    if rank == 0 and world == 1 and not dry:
+    if args.full and rank == 0 and world == 1 and not dry:
         out_line["cpu_baseline"] = ref_cpu_baseline(cfg_name)
         if args.cpu_frames != 0 and not svs and not pitch:
             if args.cpu_frames > 0:

@@ -8,9 +8,64 @@ from prodiff_amd import synth
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def load(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as d:
-        return {k: d[k] for k in d.files}
+PART_BYTES = 900 * 1024      # array bytes per file: every committed fixture file stays under 1 MiB
+
+
+def part_paths(name, root=GOLDEN):
+    """name.npz, then name.p1.npz, name.p2.npz, ... as far as they exist."""
+    paths, i = [os.path.join(root, name + ".npz")], 1
+    while os.path.exists(os.path.join(root, f"{name}.p{i}.npz")):
+        paths.append(os.path.join(root, f"{name}.p{i}.npz"))
+        i += 1
+    return paths
+
+
+def save(name, arrays, root=GOLDEN, part_bytes=PART_BYTES):
+    """Write a fixture as name.npz and, where its arrays exceed part_bytes, name.p1.npz, ...: arrays
+    fill the parts in order; one larger than a part is cut along its flattened length into
+    key@0, key@1, ... beside key@shape.  load() puts them together again.  Returns the paths."""
+    parts, room = [{}], part_bytes
+
+    def put(k, v):
+        nonlocal room
+        if v.nbytes > room and parts[-1]:
+            parts.append({})
+            room = part_bytes
+        parts[-1][k] = v
+        room -= v.nbytes
+
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        assert "@" not in k, k
+        if v.nbytes <= part_bytes:
+            put(k, v)
+            continue
+        flat, n = v.reshape(-1), max(1, part_bytes // v.itemsize)
+        put(k + "@shape", np.array(v.shape, np.int64))
+        for i in range(0, flat.size, n):
+            put(f"{k}@{i // n}", flat[i:i + n])
+    for old in part_paths(name, root)[1:]:
+        os.remove(old)
+    paths = []
+    for i, p in enumerate(parts):
+        paths.append(os.path.join(root, name + (f".p{i}" if i else "") + ".npz"))
+        np.savez_compressed(paths[-1], **p)
+    return paths
+
+
+def load(name, root=GOLDEN):
+    d = {}
+    for path in part_paths(name, root):
+        with np.load(path) as z:
+            d.update({k: z[k] for k in z.files})
+    for key in [k for k in d if k.endswith("@shape")]:
+        k = key[:-len("@shape")]
+        shape, chunks, i = d.pop(key), [], 0
+        while f"{k}@{i}" in d:
+            chunks.append(d.pop(f"{k}@{i}"))
+            i += 1
+        d[k] = np.concatenate(chunks).reshape([int(s) for s in shape])
+    return d
 
 
 def wavenet_params(dims, seed):

@@ -260,6 +260,91 @@ def test_bench_tables_cover_every_dominant_tag():
     assert bench.dominant_kernel({"nsf_pair": (27, 5.0), "wn_stack": (2, 1.0)}, fl, by) == "nsf_pair"
 
 
+def test_golden_fixtures_in_parts(tmp_path):
+    """golden_io.save cuts a fixture into files of at most PART_BYTES of arrays (an array larger
+    than that along its flattened length) and load() returns the arrays bit for bit; no committed
+    fixture file exceeds 1 MiB."""
+    rng = np.random.default_rng(0)
+    arrays = {"a": rng.standard_normal((3, 50, 7)).astype(np.float32), "n": np.int64(5), "names": np.array(["x", "yz"]),
+              "b": rng.standard_normal(1001), "c": rng.integers(0, 9, (40,)), "empty": np.zeros((0, 4), np.float32)}
+    paths = G.save("fx", arrays, root=str(tmp_path), part_bytes=2000)
+    assert len(paths) > 3 and paths == G.part_paths("fx", str(tmp_path))
+    for p in paths:
+        with np.load(p) as z:
+            assert sum(z[k].nbytes for k in z.files) <= 2000
+    back = G.load("fx", root=str(tmp_path))
+    assert set(back) == set(arrays)
+    for k, v in arrays.items():
+        assert back[k].dtype == np.asarray(v).dtype and back[k].shape == np.asarray(v).shape
+        np.testing.assert_array_equal(back[k], v)
+    # a smaller rewrite leaves no stale part behind
+    assert G.save("fx", {"n": np.int64(1)}, root=str(tmp_path)) == G.part_paths("fx", str(tmp_path))
+    big = [f for f in os.listdir(G.GOLDEN) if os.path.getsize(os.path.join(G.GOLDEN, f)) > 1 << 20]
+    assert not big, big
+
+
+def _bench_line(monkeypatch, capsys, argv):
+    import json
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py"] + argv)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_dry_run(tmp_path, monkeypatch, capsys):
+    """`--dump-outputs DIR` writes the last timed step's outputs as float32 DIR/<name>.npy, the same
+    from run to run; `--steps` sets the timed steps and the line carries `ms_per_step` (CPU dry run:
+    stub synthesis, mel = the condition's first 80 columns, so the dump pins the inputs too)."""
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--frames", "7", "--dry-run"]
+    runs = []
+    for name in ("a", "b"):
+        d = _bench_line(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+        assert d["ms_per_step"] > 0 and d["unit"] == "mel-frames/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 2 * 7 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+        assert sorted(os.listdir(tmp_path / name)) == ["mel.npy", "wav.npy"]
+        runs.append({k: np.load(tmp_path / name / (k + ".npy")) for k in ("mel", "wav")})
+    for k, shape in (("mel", (2 * 7, 80)), ("wav", (2 * 7 * 256,))):
+        assert runs[0][k].dtype == np.float32 and runs[0][k].shape == shape
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
+    assert np.abs(runs[0]["mel"]).max() > 0
+
+
+def test_bench_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """Outputs over the byte budget are cut to a fixed sample: the same indices on every call, each
+    array its share of the budget."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    g = torch.Generator().manual_seed(0)
+    mels = [torch.randn(9, 80, generator=g) for _ in range(2)]
+    wavs = [torch.randn(9 * 256, generator=g) for _ in range(2)]
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), (mels, wavs), True, False)
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("mel", "wav")}
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in ("mel", "wav")}
+    assert 0 < a["mel"].nbytes + a["wav"].nbytes <= 4000 and a["wav"].size > a["mel"].size > 0
+    for k, full in (("mel", torch.cat(mels)), ("wav", torch.cat(wavs))):
+        np.testing.assert_array_equal(a[k], b[k])
+        assert np.isin(a[k], full.numpy().reshape(-1)).all()
+    bench.dump_outputs(str(tmp_path / "p"), torch.ones(2, 5, dtype=torch.float64), False, True)
+    assert np.load(tmp_path / "p" / "pitch.npy").dtype == np.float32
+
+
+def test_bench_full_option_off_by_default(monkeypatch, capsys):
+    """`--full` is an option of every run and off by default; the plain line leaves the fields of the
+    measurements behind it empty (CPU dry run: the launcher and the line, no GPU legs)."""
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--frames", "7", "--dry-run"]
+    d = _bench_line(monkeypatch, capsys, argv)
+    assert d["full"] is False
+    assert d["cpu_baseline"] is None and d["cpu_baseline_port"] is None and d["utilisation"] is None
+    assert d["roofline"] is None and d["kernels"] == {}
+    assert _bench_line(monkeypatch, capsys, argv + ["--full"])["full"] is True
+
+
 def test_collate_pad_stack_equals_per_item_pad():
     """pipeline._pad_stack (the batch collate: one stack for equal lengths, one zero fill and a copy
     per row otherwise) equals the per-item F.pad + stack it replaced, for float frames and integer

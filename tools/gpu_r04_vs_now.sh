@@ -10,7 +10,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 for c in "$@"; do
   for rep in 1 2; do
     for side in r04 now; do
-      d=$R; extra="$NOW_ARGS"; [ $side = r04 ] && d=$R/tools/bin/r04 && extra=""
+      d=$R; extra="--full $NOW_ARGS"; [ $side = r04 ] && d=$R/tools/bin/r04 && extra=""
       (cd $d && timeout -k 10 300 python -u bench.py --config $c --cpu-frames 0 $extra > $O/${c}_${side}_$rep.json 2> $O/${c}_${side}_$rep.err)
       python - $O/${c}_${side}_$rep.json "$c $side $rep" <<'PY'
 import json, sys

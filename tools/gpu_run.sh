@@ -4,7 +4,7 @@
 #
 # usage (GPU box): tools/gpu_run.sh <tag> <part> [<part> ...]
 #   tests[=<pytest -k expr>]  every -m gpu test (or the selected ones)       -> gpu_tests.log
-#   bench=<cfg>[,<cfg>...]    one bench.py line per config (C3 C2 C4 C5 C5DS) -> bench_<cfg>.json
+#   bench=<cfg>[,<cfg>...]    one bench.py --full line per config (C3 C2 C4 C5 C5DS) -> bench_<cfg>.json
 #   trace=<cfg>               rocprofv3 --kernel-trace --stats of that bench -> trace_<cfg>/
 #   (trace / traffic / sq run one job at a time, --overlap 1: the bench line's roofline launch times
 #   come from its isolated pass, bench.py)
@@ -42,7 +42,7 @@ for part in "$@"; do
       tail -2 $O/gpu_tests.log ;;
     bench)
       for c in ${val//,/ }; do
-        timeout -k 10 300 python -u bench.py $(bench_args $c) > $O/bench_$c.json 2> $O/bench_$c.err
+        timeout -k 10 300 python -u bench.py --full $(bench_args $c) > $O/bench_$c.json 2> $O/bench_$c.err
         python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); \
 print(sys.argv[2], d['ms_per_step'], 'ms/step', d['value'], d['roofline']['kernel'], d['roofline']['frac'])" \
           $O/bench_$c.json $c
