@@ -44,6 +44,9 @@ int pd_version(void);
  * (A/B variant libraries, tools/build_variant_lib.sh).  bench.py records it; the GPU tests refuse a
  * variant library unless PRODIFF_ALLOW_VARIANT=1. */
 const char* pd_build_config(void);
+/* Device bytes held by the live handles of this process (weight pools, their bf16 mirrors and
+ * the handles' other allocations); 0 once every handle is destroyed. */
+size_t pd_live_device_bytes(void);
 
 /* Per-launch timing for benchmarks: when enabled, HIP events are recorded on the
  * launch stream around every hot-path kernel (tagged by use, e.g. "fd_kp_kernel").
@@ -85,6 +88,7 @@ typedef struct {
 /* Packs the weights into the kernels' layouts (device-to-device, on `stream`). */
 int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, int dtype,
                       void* stream, pd_wavenet** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
 void pd_wavenet_destroy(pd_wavenet* h);
 /* Kernel-variant option of a handle; set before its first call.  PD_WN_OPT_LAYER selects the
  * bf16 residual-layer implementation: 0 the fused kernel with 32-frame blocks, 3 the fused
@@ -223,6 +227,7 @@ typedef struct {
 
 int fd_create(const fd_dims* dims, const float* const* params, int dtype, void* stream,
               fd_model** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
 void fd_destroy(fd_model* m);
 int fd_hop(const fd_model* m);   /* prod(upsample_ratios) = samples per mel frame */
 /* Workspace of fd_forward (S = 1) or fd_sample (S = N steps; bounded: steps run in chunks of
@@ -319,6 +324,7 @@ int nsf_num_params(const nsf_dims* dims);
 /* dtype PD_DTYPE_F32: exact fp32 (parity path); PD_DTYPE_BF16: bf16 weights/activations on the
  * MFMA, fp32 accumulate, fp32 source module and epilogues. */
 int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void* stream, nsf_model** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
 void nsf_destroy(nsf_model* m);
 int nsf_hop(const nsf_model* m);   /* prod(upsample_rates) */
 size_t nsf_workspace_size(const nsf_model* m, int B, int T);
@@ -410,6 +416,7 @@ typedef struct {
 int pd_cond_num_params(const pd_cond_dims* dims);
 int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dtype, void* stream,
                    pd_cond** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
 void pd_cond_destroy(pd_cond* h);
 size_t pd_cond_workspace_size(const pd_cond* h, int B, int T_txt, int T_mel);
 

@@ -67,6 +67,7 @@ _SIGS = {
     "pd_last_error": (C.c_char_p, []),
     "pd_version": (C.c_int, []),
     "pd_build_config": (C.c_char_p, []),
+    "pd_live_device_bytes": (C.c_size_t, []),
     "pd_profile_enable": (C.c_int, [C.c_int]),
     "pd_profile_summary": (C.c_int, [C.c_char_p, C.c_int]),
     "pd_profile_filter": (C.c_int, [C.c_char_p]),
@@ -137,6 +138,88 @@ def check(rc):
     if rc != 0:
         msg = lib().pd_last_error().decode(errors="replace")
         raise HipError(f"libprodiff_hip error {rc}: {msg}")
+
+
+class NativeHandle:
+    """Owner of one module's packed C handle (WaveNet, FastDiff, NSF-HiFiGAN, condition encoder):
+    the compute dtype and kernel options it is created with, and the rule for when it is packed
+    again.  ``create`` / ``destroy`` / ``set_option`` / ``num_params`` name library functions (looked
+    up on first use, so building a module does not load the library)."""
+
+    def __init__(self, name, create, destroy, set_option=None, option_ids=None, num_params=None):
+        self.name = name
+        self._create, self._destroy, self._set_option, self._num_params = create, destroy, set_option, num_params
+        self.option_ids = option_ids or {}
+        self.dtype = "fp32"
+        self.options = {}
+        self.h = None          # C.c_void_p of the live handle
+        self.sig = None
+        self._keep = None      # the pack is stream-ordered: its source tensors live as long as the handle
+        self._device = None
+
+    def set_dtype(self, dtype):
+        if dtype not in ("fp32", "bf16"):
+            raise ValueError(dtype)
+        self.dtype = dtype
+
+    def set_options(self, opts):
+        for k, v in opts.items():
+            if k not in self.option_ids:
+                raise ValueError(f"unknown {self.name} option {k!r}")
+            self.options[k] = int(v)
+
+    def signature(self, params, *extras):
+        """What the packed handle depends on: dtype, options, every parameter's storage and
+        version (load_state_dict and in-place updates change it), and the module's extras."""
+        return (self.dtype, tuple(sorted(self.options.items()))) + \
+            tuple((p.data_ptr(), p._version) for p in params) + extras
+
+    def require_gpu(self, t):
+        if not t.is_cuda:
+            raise HipError(f"{self.name} parameters must live on the GPU (call .cuda())")
+
+    def get(self, signature, build):
+        """The handle for ``signature``: the live one if it was built for the same signature, else a
+        new one from ``build() -> (dims struct, contiguous float32 tensors in the C-ABI order)``; the
+        old handle is closed once the new one stands."""
+        if self.h is not None and signature == self.sig:
+            return self.h
+        L = lib()
+        dims, tensors = build()
+        for t in tensors:
+            self.require_gpu(t)
+        if self._num_params is not None and getattr(L, self._num_params)(C.byref(dims)) != len(tensors):
+            raise HipError(f"{self.name}: parameter count does not match {self._num_params}")
+        dev = tensors[0].device
+        arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        h = C.c_void_p()
+        dt = PD_DTYPE_BF16 if self.dtype == "bf16" else PD_DTYPE_F32
+        check(getattr(L, self._create)(C.byref(dims), arr, dt, stream_ptr(dev), C.byref(h)))
+        for k, v in self.options.items():
+            rc = getattr(L, self._set_option)(h, self.option_ids[k], v)
+            if rc != 0:
+                self._destroy_idle(h, dev)
+                check(rc)
+        self.close()
+        self.h, self.sig, self._keep, self._device = h, signature, tensors, dev
+        return h
+
+    def _destroy_idle(self, h, dev):
+        import torch
+        torch.cuda.synchronize(dev)   # the pack, or kernels that read the pool, may still be queued
+        getattr(lib(), self._destroy)(h)
+
+    def close(self):
+        """Destroy the handle once its device is idle."""
+        if self.h is not None:
+            self._destroy_idle(self.h, self._device)
+            self.h = self.sig = self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def fptr(t):

@@ -360,8 +360,7 @@ int enc_gemm(GemmArgs a, float* part, hipStream_t st, const char* tag) {
 struct pd_cond {
   pd_cond_dims d;
   int H, L, K, heads, D, F;
-  float* pool = nullptr;
-  __bf16* pool_bf = nullptr;
+  WeightPool weights;   // every float* below points into it
   // per layer
   std::vector<float*> ln1g, ln1b, Wqkv, Wo, ln2g, ln2b, W1, b1, W2, b2;
   float *lnfg = nullptr, *lnfb = nullptr, *emb = nullptr, *dur_w = nullptr, *dur_b = nullptr;
@@ -425,6 +424,7 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
   PD_CHECK_ARG(!d.use_lang_id || d.num_langs > 0, "num_langs must be positive with use_lang_id");
   // add_gender_embed looks the ids up in lang_embed (prodiff_teacher.py:91-95), so gender ids need it
   PD_CHECK_ARG(!d.use_gender_id || d.use_lang_id, "use_gender_id needs use_lang_id (gender ids index lang_embed)");
+  PD_TRY(check_params(params, pd_cond_num_params(dims)));
   hipStream_t st = (hipStream_t)stream;
   pd_cond* h = new pd_cond();
   h->d = d;
@@ -432,40 +432,28 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
   h->heads = d.num_heads; h->D = D; h->F = 4 * d.hidden_size;
   const int H = h->H, F = h->F, K = h->K, L = h->L;
   // pool layout (floats, 64-aligned); GEMM weights packed as W[n][k]
-  std::vector<std::pair<float**, size_t>> plan;
+  WeightPool& wp = h->weights;
   h->ln1g.resize(L); h->ln1b.resize(L); h->Wqkv.resize(L); h->Wo.resize(L); h->ln2g.resize(L);
   h->ln2b.resize(L); h->W1.resize(L); h->b1.resize(L); h->W2.resize(L); h->b2.resize(L);
   for (int l = 0; l < L; ++l) {
-    plan.push_back({&h->ln1g[l], H}); plan.push_back({&h->ln1b[l], H});
-    plan.push_back({&h->Wqkv[l], (size_t)3 * H * H}); plan.push_back({&h->Wo[l], (size_t)H * H});
-    plan.push_back({&h->ln2g[l], H}); plan.push_back({&h->ln2b[l], H});
-    plan.push_back({&h->W1[l], (size_t)F * K * H}); plan.push_back({&h->b1[l], F});
-    plan.push_back({&h->W2[l], (size_t)H * F}); plan.push_back({&h->b2[l], H});
+    wp.add(&h->ln1g[l], H); wp.add(&h->ln1b[l], H);
+    wp.add(&h->Wqkv[l], (size_t)3 * H * H); wp.add(&h->Wo[l], (size_t)H * H);
+    wp.add(&h->ln2g[l], H); wp.add(&h->ln2b[l], H);
+    wp.add(&h->W1[l], (size_t)F * K * H); wp.add(&h->b1[l], F);
+    wp.add(&h->W2[l], (size_t)H * F); wp.add(&h->b2[l], H);
   }
-  plan.push_back({&h->lnfg, H}); plan.push_back({&h->lnfb, H});
-  plan.push_back({&h->emb, (size_t)d.vocab_size * H});
-  if (d.use_dur_embed) { plan.push_back({&h->dur_w, H}); plan.push_back({&h->dur_b, H}); }
-  if (d.use_spk_id) plan.push_back({&h->spk, (size_t)d.num_spk * H});
-  if (d.use_gender_id) plan.push_back({&h->gender, (size_t)2 * H});
-  if (d.use_lang_id) plan.push_back({&h->lang, (size_t)d.num_langs * H});
-  plan.push_back({&h->pw, H}); plan.push_back({&h->pb, H});
-  if (d.use_voicing_embed) { plan.push_back({&h->vw, H}); plan.push_back({&h->vb, H}); }
-  if (d.use_breath_embed) { plan.push_back({&h->bw, H}); plan.push_back({&h->bb, H}); }
-  size_t off = 0;
-  std::vector<size_t> offs;
-  for (auto& p : plan) { offs.push_back(off); off += (p.second + 63) / 64 * 64; }
-  if (hipMalloc(&h->pool, off * sizeof(float)) != hipSuccess) {
-    delete h;
-    set_error("hipMalloc failed for condition-encoder weights");
-    return PD_ERR_HIP;
-  }
-  for (size_t i = 0; i < plan.size(); ++i) *plan[i].first = h->pool + offs[i];
+  wp.add(&h->lnfg, H); wp.add(&h->lnfb, H);
+  wp.add(&h->emb, (size_t)d.vocab_size * H);
+  if (d.use_dur_embed) { wp.add(&h->dur_w, H); wp.add(&h->dur_b, H); }
+  if (d.use_spk_id) wp.add(&h->spk, (size_t)d.num_spk * H);
+  if (d.use_gender_id) wp.add(&h->gender, (size_t)2 * H);
+  if (d.use_lang_id) wp.add(&h->lang, (size_t)d.num_langs * H);
+  wp.add(&h->pw, H); wp.add(&h->pb, H);
+  if (d.use_voicing_embed) { wp.add(&h->vw, H); wp.add(&h->vb, H); }
+  if (d.use_breath_embed) { wp.add(&h->bw, H); wp.add(&h->bb, H); }
   auto run = [&]() -> int {
-    auto cp = [&](float* dst, const float* src, size_t n) -> int {
-      PD_CHECK_ARG(src, "null parameter pointer");
-      PD_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-      return PD_OK;
-    };
+    PD_TRY(wp.commit(st, "condition-encoder"));
+    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
     int p = 0;
     for (int l = 0; l < L; ++l) {
       PD_TRY(cp(h->ln1g[l], params[p++], H));
@@ -474,7 +462,6 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
       PD_TRY(cp(h->Wo[l], params[p++], (size_t)H * H));
       PD_TRY(cp(h->ln2g[l], params[p++], H));
       PD_TRY(cp(h->ln2b[l], params[p++], H));
-      PD_CHECK_ARG(params[p], "null parameter pointer");
       PD_TRY(pack_conv(h->W1[l], K * H, 0, 0, H, params[p++], F, H, K, st));   // ffn_1 [F, H, K]
       PD_TRY(cp(h->b1[l], params[p++], F));
       PD_TRY(cp(h->W2[l], params[p++], (size_t)H * F));
@@ -491,33 +478,16 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
     PD_TRY(cp(h->pb, params[p++], H));
     if (d.use_voicing_embed) { PD_TRY(cp(h->vw, params[p++], H)); PD_TRY(cp(h->vb, params[p++], H)); }
     if (d.use_breath_embed) { PD_TRY(cp(h->bw, params[p++], H)); PD_TRY(cp(h->bb, params[p++], H)); }
-    if (dtype == PD_DTYPE_BF16) {
-      PD_HIP(hipMalloc(&h->pool_bf, off * sizeof(__bf16)));
-      PD_TRY(convert_f32_bf16(h->pool, h->pool_bf, (long long)off, st));
-      register_bf16_pool(h->pool, off, h->pool_bf);
-    }
+    if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
     return PD_OK;
   };
   const int rc = run();
-  if (rc != PD_OK) {
-    (void)hipFree(h->pool);
-    if (h->pool_bf) (void)hipFree(h->pool_bf);
-    delete h;
-    return rc;
-  }
+  if (rc != PD_OK) { delete h; return rc; }
   *out = h;
   return PD_OK;
 }
 
-void pd_cond_destroy(pd_cond* h) {
-  if (!h) return;
-  if (h->pool_bf) {
-    unregister_bf16_pool(h->pool);
-    (void)hipFree(h->pool_bf);
-  }
-  (void)hipFree(h->pool);
-  delete h;
-}
+void pd_cond_destroy(pd_cond* h) { delete h; }
 
 size_t pd_cond_workspace_size(const pd_cond* h, int B, int T_txt, int T_mel) {
   if (!h || B < 1 || T_txt < 1 || T_mel < 0) return 0;

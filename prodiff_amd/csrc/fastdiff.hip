@@ -75,9 +75,8 @@ struct fd_model {
 
   mutable hipStream_t side = nullptr;
   mutable hipEvent_t ev_hidden = nullptr, ev_kp[4] = {}, ev_lvc[4] = {};
-  float* pool = nullptr;
-  __bf16* pool_bf = nullptr;   // bf16 mirror of `pool` (PD_DTYPE_BF16), registered with launch_gemm
-  void* kps = nullptr;         // the blocks' pre-scaled kernel-predictor weights (kks_w, kks_b)
+  WeightPool weights;          // every float* below points into it; bf16() is set for PD_DTYPE_BF16
+  DevBuf kps;                  // the blocks' pre-scaled kernel-predictor weights (kks_w, kks_b)
   // step MLP
   float *fc1_w, *fc1_b, *fc2_w, *fc2_b;
   float *first_w, *first_b;          // [32][7]
@@ -98,6 +97,18 @@ struct fd_model {
     float *c0_w, *c0_b, *c1_w, *c1_b;   // [32][96]
     float *c2_w, *c2_b;                 // [32][96 + 32] : conv.2 taps ++ residual_dense
   } dn[4];
+
+  ~fd_model() {   // the side stream and its events exist once a sampler call has used them
+    if (side) {
+      (void)hipStreamSynchronize(side);
+      (void)hipStreamDestroy(side);
+    }
+    if (ev_hidden) (void)hipEventDestroy(ev_hidden);
+    for (int n = 0; n < 4; ++n) {
+      if (ev_kp[n]) (void)hipEventDestroy(ev_kp[n]);
+      if (ev_lvc[n]) (void)hipEventDestroy(ev_lvc[n]);
+    }
+  }
 };
 
 namespace {
@@ -2396,11 +2407,11 @@ __global__ void pack_final_kernel(float* dst, const float* src) {
 // Does block n run as the whole-block LVC kernel (bf16; hop % 32 == 0: one frame per
 // 32-row tile; hop | 32: several, masked per frame)?
 bool fd_block_fused(const fd_model* m, int n) {
-  return m->pool_bf && m->lvc_ts > 0 && (m->hops[n] % 32 == 0 || (32 % m->hops[n] == 0 && m->lvc_sub));
+  return m->weights.bf16() && m->lvc_ts > 0 && (m->hops[n] % 32 == 0 || (32 % m->hops[n] == 0 && m->lvc_sub));
 }
 // Kernel predictor on the side stream (fd_sample): every block on the whole-block kernel.
 bool fd_kp_side(const fd_model* m) {
-  if (!m->kp_side || !m->pool_bf) return false;
+  if (!m->kp_side || !m->weights.bf16()) return false;
   for (int n = 0; n < m->nblocks; ++n)
     if (!fd_block_fused(m, n)) return false;
   return true;
@@ -2541,7 +2552,7 @@ int fd_kp_hidden_all(const fd_model* m, float* ws, const FdWs& W, const float* c
 // Does the last LVC block run as the fused kernel (upsample + first conv + final update)?
 bool fd_final_fused(const fd_model* m) {
   const int n = m->nblocks - 1;
-  return m->pool_bf && m->lvc_ts > 0 && m->hops[n] % 32 == 0 && m->lvc_fuse && m->ratios[n] >= 4;
+  return m->weights.bf16() && m->lvc_ts > 0 && m->hops[n] % 32 == 0 && m->lvc_fuse && m->ratios[n] >= 4;
 }
 
 // The sampler update fused into the last LVC block (FIN): audio_out = (xa - ce eps)/den + sig z.
@@ -2606,12 +2617,12 @@ int fd_net(const fd_model* m, float* ws, const FdWs& W, const float* xa, const f
            const float* nz, int step, int B, int Tc, float** xout, hipStream_t st,
            const FdFinal* fin = nullptr, bool side = false, const int* lens = nullptr) {
   const int nb = m->nblocks;
-  if (lens && m->pool_bf && m->lvc_ts == 0) {
+  if (lens && m->weights.bf16() && m->lvc_ts == 0) {
     set_error("FD_OPT_LVC_TS 0 (per-layer LVC launches) does not take ragged batches (lens)");
     return PD_ERR_UNSUPPORTED;
   }
   const long long L = (long long)Tc * m->hops[nb - 1];
-  const bool bf = m->pool_bf != nullptr;
+  const bool bf = m->weights.bf16() != nullptr;
   // whole-block LVC kernel with its prologue/epilogue fusions (bf16)
   // (hop % 32 == 0: one frame per 32-row tile; hop | 32: several, masked per frame)
   auto fused_block = [&](int n) { return fd_block_fused(m, n); };
@@ -2848,6 +2859,7 @@ int fd_create(const fd_dims* dims, const float* const* params, int dtype, void* 
                    dims->step_embed_out == EMB_OUT,
                "only the FastDiff base.yaml architecture (32/80/64, 4 LVC layers) is supported");
   PD_CHECK_ARG(dims->num_blocks >= 1 && dims->num_blocks <= 4, "num_blocks in [1,4]");
+  PD_TRY(check_params(params, FD_NUM_PARAMS(dims->num_blocks)));
   hipStream_t st = (hipStream_t)stream;
   fd_model* m = new fd_model();
   m->nblocks = dims->num_blocks;
@@ -2860,42 +2872,32 @@ int fd_create(const fd_dims* dims, const float* const* params, int dtype, void* 
     m->hops[n] = hop;
   }
   // allocation plan
-  std::vector<std::pair<float**, size_t>> plan;
-  plan.push_back({&m->fc1_w, (size_t)EMB_MID * EMB_IN}); plan.push_back({&m->fc1_b, EMB_MID});
-  plan.push_back({&m->fc2_w, (size_t)EMB_OUT * EMB_MID}); plan.push_back({&m->fc2_b, EMB_OUT});
-  plan.push_back({&m->first_w, 224}); plan.push_back({&m->first_b, CI});
-  plan.push_back({&m->final_w, 224}); plan.push_back({&m->final_b, 1});
+  WeightPool& wp = m->weights;
+  wp.add(&m->fc1_w, (size_t)EMB_MID * EMB_IN); wp.add(&m->fc1_b, EMB_MID);
+  wp.add(&m->fc2_w, (size_t)EMB_OUT * EMB_MID); wp.add(&m->fc2_b, EMB_OUT);
+  wp.add(&m->first_w, 224); wp.add(&m->first_b, CI);
+  wp.add(&m->final_w, 224); wp.add(&m->final_b, 1);
   for (int n = 0; n < m->nblocks; ++n) {
     auto& K = m->blk[n];
-    plan.push_back({&K.up_w, (size_t)2 * m->ratios[n] * CI * CI}); plan.push_back({&K.up_b, CI});
-    plan.push_back({&K.upf_w, (size_t)2 * m->ratios[n] * CI * CI});
-    plan.push_back({&K.fct_w, (size_t)CC * EMB_OUT}); plan.push_back({&K.fct_b, CC});
-    plan.push_back({&K.kin_w, (size_t)HK * 5 * 96}); plan.push_back({&K.kin_b, HK});
-    for (int j = 0; j < 6; ++j) { plan.push_back({&K.kres_w[j], (size_t)HK * 3 * HK}); plan.push_back({&K.kres_b[j], HK}); }
-    plan.push_back({&K.kk_w, (size_t)NLY * KPERLAYER * 3 * HK}); plan.push_back({&K.kk_b, (size_t)NLY * KPERLAYER});
-    plan.push_back({&K.kb_w, (size_t)2 * CI * NLY * 3 * HK}); plan.push_back({&K.kb_b, (size_t)2 * CI * NLY});
-    for (int i = 0; i < NLY; ++i) { plan.push_back({&K.cv_w[i], (size_t)CI * 96}); plan.push_back({&K.cv_b[i], CI}); }
+    wp.add(&K.up_w, (size_t)2 * m->ratios[n] * CI * CI); wp.add(&K.up_b, CI);
+    wp.add(&K.upf_w, (size_t)2 * m->ratios[n] * CI * CI);
+    wp.add(&K.fct_w, (size_t)CC * EMB_OUT); wp.add(&K.fct_b, CC);
+    wp.add(&K.kin_w, (size_t)HK * 5 * 96); wp.add(&K.kin_b, HK);
+    for (int j = 0; j < 6; ++j) { wp.add(&K.kres_w[j], (size_t)HK * 3 * HK); wp.add(&K.kres_b[j], HK); }
+    wp.add(&K.kk_w, (size_t)NLY * KPERLAYER * 3 * HK); wp.add(&K.kk_b, (size_t)NLY * KPERLAYER);
+    wp.add(&K.kb_w, (size_t)2 * CI * NLY * 3 * HK); wp.add(&K.kb_b, (size_t)2 * CI * NLY);
+    for (int i = 0; i < NLY; ++i) { wp.add(&K.cv_w[i], (size_t)CI * 96); wp.add(&K.cv_b[i], CI); }
   }
   for (int n = 0; n < m->nblocks; ++n) {
     auto& D = m->dn[n];
-    plan.push_back({&D.c0_w, (size_t)CI * 96}); plan.push_back({&D.c0_b, CI});
-    plan.push_back({&D.c1_w, (size_t)CI * 96}); plan.push_back({&D.c1_b, CI});
-    plan.push_back({&D.c2_w, (size_t)CI * 128}); plan.push_back({&D.c2_b, CI});
+    wp.add(&D.c0_w, (size_t)CI * 96); wp.add(&D.c0_b, CI);
+    wp.add(&D.c1_w, (size_t)CI * 96); wp.add(&D.c1_b, CI);
+    wp.add(&D.c2_w, (size_t)CI * 128); wp.add(&D.c2_b, CI);
   }
-  size_t off = 0;
-  std::vector<size_t> offs;
-  for (auto& p : plan) { offs.push_back(off); off += (p.second + 63) / 64 * 64; }
-  if (hipMalloc((void**)&m->pool, off * sizeof(float)) != hipSuccess) {
-    delete m; set_error("hipMalloc failed for FastDiff weights"); return PD_ERR_HIP;
-  }
-  for (size_t i = 0; i < plan.size(); ++i) *plan[i].first = m->pool + offs[i];
 
   auto run = [&]() -> int {
-    PD_HIP(hipMemsetAsync(m->pool, 0, off * sizeof(float), st));
-    auto cp = [&](float* dst, const float* src, size_t n) -> int {
-      PD_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-      return PD_OK;
-    };
+    PD_TRY(wp.commit(st, "FastDiff"));
+    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
     int p = 0;
     auto nxt = [&]() { const float* q = params[p++]; return q; };
     // order: see include/prodiff_hip.h (FD_PARAM_ORDER)
@@ -2958,16 +2960,16 @@ int fd_create(const fd_dims* dims, const float* const* params, int dtype, void* 
     }
     if (p != FD_NUM_PARAMS(m->nblocks)) { set_error("fd_create: parameter count mismatch"); return PD_ERR_ARG; }
     if (dtype == PD_DTYPE_BF16) {
-      PD_HIP(hipMalloc((void**)&m->pool_bf, off * sizeof(__bf16)));
-      PD_TRY(convert_f32_bf16(m->pool, m->pool_bf, (long long)off, st));
-      register_bf16_pool(m->pool, off, m->pool_bf);
+      PD_TRY(wp.mirror_bf16(st));
       // pre-scaled kernel-predictor weights of every block (bf16 rows, fp32 biases)
       const size_t nw = (size_t)NLY * KPERLAYER * 3 * HK, nbias = (size_t)NLY * KPERLAYER;
-      PD_HIP(hipMalloc(&m->kps, m->nblocks * (nw * sizeof(__bf16) + nbias * sizeof(float))));
+      PD_TRY(m->kps.alloc(m->nblocks * (nw * sizeof(__bf16) + nbias * sizeof(float)),
+                          "the FastDiff pre-scaled kernel-predictor weights"));
+      float* kps = static_cast<float*>(m->kps.get());
       for (int n = 0; n < m->nblocks; ++n) {
         auto& K = m->blk[n];
-        K.kks_b = reinterpret_cast<float*>(m->kps) + n * nbias;
-        K.kks_w = reinterpret_cast<__bf16*>(reinterpret_cast<float*>(m->kps) + m->nblocks * nbias) + n * nw;
+        K.kks_b = kps + n * nbias;
+        K.kks_w = reinterpret_cast<__bf16*>(kps + m->nblocks * nbias) + n * nw;
         hipLaunchKernelGGL(kp_prescale_kernel, dim3(cdiv((long long)nw, 256)), dim3(256), 0, st, K.kk_w, K.kk_b, K.kks_w,
                            K.kks_b);
         PD_LAUNCH_CHECK();
@@ -2975,39 +2977,13 @@ int fd_create(const fd_dims* dims, const float* const* params, int dtype, void* 
     }
     return PD_OK;
   };
-  for (int i = 0; i < FD_NUM_PARAMS(m->nblocks); ++i)
-    if (!params[i]) { (void)hipFree(m->pool); delete m; set_error("null parameter " + std::to_string(i)); return PD_ERR_ARG; }
-  int rc = run();
-  if (rc != PD_OK) {
-    (void)hipFree(m->pool);
-    if (m->pool_bf) (void)hipFree(m->pool_bf);
-    if (m->kps) (void)hipFree(m->kps);
-    delete m;
-    return rc;
-  }
+  const int rc = run();
+  if (rc != PD_OK) { delete m; return rc; }
   *out = m;
   return PD_OK;
 }
 
-void fd_destroy(fd_model* m) {
-  if (!m) return;
-  if (m->side) {
-    (void)hipStreamSynchronize(m->side);
-    (void)hipStreamDestroy(m->side);
-    (void)hipEventDestroy(m->ev_hidden);
-    for (int n = 0; n < 4; ++n) {
-      if (m->ev_kp[n]) (void)hipEventDestroy(m->ev_kp[n]);
-      if (m->ev_lvc[n]) (void)hipEventDestroy(m->ev_lvc[n]);
-    }
-  }
-  if (m->pool_bf) {
-    unregister_bf16_pool(m->pool);
-    (void)hipFree(m->pool_bf);
-  }
-  if (m->kps) (void)hipFree(m->kps);
-  (void)hipFree(m->pool);
-  delete m;
-}
+void fd_destroy(fd_model* m) { delete m; }
 
 int fd_hop(const fd_model* m) { return m ? m->hops[m->nblocks - 1] : 0; }
 
@@ -3075,7 +3051,7 @@ int fd_forward(const fd_model* m, const float* audio, const float* cond, const f
   PD_TRY(fd_step_mlp(m, ws, W, B, st));
   PD_TRY(transpose_ct_to_tc(cond, ws + W.condT, B, CC, Tc, st));
   float* x = nullptr;
-  if (m->pool_bf) PD_TRY(fd_kp_hidden_all(m, ws, W, ws + W.condT, ws + W.nz, 1, B, Tc, st));
+  if (m->weights.bf16()) PD_TRY(fd_kp_hidden_all(m, ws, W, ws + W.condT, ws + W.nz, 1, B, Tc, st));
   PD_TRY(fd_net(m, ws, W, audio, ws + W.condT, ws + W.nz, 0, B, Tc, &x, st));
   hipLaunchKernelGGL(final_conv_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, x, m->final_w, m->final_b,
                      eps, (float*)nullptr, 0.f, 0.f, 0.f, (const float*)nullptr, 0ull, 0u, (const int*)nullptr, L,
@@ -3130,7 +3106,7 @@ int fd_sample_coefs(const fd_model* m, const float* mel, const float* ce_, const
     for (int j = 0; j < nc; ++j) sv[j] = steps_[j0 + j];
     PD_TRY(fill_steps(ws + W.steps, sv.data(), nc, B, st));
     PD_TRY(fd_step_mlp(m, ws, W, nc * B, st));
-    if (m->pool_bf) PD_TRY(fd_kp_hidden_all(m, ws, W, mel, ws + W.nz, nc, B, Tc, st, lens));
+    if (m->weights.bf16()) PD_TRY(fd_kp_hidden_all(m, ws, W, mel, ws + W.nz, nc, B, Tc, st, lens));
     if (side) {
       PD_HIP(hipEventRecord(m->ev_hidden, st));
       PD_HIP(hipStreamWaitEvent(m->side, m->ev_hidden, 0));

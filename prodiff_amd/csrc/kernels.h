@@ -1,5 +1,8 @@
 // Small utility kernels shared by the WaveNet and FastDiff paths.
 #pragma once
+#include <utility>
+#include <vector>
+
 #include "common.h"
 
 namespace pd {
@@ -50,11 +53,54 @@ int weight_norm_fold(float* w, const float* g, const float* v, int Cout, int per
 
 // fp32 -> bf16 (round to nearest even)
 int convert_f32_bf16(const float* src, __bf16* dst, long long n, hipStream_t st);
-// bf16 mirrors of packed fp32 weight pools: launch_gemm uses the bf16 copy of any
-// weight pointer inside a registered pool (same element offset).
-void register_bf16_pool(const float* base, size_t n, const __bf16* bf);
-void unregister_bf16_pool(const float* base);
+// bf16 mirrors of packed fp32 weight pools (WeightPool::mirror_bf16): launch_gemm uses the bf16
+// copy of any weight pointer inside a mirrored pool (same element offset).
 const __bf16* lookup_bf16(const float* p);
+
+// The packed weights of one native handle: a single fp32 device allocation cut into 64-float
+// aligned slots, and (PD_DTYPE_BF16) its bf16 mirror.  Plan with add(), then commit() allocates,
+// zeroes the pool on the stream (so the alignment padding reads 0) and points every slot into
+// it.  The destructor takes the mirror out of lookup_bf16's registry before it frees anything:
+// a handle that holds one by value needs no cleanup code of its own.
+class WeightPool {
+ public:
+  WeightPool() = default;
+  WeightPool(const WeightPool&) = delete;
+  WeightPool& operator=(const WeightPool&) = delete;
+  ~WeightPool();
+  // *slot must stay where it is until commit()
+  void add(float** slot, size_t n);
+  void add(const float** slot, size_t n) { add(const_cast<float**>(slot), n); }
+  int commit(hipStream_t st, const char* what);
+  // allocates the mirror, converts the pool as it is on the stream at this point, registers it
+  int mirror_bf16(hipStream_t st);
+  const __bf16* bf16() const { return bf_; }   // null without a mirror
+ private:
+  std::vector<std::pair<float**, size_t>> plan_;
+  float* pool_ = nullptr;
+  __bf16* bf_ = nullptr;
+  size_t n_ = 0;   // floats in the pool, padding included
+  bool registered_ = false;
+};
+
+// One further device allocation owned by a handle (move-only).
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); return *this; }
+  ~DevBuf();
+  int alloc(size_t bytes, const char* what);
+  void* get() const { return p_; }
+ private:
+  void* p_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// PD_ERR_ARG naming the first null entry of a create call's parameter list.
+int check_params(const float* const* params, int n);
+// dst[i] = src[i], device to device on the stream
+int copy_f32(float* dst, const float* src, size_t n, hipStream_t st);
 
 // Philox fills, U[0,1) or N(0,1), per utterance (common.h philox_*_u): out[b][e], e < per, keyed by utt_id(ids, b).
 int fill_uniform_utt(float* out, int B, long long per, unsigned long long seed, unsigned stream, const int* ids,

@@ -1,4 +1,5 @@
 // Small utility kernels + error plumbing.
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -370,7 +371,6 @@ namespace {
 struct PoolRec { const float* base; size_t n; const __bf16* bf; };
 std::vector<PoolRec> g_pools;
 std::mutex g_pool_mu;
-}  // namespace
 
 void register_bf16_pool(const float* base, size_t n, const __bf16* bf) {
   std::lock_guard<std::mutex> lk(g_pool_mu);
@@ -383,11 +383,85 @@ void unregister_bf16_pool(const float* base) {
     if (g_pools[i].base == base) { g_pools.erase(g_pools.begin() + i); return; }
 }
 
+// device bytes held by live WeightPools and DevBufs (pd_live_device_bytes)
+std::atomic<size_t> g_live_bytes{0};
+
+bool dev_alloc(void** p, size_t bytes) {
+  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return false; }
+  g_live_bytes += bytes;
+  return true;
+}
+
+void dev_free(void* p, size_t bytes) {
+  if (!p) return;
+  (void)hipFree(p);
+  g_live_bytes -= bytes;
+}
+}  // namespace
+
 const __bf16* lookup_bf16(const float* p) {
   std::lock_guard<std::mutex> lk(g_pool_mu);
   for (auto& r : g_pools)
     if (p >= r.base && p < r.base + r.n) return r.bf + (p - r.base);
   return nullptr;
+}
+
+void WeightPool::add(float** slot, size_t n) { plan_.push_back({slot, n}); }
+
+int WeightPool::commit(hipStream_t st, const char* what) {
+  size_t off = 0;
+  for (auto& p : plan_) off += (p.second + 63) / 64 * 64;
+  if (!dev_alloc((void**)&pool_, off * sizeof(float))) {
+    set_error(std::string("hipMalloc failed for ") + what + " weights");
+    return PD_ERR_HIP;
+  }
+  n_ = off;
+  off = 0;
+  for (auto& p : plan_) { *p.first = pool_ + off; off += (p.second + 63) / 64 * 64; }
+  plan_.clear();
+  PD_HIP(hipMemsetAsync(pool_, 0, n_ * sizeof(float), st));
+  return PD_OK;
+}
+
+int WeightPool::mirror_bf16(hipStream_t st) {
+  if (!dev_alloc((void**)&bf_, n_ * sizeof(__bf16))) {
+    set_error("hipMalloc failed for the bf16 weight mirror");
+    return PD_ERR_HIP;
+  }
+  PD_TRY(convert_f32_bf16(pool_, bf_, (long long)n_, st));
+  register_bf16_pool(pool_, n_, bf_);
+  registered_ = true;
+  return PD_OK;
+}
+
+WeightPool::~WeightPool() {
+  if (registered_) unregister_bf16_pool(pool_);
+  dev_free(bf_, n_ * sizeof(__bf16));
+  dev_free(pool_, n_ * sizeof(float));
+}
+
+int DevBuf::alloc(size_t bytes, const char* what) {
+  dev_free(p_, bytes_);
+  bytes_ = 0;
+  if (!dev_alloc(&p_, bytes)) {
+    set_error(std::string("hipMalloc failed for ") + what);
+    return PD_ERR_HIP;
+  }
+  bytes_ = bytes;
+  return PD_OK;
+}
+
+DevBuf::~DevBuf() { dev_free(p_, bytes_); }
+
+int check_params(const float* const* params, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!params[i]) { set_error("argument: null parameter " + std::to_string(i)); return PD_ERR_ARG; }
+  return PD_OK;
+}
+
+int copy_f32(float* dst, const float* src, size_t n, hipStream_t st) {
+  PD_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return PD_OK;
 }
 
 // ---------------------------------------------------------------- RNG fills
@@ -485,6 +559,7 @@ extern "C" int pd_profile_summary(char* buf, int buflen) {
 
 extern "C" const char* pd_last_error(void) { return pd::get_error(); }
 extern "C" int pd_version(void) { return 2; }
+extern "C" size_t pd_live_device_bytes(void) { return pd::g_live_bytes.load(); }
 
 namespace pd {
 const char* fastdiff_build_flags();

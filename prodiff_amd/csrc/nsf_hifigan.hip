@@ -52,9 +52,7 @@ struct NsfUps {
 struct nsf_model {
   nsf_dims d{};
   int dim = 9, C0 = 0, upp = 1;
-  float* pool = nullptr;
-  __bf16* pool_bf = nullptr;     // PD_DTYPE_BF16: bf16 mirror, registered with launch_gemm
-  size_t pool_n = 0;
+  WeightPool weights;            // every weight pointer below points into it
   const float* lin_w = nullptr;
   const float* lin_b = nullptr;
   NsfConv pre, post;
@@ -1874,7 +1872,7 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
   const int np = nsf_num_params(dims);
   PD_CHECK_ARG(np > 0, "nsf_dims: bad counts");
   PD_CHECK_ARG(dtype == PD_DTYPE_F32 || dtype == PD_DTYPE_BF16, "dtype");
-  for (int i = 0; i < np; ++i) PD_CHECK_ARG(params[i] != nullptr, "null parameter " + std::to_string(i));
+  PD_TRY(check_params(params, np));
   const nsf_dims& d = *dims;
   PD_CHECK_ARG(d.num_mels > 0 && d.num_mels % 4 == 0, "num_mels must be a multiple of 4");
   PD_CHECK_ARG(d.harmonic_num >= 0 && d.sampling_rate > 0, "harmonic_num / sampling_rate");
@@ -1899,13 +1897,11 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
   for (int i = 0; i < d.num_upsamples; ++i) m->upp *= d.upsample_rates[i];
   m->convs_per_block = (d.resblock == 1 ? 2 : 1) * d.num_dilations;
 
-  // --- pool layout (floats)
-  size_t off = 0;
-  auto take = [&](size_t n) { size_t o = off; off += (n + 63) / 64 * 64; return o; };
+  // --- pool layout: slots in the order the pool holds them (the vectors are sized first, so
+  // the slot addresses stay put until commit)
+  WeightPool& wp = m->weights;
   const int dim = m->dim;
-  size_t o_lin_w = take(dim), o_lin_b = take(1);
-  std::vector<size_t> o_nc_w, o_nc_b, o_ups_b;
-  std::vector<std::vector<size_t>> o_ups_w;
+  wp.add(&m->lin_w, dim); wp.add(&m->lin_b, 1);
   m->ups.resize(d.num_upsamples);
   for (int i = 0; i < d.num_upsamples; ++i) {
     NsfUps& U = m->ups[i];
@@ -1922,27 +1918,26 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
     } else {
       U.nc_k = 1; U.nc_stride = 1; U.nc_pad = 0;
     }
-    o_nc_w.push_back(take((size_t)U.cout * U.nc_k));
-    o_nc_b.push_back(take(U.cout));
+    wp.add(&U.nc_w, (size_t)U.cout * U.nc_k);
+    wp.add(&U.nc_b, U.cout);
     const int p = (U.k - U.u) / 2;
-    std::vector<size_t> ph;
+    U.w.resize(U.u);
     U.qmin.resize(U.u);
     for (int phi = 0; phi < U.u; ++phi) {
-      ph.push_back(take((size_t)U.cout * U.ntap * U.kpad));
+      wp.add(&U.w[phi], (size_t)U.cout * U.ntap * U.kpad);
       const int num = p - phi;              // first q with q*u + phi - p >= 0
       U.qmin[phi] = num > 0 ? (num + U.u - 1) / U.u : 0;
     }
-    o_ups_w.push_back(ph);
-    o_ups_b.push_back(take(U.cout));
+    wp.add(&U.b, U.cout);
   }
-  auto conv_init = [&](NsfConv& c, int cin, int cout, int taps, int dil, size_t& ow, size_t& ob) {
+  auto conv_init = [&](NsfConv& c, int cin, int cout, int taps, int dil) {
     c.cin = cin; c.cout = cout; c.taps = taps; c.dil = dil; c.kpad = round_up(cin, GEMM_BK);
-    ow = take((size_t)cout * taps * c.kpad);
-    ob = take(cout);
+    wp.add(&c.w, (size_t)cout * taps * c.kpad);
+    wp.add(&c.b, cout);
   };
-  size_t o_pre_w, o_pre_b, o_post_w, o_post_b;
-  conv_init(m->pre, d.num_mels, m->C0, 7, 1, o_pre_w, o_pre_b);
-  std::vector<size_t> o_res_w, o_res_b;
+  conv_init(m->pre, d.num_mels, m->C0, 7, 1);
+  m->res.resize((size_t)d.num_upsamples * d.num_kernels * m->convs_per_block);
+  size_t r = 0;
   for (int i = 0; i < d.num_upsamples; ++i) {
     const int c = m->C0 >> (i + 1);
     for (int j = 0; j < d.num_kernels; ++j) {
@@ -1950,97 +1945,58 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
       for (int q = 0; q < m->convs_per_block; ++q) {
         // ResBlock1: convs1.{0..D-1} (dilated) then convs2.{0..D-1} (dilation 1); ResBlock2: convs.{0..D-1}
         int dil = (d.resblock == 1 && q >= d.num_dilations) ? 1 : d.resblock_dilation_sizes[j][q % d.num_dilations];
-        NsfConv cv;
-        size_t ow, ob;
-        conv_init(cv, c, c, k, dil, ow, ob);
-        m->res.push_back(cv);
-        o_res_w.push_back(ow);
-        o_res_b.push_back(ob);
+        conv_init(m->res[r++], c, c, k, dil);
       }
     }
   }
-  conv_init(m->post, m->C0 >> d.num_upsamples, 1, 7, 1, o_post_w, o_post_b);
+  conv_init(m->post, m->C0 >> d.num_upsamples, 1, 7, 1);
 
   auto run = [&]() -> int {
-    PD_HIP(hipMalloc((void**)&m->pool, off * sizeof(float)));
-    PD_HIP(hipMemsetAsync(m->pool, 0, off * sizeof(float), st));
-    float* P = m->pool;
-    auto cp = [&](size_t o, const float* src, size_t n) -> int {
-      PD_HIP(hipMemcpyAsync(P + o, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-      return PD_OK;
-    };
+    PD_TRY(wp.commit(st, "NSF-HiFiGAN"));
+    // the handle reads its weights through const pointers; packing is the one place that writes them
+    auto W = [](const float* q) { return const_cast<float*>(q); };
+    auto cp = [&](const float* dst, const float* src, size_t n) { return copy_f32(W(dst), src, n, st); };
     int p = 0;
-    PD_TRY(cp(o_lin_w, params[p++], dim));
-    PD_TRY(cp(o_lin_b, params[p++], 1));
-    m->lin_w = P + o_lin_w;
-    m->lin_b = P + o_lin_b;
+    PD_TRY(cp(m->lin_w, params[p++], dim));
+    PD_TRY(cp(m->lin_b, params[p++], 1));
     for (int i = 0; i < d.num_upsamples; ++i) {
       NsfUps& U = m->ups[i];
       hipLaunchKernelGGL(nsf_pack_noise_kernel, dim3(cdiv((long long)U.cout * U.nc_k, 256)), dim3(256), 0, st,
-                         P + o_nc_w[i], params[p++], U.cout, U.nc_k);
+                         W(U.nc_w), params[p++], U.cout, U.nc_k);
       PD_LAUNCH_CHECK();
-      PD_TRY(cp(o_nc_b[i], params[p++], U.cout));
-      U.nc_w = P + o_nc_w[i];
-      U.nc_b = P + o_nc_b[i];
+      PD_TRY(cp(U.nc_b, params[p++], U.cout));
     }
-    PD_TRY(pack_conv(P + o_pre_w, 7 * m->pre.kpad, 0, 0, m->pre.kpad, params[p++], m->C0, d.num_mels, 7, st));
-    PD_TRY(cp(o_pre_b, params[p++], m->C0));
-    m->pre.w = P + o_pre_w;
-    m->pre.b = P + o_pre_b;
+    PD_TRY(pack_conv(W(m->pre.w), 7 * m->pre.kpad, 0, 0, m->pre.kpad, params[p++], m->C0, d.num_mels, 7, st));
+    PD_TRY(cp(m->pre.b, params[p++], m->C0));
     for (int i = 0; i < d.num_upsamples; ++i) {
       NsfUps& U = m->ups[i];
       const float* w = params[p++];
       for (int phi = 0; phi < U.u; ++phi) {
         long long n = (long long)U.cout * U.ntap * U.cin;
-        hipLaunchKernelGGL(nsf_pack_ups_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, P + o_ups_w[i][phi], w, U.cin,
+        hipLaunchKernelGGL(nsf_pack_ups_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, W(U.w[phi]), w, U.cin,
                            U.cout, U.k, U.u, phi, U.ntap, U.kpad);
         PD_LAUNCH_CHECK();
-        U.w.push_back(P + o_ups_w[i][phi]);
       }
-      PD_TRY(cp(o_ups_b[i], params[p++], U.cout));
-      U.b = P + o_ups_b[i];
+      PD_TRY(cp(U.b, params[p++], U.cout));
     }
-    for (size_t r = 0; r < m->res.size(); ++r) {
-      NsfConv& c = m->res[r];
-      PD_TRY(pack_conv(P + o_res_w[r], c.taps * c.kpad, 0, 0, c.kpad, params[p++], c.cout, c.cin, c.taps, st));
-      PD_TRY(cp(o_res_b[r], params[p++], c.cout));
-      c.w = P + o_res_w[r];
-      c.b = P + o_res_b[r];
+    for (NsfConv& c : m->res) {
+      PD_TRY(pack_conv(W(c.w), c.taps * c.kpad, 0, 0, c.kpad, params[p++], c.cout, c.cin, c.taps, st));
+      PD_TRY(cp(c.b, params[p++], c.cout));
     }
-    PD_TRY(pack_conv(P + o_post_w, 7 * m->post.kpad, 0, 0, m->post.kpad, params[p++], 1, m->post.cin, 7, st));
-    PD_TRY(cp(o_post_b, params[p++], 1));
-    m->post.w = P + o_post_w;
-    m->post.b = P + o_post_b;
+    PD_TRY(pack_conv(W(m->post.w), 7 * m->post.kpad, 0, 0, m->post.kpad, params[p++], 1, m->post.cin, 7, st));
+    PD_TRY(cp(m->post.b, params[p++], 1));
     if (p != np) { set_error("nsf_create: parameter count mismatch"); return PD_ERR_ARG; }
-    m->pool_n = off;
-    if (dtype == PD_DTYPE_BF16) {
-      // every GEMM weight then streams as bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
-      PD_HIP(hipMalloc((void**)&m->pool_bf, off * sizeof(__bf16)));
-      PD_TRY(convert_f32_bf16(m->pool, m->pool_bf, (long long)off, st));
-      register_bf16_pool(m->pool, off, m->pool_bf);
-    }
+    // PD_DTYPE_BF16: every GEMM weight then streams as bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
+    if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
     return PD_OK;
   };
-  int rc = run();
-  if (rc != PD_OK) {
-    if (m->pool) (void)hipFree(m->pool);
-    if (m->pool_bf) (void)hipFree(m->pool_bf);
-    delete m;
-    return rc;
-  }
+  const int rc = run();
+  if (rc != PD_OK) { delete m; return rc; }
   *out = m;
   return PD_OK;
 }
 
-void nsf_destroy(nsf_model* m) {
-  if (!m) return;
-  if (m->pool_bf) {
-    unregister_bf16_pool(m->pool);
-    (void)hipFree(m->pool_bf);
-  }
-  (void)hipFree(m->pool);
-  delete m;
-}
+void nsf_destroy(nsf_model* m) { delete m; }
 
 int nsf_hop(const nsf_model* m) { return m ? m->upp : 0; }
 

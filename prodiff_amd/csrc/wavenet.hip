@@ -22,12 +22,10 @@ using namespace pd;
 struct pd_wavenet {
   int M, H, L, C, cyc, dtype;
   int ldw_in, ldw1;
-  float* pool = nullptr;
-  __bf16* pool_bf = nullptr;   // bf16 mirror of `pool` (PD_DTYPE_BF16), registered with launch_gemm
-  size_t pool_n = 0;
+  WeightPool weights;   // every float* below points into it
   float *Win, *b_in, *W1, *b1, *W2, *b2, *Wd, *bd, *Wl1, *bl1, *Wl2, *bl2, *Ws, *bs, *Wo, *bo;
   // bf16 path, C == 256: residual-layer weights in MFMA-fragment order (wn_layer_bf16_kernel)
-  __bf16* frag = nullptr;
+  DevBuf frag;
   __bf16* W1f = nullptr;   // [L][2C/32 tiles][K/16 steps][64 lanes][8]
   __bf16* W2f = nullptr;
   __bf16* W1p = nullptr;   // [L][C/16 pair tiles][K/16][64][8] (wn_gate_bf16_kernel)
@@ -1750,39 +1748,25 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
   PD_CHECK_ARG(H > 0 && H % 4 == 0, "hidden_size must be a positive multiple of 4");
   PD_CHECK_ARG(C > 0 && C % 32 == 0, "residual_channels must be a positive multiple of 32");
   PD_CHECK_ARG(L > 0 && cyc > 0, "residual_layers/dilation_cycle_length must be positive");
-  for (int i = 0; i < PD_WAVENET_NUM_PARAMS(L); ++i)
-    PD_CHECK_ARG(params[i] != nullptr, "null parameter pointer " + std::to_string(i));
+  PD_TRY(check_params(params, PD_WAVENET_NUM_PARAMS(L)));
   hipStream_t st = (hipStream_t)stream;
 
   pd_wavenet* h = new pd_wavenet();
   h->M = M; h->H = H; h->L = L; h->C = C; h->cyc = cyc; h->dtype = dtype;
   h->ldw_in = round_up(M, GEMM_BK);
   h->ldw1 = 3 * C + round_up(H, GEMM_BK);
-  size_t off = 0;
-  std::vector<std::pair<float**, size_t>> plan = {
-      {&h->Win, (size_t)C * h->ldw_in}, {&h->b_in, (size_t)C},
-      {&h->W1, (size_t)4 * C * C}, {&h->b1, (size_t)4 * C},
-      {&h->W2, (size_t)C * 4 * C}, {&h->b2, (size_t)C},
-      {&h->Wd, (size_t)L * C * C}, {&h->bd, (size_t)L * C},
-      {&h->Wl1, (size_t)L * 2 * C * h->ldw1}, {&h->bl1, (size_t)L * 2 * C},
-      {&h->Wl2, (size_t)L * 2 * C * C}, {&h->bl2, (size_t)L * 2 * C},
-      {&h->Ws, (size_t)C * C}, {&h->bs, (size_t)C},
-      {&h->Wo, (size_t)M * C}, {&h->bo, (size_t)M}};
-  std::vector<size_t> offs;
-  for (auto& p : plan) { offs.push_back(off); off += (p.second + 63) / 64 * 64; }
-  if (hipMalloc((void**)&h->pool, off * sizeof(float)) != hipSuccess) {
-    delete h;
-    set_error("hipMalloc failed for WaveNet weights");
-    return PD_ERR_HIP;
-  }
-  for (size_t i = 0; i < plan.size(); ++i) *plan[i].first = h->pool + offs[i];
-  int rc = PD_OK;
+  WeightPool& wp = h->weights;
+  wp.add(&h->Win, (size_t)C * h->ldw_in); wp.add(&h->b_in, (size_t)C);
+  wp.add(&h->W1, (size_t)4 * C * C); wp.add(&h->b1, (size_t)4 * C);
+  wp.add(&h->W2, (size_t)C * 4 * C); wp.add(&h->b2, (size_t)C);
+  wp.add(&h->Wd, (size_t)L * C * C); wp.add(&h->bd, (size_t)L * C);
+  wp.add(&h->Wl1, (size_t)L * 2 * C * h->ldw1); wp.add(&h->bl1, (size_t)L * 2 * C);
+  wp.add(&h->Wl2, (size_t)L * 2 * C * C); wp.add(&h->bl2, (size_t)L * 2 * C);
+  wp.add(&h->Ws, (size_t)C * C); wp.add(&h->bs, (size_t)C);
+  wp.add(&h->Wo, (size_t)M * C); wp.add(&h->bo, (size_t)M);
   auto run = [&]() -> int {
-    PD_HIP(hipMemsetAsync(h->pool, 0, off * sizeof(float), st));
-    auto cp = [&](float* dst, const float* src, size_t n) -> int {
-      PD_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-      return PD_OK;
-    };
+    PD_TRY(wp.commit(st, "WaveNet"));
+    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
     int p = 0;
     PD_TRY(pack_conv(h->Win, h->ldw_in, 0, 0, h->ldw_in, params[p++], C, M, 1, st));
     PD_TRY(cp(h->b_in, params[p++], C));
@@ -1812,17 +1796,14 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
     PD_TRY(cp(h->bs, params[p++], C));
     PD_TRY(cp(h->Wo, params[p++], (size_t)M * C));
     PD_TRY(cp(h->bo, params[p++], M));
-    h->pool_n = off;
     if (dtype == PD_DTYPE_BF16) {
-      PD_HIP(hipMalloc(&h->pool_bf, off * sizeof(__bf16)));
-      PD_TRY(convert_f32_bf16(h->pool, h->pool_bf, (long long)off, st));
-      register_bf16_pool(h->pool, off, h->pool_bf);
+      PD_TRY(wp.mirror_bf16(st));
       if (C == WNF_C && 3 * C + H == 1024) {   // H == 256: the fused kernel is built for K1 = 1024
         const int K1 = 3 * C + H;
         const size_t per = (size_t)4 * C * K1 + (size_t)2 * C * C;
-        PD_HIP(hipMalloc(&h->frag, (size_t)L * per * sizeof(__bf16)));
-        h->W1f = h->frag;
-        h->W2f = h->frag + (size_t)L * 2 * C * K1;
+        PD_TRY(h->frag.alloc((size_t)L * per * sizeof(__bf16), "the WaveNet fragment-order weights"));
+        h->W1f = static_cast<__bf16*>(h->frag.get());
+        h->W2f = h->W1f + (size_t)L * 2 * C * K1;
         h->W1p = h->W2f + (size_t)L * 2 * C * C;
         for (int l = 0; l < L; ++l) {
           const long long n1 = (long long)2 * C * K1, n2 = (long long)2 * C * C;
@@ -1840,14 +1821,8 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
     }
     return PD_OK;
   };
-  rc = run();
-  if (rc != PD_OK) {
-    (void)hipFree(h->pool);
-    if (h->pool_bf) (void)hipFree(h->pool_bf);
-    if (h->frag) (void)hipFree(h->frag);
-    delete h;
-    return rc;
-  }
+  const int rc = run();
+  if (rc != PD_OK) { delete h; return rc; }
   *out = h;
   return PD_OK;
 }
@@ -1893,16 +1868,7 @@ int pd_wavenet_set_option(pd_wavenet* h, int option, int value) {
   return PD_ERR_ARG;
 }
 
-void pd_wavenet_destroy(pd_wavenet* h) {
-  if (!h) return;
-  if (h->pool_bf) {
-    unregister_bf16_pool(h->pool);
-    (void)hipFree(h->pool_bf);
-  }
-  if (h->frag) (void)hipFree(h->frag);
-  (void)hipFree(h->pool);
-  delete h;
-}
+void pd_wavenet_destroy(pd_wavenet* h) { delete h; }
 
 size_t pd_wavenet_workspace_size(const pd_wavenet* h, int B, int T, int S) {
   if (!h || B < 0 || T < 0 || S < 1) return 0;

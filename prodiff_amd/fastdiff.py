@@ -132,26 +132,18 @@ class FastDiff(nn.Module):
                                                   dilation=1, bias=True))
         if use_weight_norm:
             self.apply_weight_norm()
-        self.compute_dtype = "fp32"
-        self._options = {}
-        self._h = None
-        self._sig = None
+        self._native = _lib.NativeHandle("FastDiff", "fd_create", "fd_destroy", "fd_set_option", _lib.FD_OPTIONS)
         self._ws = _lib.Workspace()
 
     def set_compute_dtype(self, dtype):
         """'fp32' (exact, the parity path) or 'bf16' (bf16 MFMA, bf16 LVC kernels)."""
-        if dtype not in ("fp32", "bf16"):
-            raise ValueError(dtype)
-        self.compute_dtype = dtype
+        self._native.set_dtype(dtype)
         return self
 
     def set_options(self, **opts):
         """Kernel-variant options (fd_set_option, include/prodiff_hip.h FD_OPT_*): lvc_ts,
         lvc_ts_sub, lvc_fuse, lvc_pf, lvc_sub, kp_side.  Unset ones keep the measured defaults."""
-        for k, v in opts.items():
-            if k not in _lib.FD_OPTIONS:
-                raise ValueError(f"unknown FastDiff option {k!r}")
-            self._options[k] = int(v)
+        self._native.set_options(opts)
         return self
 
     # ------------------------------------------------------- weight norm
@@ -184,20 +176,13 @@ class FastDiff(nn.Module):
         seq += [self.final_conv[0]]
         return seq
 
-    def _param_sig(self):
-        return (self.compute_dtype, tuple(sorted(self._options.items()))) + \
-            tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def handle(self):
-        sig = self._param_sig()
-        if self._h is not None and sig == self._sig:
-            return self._h
+    def _pack(self):
+        """Weight-norm pairs folded on the device, then (weight, bias) per conv in the C-ABI order."""
         L = _lib.lib()
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise _lib.HipError("FastDiff parameters must live on the GPU (call .cuda())")
-        st = _lib.stream_ptr(dev)
-        keep, ptrs = [], []
+        first = next(self.parameters())
+        self._native.require_gpu(first)
+        st = _lib.stream_ptr(first.device)
+        tensors = []
         for m in self._convs_in_order():
             if hasattr(m, "weight_g"):
                 g = m.weight_g.detach().float().contiguous()
@@ -207,40 +192,17 @@ class FastDiff(nn.Module):
                                                  v[0].numel(), st))
             else:
                 w = m.weight.detach().float().contiguous()
-            b = m.bias.detach().float().contiguous()
-            keep += [w, b]
-            ptrs += [w.data_ptr(), b.data_ptr()]
-        arr = (_lib.C.c_void_p * len(ptrs))(*ptrs)
+            tensors += [w, m.bias.detach().float().contiguous()]
         d = self._dims
         ratios = (_lib.C.c_int * 4)(*(self.upsample_ratios + [0] * (4 - len(self.upsample_ratios))))
         dims = _lib.fd_dims(d["audio_channels"], d["inner_channels"], d["cond_channels"], self.lvc_block_nums,
                             ratios, d["lvc_layers_each_block"], d["lvc_kernel_size"],
                             d["kpnet_hidden_channels"], d["kpnet_conv_size"], d["step_embed_in"],
                             d["step_embed_mid"], d["step_embed_out"])
-        h = _lib.C.c_void_p()
-        dt = _lib.PD_DTYPE_BF16 if self.compute_dtype == "bf16" else _lib.PD_DTYPE_F32
-        _lib.check(L.fd_create(_lib.C.byref(dims), arr, dt, st, _lib.C.byref(h)))
-        for k, v in self._options.items():
-            rc = L.fd_set_option(h, _lib.FD_OPTIONS[k], v)
-            if rc != 0:
-                L.fd_destroy(h)
-                _lib.check(rc)
-        self._release()
-        self._h, self._sig, self._keep = h, sig, keep
-        return h
+        return dims, tensors
 
-    def _release(self):
-        if self._h is not None:
-            torch.cuda.synchronize()
-            _lib.lib().fd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _lib.lib().fd_destroy(self._h)
-        except Exception:
-            pass
+    def handle(self):
+        return self._native.get(self._native.signature(self.parameters()), self._pack)
 
     # ------------------------------------------------------- forward
     @torch.no_grad()
@@ -270,12 +232,9 @@ class FastDiff(nn.Module):
         _lib.check(_lib.lib().fd_draw_x_T(h, _lib.fptr(x), B, Tc, int(seed), _lib.iptr(uid), _lib.stream_ptr(dev)))
         return x
 
-    @torch.no_grad()
-    def sample_coefs(self, mel, ce, den, sg, steps, x_T=None, noise=None, seed=None, utt_ids=None, draw0=0,
-                     lens=None):
-        """The reverse loop with explicit per-pass coefficients (fd_sample_coefs): pass j
-        evaluates eps at steps[j] and sets x = (x - ce[j] eps) / den[j] + sg[j] z.  ``lens``: ragged
-        batch, each row's utterance length in mel frames (``sample``)."""
+    def _sample(self, fn, mel, coefs, steps, x_T, noise, seed, utt_ids, lens, min_noise=0, extra=()):
+        """fd_sample / fd_sample_coefs: three per-pass coefficient arrays, the steps, and (``extra``)
+        the arguments between ``lens`` and ``wav``."""
         h = self.handle()
         B, Tc, _ = mel.shape
         N = len(steps)
@@ -284,6 +243,8 @@ class FastDiff(nn.Module):
         mel = mel.float().contiguous()
         xT = None if x_T is None else x_T.float().reshape(B, L).contiguous()
         nz = None if noise is None else noise.float().reshape(-1, B, L).contiguous()
+        if nz is not None and nz.shape[0] < min_noise:
+            raise ValueError(f"noise holds {nz.shape[0]} draws, sampler needs {min_noise}")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         wav = torch.empty(B, 1, L, device=dev, dtype=torch.float32)
@@ -291,11 +252,19 @@ class FastDiff(nn.Module):
         ln = _lib.lens(lens, B, Tc, dev)
         lib = _lib.lib()
         ws, wsb = self._ws.get(lib.fd_workspace_size(h, B, Tc, N), dev)
-        _lib.check(lib.fd_sample_coefs(h, _lib.fptr(mel), _lib.farr(ce), _lib.farr(den), _lib.farr(sg),
-                                       _lib.farr(steps), N, _lib.fptr(xT), _lib.fptr(nz), seed, _lib.iptr(uid),
-                                       _lib.iptr(ln), int(draw0), _lib.fptr(wav), B, Tc, ws, wsb,
-                                       _lib.stream_ptr(dev)))
+        _lib.check(getattr(lib, fn)(h, _lib.fptr(mel), *[_lib.farr(c) for c in coefs], _lib.farr(steps), N,
+                                    _lib.fptr(xT), _lib.fptr(nz), seed, _lib.iptr(uid), _lib.iptr(ln), *extra,
+                                    _lib.fptr(wav), B, Tc, ws, wsb, _lib.stream_ptr(dev)))
         return wav
+
+    @torch.no_grad()
+    def sample_coefs(self, mel, ce, den, sg, steps, x_T=None, noise=None, seed=None, utt_ids=None, draw0=0,
+                     lens=None):
+        """The reverse loop with explicit per-pass coefficients (fd_sample_coefs): pass j
+        evaluates eps at steps[j] and sets x = (x - ce[j] eps) / den[j] + sg[j] z.  ``lens``: ragged
+        batch, each row's utterance length in mel frames (``sample``)."""
+        return self._sample("fd_sample_coefs", mel, (ce, den, sg), steps, x_T, noise, seed, utt_ids, lens,
+                            extra=(int(draw0),))
 
     @torch.no_grad()
     def sample(self, mel, beta, alpha, sigma, steps, x_T=None, noise=None, seed=None, utt_ids=None, lens=None):
@@ -305,27 +274,8 @@ class FastDiff(nn.Module):
         Missing draws: on-device Philox keyed by ``seed`` and each row's ``utt_ids``.
         lens: ragged batch -- each row's utterance length in mel frames (<= T'); row b's first
         lens[b] * hop samples equal a run of that utterance alone (include/prodiff_hip.h)."""
-        h = self.handle()
-        B, Tc, _ = mel.shape
-        N = len(steps)
-        L = Tc * self.hop_length
-        dev = mel.device
-        mel = mel.float().contiguous()
-        xT = None if x_T is None else x_T.float().reshape(B, L).contiguous()
-        nz = None if noise is None else noise.float().reshape(-1, B, L).contiguous()
-        if nz is not None and nz.shape[0] < N - 1:
-            raise ValueError(f"noise holds {nz.shape[0]} draws, sampler needs {N - 1}")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        wav = torch.empty(B, 1, L, device=dev, dtype=torch.float32)
-        uid = _lib.utt_ids(utt_ids, B, dev)
-        ln = _lib.lens(lens, B, Tc, dev)
-        lib = _lib.lib()
-        ws, wsb = self._ws.get(lib.fd_workspace_size(h, B, Tc, N), dev)
-        _lib.check(lib.fd_sample(h, _lib.fptr(mel), _lib.farr(beta), _lib.farr(alpha), _lib.farr(sigma),
-                                 _lib.farr(steps), N, _lib.fptr(xT), _lib.fptr(nz), seed, _lib.iptr(uid),
-                                 _lib.iptr(ln), _lib.fptr(wav), B, Tc, ws, wsb, _lib.stream_ptr(dev)))
-        return wav
+        return self._sample("fd_sample", mel, (beta, alpha, sigma), steps, x_T, noise, seed, utt_ids, lens,
+                            min_noise=len(steps) - 1)
 
 
 def _pass_coefs(b, a, s, steps, ddim):

@@ -87,28 +87,18 @@ class Generator(nn.Module):
             for k, d in zip(_get(h, "resblock_kernel_sizes"), _get(h, "resblock_dilation_sizes")):
                 self.resblocks.append(rb(c, k, d))
         self.conv_post = nn.Conv1d(ch0 // 2 ** len(rates), 1, 7, 1, padding=3)
-        self._h = None
-        self._sig = None
+        self._native = _lib.NativeHandle("NSF-HiFiGAN", "nsf_create", "nsf_destroy", "nsf_set_option",
+                                         _lib.NSF_OPTIONS, num_params="nsf_num_params")
         self._ws = _lib.Workspace()
-        self.compute_dtype = "fp32"
-        self._options = {}
 
     def set_options(self, **opts):
         """Kernel-variant options (nsf_set_option, include/prodiff_hip.h NSF_OPT_*): small_max."""
-        for k, v in opts.items():
-            if k not in _lib.NSF_OPTIONS:
-                raise ValueError(f"unknown NSF-HiFiGAN option {k!r}")
-            self._options[k] = int(v)
-        self._release()
+        self._native.set_options(opts)
         return self
 
     def set_compute_dtype(self, dtype):
         """"fp32" (exact parity path) or "bf16" (bf16 MFMA GEMMs, fp32 accumulate)."""
-        if dtype not in ("fp32", "bf16"):
-            raise ValueError(dtype)
-        if dtype != self.compute_dtype:
-            self._release()
-            self.compute_dtype = dtype
+        self._native.set_dtype(dtype)
         return self
 
     # ------------------------------------------------------------------ weights
@@ -126,7 +116,6 @@ class Generator(nn.Module):
                 sd[base + ".weight"] = (v.float() * vv.float() / n).to(vv.dtype)
             else:
                 sd[k] = v
-        self._release()
         return super().load_state_dict(sd, strict=strict)
 
     def remove_weight_norm(self):
@@ -157,46 +146,10 @@ class Generator(nn.Module):
         d.harmonic_num = self.harmonic_num
         return d
 
-    def _param_sig(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
     def handle(self):
-        sig = self._param_sig()
-        if self._h is not None and self._sig == sig:
-            return self._h
-        self._release()
-        L = _lib.lib()
-        dev = self.conv_pre.weight.device
-        if dev.type != "cuda":
-            raise _lib.HipError("NSF-HiFiGAN parameters must live on the GPU (call .cuda())")
-        dims = self._dims()
-        params = [v.detach().float().contiguous() for v in self.state_dict().values()]
-        if len(params) != L.nsf_num_params(C_byref(dims)):
-            raise _lib.HipError("parameter count does not match nsf_dims")
-        self._keep = params
-        arr = (_lib.C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        h = _lib.C.c_void_p()
-        dt = _lib.PD_DTYPE_BF16 if self.compute_dtype == "bf16" else _lib.PD_DTYPE_F32
-        _lib.check(L.nsf_create(C_byref(dims), arr, dt, _lib.stream_ptr(dev), _lib.C.byref(h)))
-        for k, v in self._options.items():
-            rc = L.nsf_set_option(h, _lib.NSF_OPTIONS[k], v)
-            if rc != 0:
-                L.nsf_destroy(h)
-                _lib.check(rc)
-        self._h, self._sig = h, sig
-        return h
-
-    def _release(self):
-        if getattr(self, "_h", None) is not None:
-            torch.cuda.synchronize()
-            _lib.lib().nsf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        return self._native.get(
+            self._native.signature(self.parameters()),
+            lambda: (self._dims(), [v.detach().float().contiguous() for v in self.state_dict().values()]))
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -230,10 +183,6 @@ class Generator(nn.Module):
     def forward(self, x, f0, **kw):
         """Reference signature: x [B, num_mels, T] (natural-log mel), f0 [B,T] -> [B,1,T*hop]."""
         return self.synthesize(x.transpose(1, 2).contiguous(), f0, 1.0, **kw)[:, None, :]
-
-
-def C_byref(x):
-    return _lib.C.byref(x)
 
 
 class AttrDict(dict):

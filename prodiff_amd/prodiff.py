@@ -56,25 +56,18 @@ class WaveNet(nn.Module):
         self.skip_projection = nn.Conv1d(C, C, 1)
         self.output_projection = nn.Conv1d(C, in_dims, 1)
         nn.init.zeros_(self.output_projection.weight)
-        self.compute_dtype = "fp32"
-        self._options = {}
-        self._h = None
-        self._sig = None
+        self._native = _lib.NativeHandle("WaveNet", "pd_wavenet_create", "pd_wavenet_destroy",
+                                         "pd_wavenet_set_option", _lib.WN_OPTIONS)
         self._ws = _lib.Workspace()
 
     def set_compute_dtype(self, dtype):
         """'fp32' (exact, the parity path) or 'bf16' (bf16 MFMA, fp32 accumulate)."""
-        if dtype not in ("fp32", "bf16"):
-            raise ValueError(dtype)
-        self.compute_dtype = dtype
+        self._native.set_dtype(dtype)
         return self
 
     def set_options(self, **opts):
         """Kernel-variant options (pd_wavenet_set_option, include/prodiff_hip.h PD_WN_OPT_*): layer."""
-        for k, v in opts.items():
-            if k not in _lib.WN_OPTIONS:
-                raise ValueError(f"unknown WaveNet option {k!r}")
-            self._options[k] = int(v)
+        self._native.set_options(opts)
         return self
 
     # ----------------------------------------------------------- packing
@@ -92,51 +85,17 @@ class WaveNet(nn.Module):
         return out
 
     def param_signature(self):
-        """What the packed handle depends on: dtype, options and every parameter's storage
-        and version (load_state_dict / in-place updates change it)."""
-        ps = self.ordered_params()
-        return (self.compute_dtype, tuple(sorted(self._options.items()))) + tuple((p.data_ptr(), p._version) for p in ps)
+        """What the packed handle depends on (``_lib.NativeHandle.signature``)."""
+        return self._native.signature(self.ordered_params())
+
+    def _pack(self):
+        dims = _lib.pd_wavenet_dims(self.in_dims, self.hidden_size, self.n_layers,
+                                    self.residual_channels, self.dilation_cycle_length)
+        return dims, [p.detach().float().contiguous() for p in self.ordered_params()]
 
     def handle(self):
         """The packed C handle; re-packed whenever a parameter is replaced or modified."""
-        ps = self.ordered_params()
-        sig = self.param_signature()
-        if self._h is not None and sig == self._sig:
-            return self._h
-        L = _lib.lib()
-        dev = ps[0].device
-        if dev.type != "cuda":
-            raise _lib.HipError("WaveNet parameters must live on the GPU (call .cuda())")
-        tensors = [p.detach().float().contiguous() for p in ps]
-        arr = (_lib.C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-        dims = _lib.pd_wavenet_dims(self.in_dims, self.hidden_size, self.n_layers,
-                                    self.residual_channels, self.dilation_cycle_length)
-        h = _lib.C.c_void_p()
-        dt = _lib.PD_DTYPE_BF16 if self.compute_dtype == "bf16" else _lib.PD_DTYPE_F32
-        _lib.check(L.pd_wavenet_create(_lib.C.byref(dims), arr, dt,
-                                       _lib.stream_ptr(dev), _lib.C.byref(h)))
-        for k, v in self._options.items():
-            rc = L.pd_wavenet_set_option(h, _lib.WN_OPTIONS[k], v)
-            if rc != 0:
-                L.pd_wavenet_destroy(h)
-                _lib.check(rc)
-        self._release()
-        self._h, self._sig = h, sig
-        self._keep = tensors   # the pack is stream-ordered; keep sources alive
-        return h
-
-    def _release(self):
-        if self._h is not None:
-            torch.cuda.synchronize()
-            _lib.lib().pd_wavenet_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _lib.lib().pd_wavenet_destroy(self._h)
-        except Exception:
-            pass
+        return self._native.get(self.param_signature(), self._pack)
 
     # ----------------------------------------------------------- forward
     @torch.no_grad()
@@ -168,13 +127,14 @@ class SampleGraph:
     def __init__(self, graph, cond, mel, denoiser, keep=()):
         self.graph, self.cond, self.mel = graph, cond, mel
         self._denoiser = denoiser
-        self._handle = denoiser._h.value
+        self._handle = denoiser._native.h.value
         self._sig = denoiser.param_signature()
         self._keep = keep        # workspace and captured draw buffers stay alive with the graph
 
     def replay(self):
         d = self._denoiser
-        if d._h is None or d._h.value != self._handle or d.param_signature() != self._sig:
+        h = d._native.h
+        if h is None or h.value != self._handle or d.param_signature() != self._sig:
             raise RuntimeError("SampleGraph: the denoiser was re-packed or its parameters changed "
                                "since capture; capture again")
         self.graph.replay()

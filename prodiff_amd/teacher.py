@@ -162,17 +162,14 @@ class ProDiffTeacher(nn.Module):
                                                time_scale=hparams["timescale"], num_features=1,
                                                sampling_algorithm=hparams.get("sampling_algorithm", "euler"),
                                                spec_min=hparams["spec_min"], spec_max=hparams["spec_max"])
-        self.compute_dtype = "fp32"
-        self._h = None
-        self._sig = None
+        self._native = _lib.NativeHandle("ProDiffTeacher", "pd_cond_create", "pd_cond_destroy",
+                                         num_params="pd_cond_num_params")
         self._ws = _lib.Workspace()
 
     def set_compute_dtype(self, dtype):
         """'fp32' (the parity path) or 'bf16' (bf16 MFMA GEMMs, fp32 accumulate) for the condition
         stage and the diffusion."""
-        if dtype not in ("fp32", "bf16"):
-            raise ValueError(dtype)
-        self.compute_dtype = dtype
+        self._native.set_dtype(dtype)
         if hasattr(self, "diffusion"):
             self.diffusion.set_compute_dtype(dtype)
         return self
@@ -208,38 +205,9 @@ class ProDiffTeacher(nn.Module):
 
     def cond_handle(self):
         ps = self.ordered_cond_params()
-        sig = (self.compute_dtype, self.cond_dims().rel_pos) + tuple((p.data_ptr(), p._version) for p in ps)
-        if self._h is not None and sig == self._sig:
-            return self._h
-        L = _lib.lib()
-        dev = ps[0].device
-        if dev.type != "cuda":
-            raise _lib.HipError("ProDiffTeacher parameters must live on the GPU (call .cuda())")
-        tensors = [p.detach().float().contiguous() for p in ps]
-        dims = self.cond_dims()
-        if L.pd_cond_num_params(_lib.C.byref(dims)) != len(tensors):
-            raise _lib.HipError("parameter count does not match pd_cond_num_params")
-        arr = (_lib.C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-        h = _lib.C.c_void_p()
-        dt = _lib.PD_DTYPE_BF16 if self.compute_dtype == "bf16" else _lib.PD_DTYPE_F32
-        _lib.check(L.pd_cond_create(_lib.C.byref(dims), arr, dt, _lib.stream_ptr(dev), _lib.C.byref(h)))
-        self._release()
-        self._h, self._sig = h, sig
-        self._keep = tensors
-        return h
-
-    def _release(self):
-        if self._h is not None:
-            torch.cuda.synchronize()
-            _lib.lib().pd_cond_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _lib.lib().pd_cond_destroy(self._h)
-        except Exception:
-            pass
+        dims = self.cond_dims()   # rel_pos (the table length, which grows) is part of the packed state
+        return self._native.get(self._native.signature(ps, dims.rel_pos),
+                                lambda: (dims, [p.detach().float().contiguous() for p in ps]))
 
     # ----------------------------------------------------------- forward
     @torch.no_grad()

@@ -371,3 +371,79 @@ def test_collate_pad_stack_equals_per_item_pad():
     assert b["ntok"] == [3, 2] and b["nframes"] == [5, 2]
     assert b["txt_tokens"].tolist() == [[1, 2, 3], [1, 2, 0]]
     assert b["mel2ph"].tolist() == [[1] * 5, [1, 1, 0, 0, 0]]
+
+
+# ---------------------------------------------------------------- the shared handle lifecycle
+NSF_SMALL = dict(synth.NSF_DEFAULTS, upsample_initial_channel=32, upsample_rates=(4, 4), upsample_kernel_sizes=(8, 8))
+
+
+def _four_modules():
+    """One small instance of each module that owns a native handle, and the call that packs it."""
+    from prodiff_amd.nsf_hifigan import Generator
+    from prodiff_amd.teacher import ProDiffTeacher
+    wn, fd, g, t = WaveNet(80, 32, 2, 64, 1), FastDiff(), Generator(NSF_SMALL), ProDiffTeacher(40, TEACHER_HP)
+    return [("WaveNet", wn, wn.handle), ("FastDiff", fd, fd.handle), ("NSF-HiFiGAN", g, g.handle),
+            ("ProDiffTeacher", t, t.cond_handle)]
+
+
+def _four_creates():
+    """(create function, dims struct, parameter count) of the four components, small valid dims."""
+    from prodiff_amd.nsf_hifigan import Generator
+    from prodiff_amd.teacher import ProDiffTeacher
+    lib = _lib.lib()
+    fd = _lib.fd_dims(1, 32, 80, 3, (_lib.C.c_int * 4)(8, 8, 4, 0), 4, 3, 64, 3, 128, 512, 512)
+    nsf = Generator(NSF_SMALL)._dims()
+    cond = ProDiffTeacher(40, TEACHER_HP).cond_dims()
+    return [(lib.pd_wavenet_create, _lib.pd_wavenet_dims(80, 32, 2, 64, 1), 6 + 8 * 2 + 4),
+            (lib.fd_create, fd, len(FastDiff()._convs_in_order()) * 2),
+            (lib.nsf_create, nsf, lib.nsf_num_params(_lib.C.byref(nsf))),
+            (lib.pd_cond_create, cond, lib.pd_cond_num_params(_lib.C.byref(cond)))]
+
+
+def _call_create(create, dims, ptrs, dtype):
+    out = _lib.C.c_void_p(0x5a5a)
+    arr = (_lib.C.c_void_p * len(ptrs))(*ptrs)
+    rc = create(_lib.C.byref(dims), arr, dtype, None, _lib.C.byref(out))
+    return rc, _lib.lib().pd_last_error().decode(), out.value
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="hands fake parameter pointers to the library: only where no device can read them")
+@pytest.mark.parametrize("dtype", [_lib.PD_DTYPE_F32, _lib.PD_DTYPE_BF16])
+def test_create_without_a_device_fails_cleanly(dtype):
+    """Without a device every create stops at the weight pool's hipMalloc: PD_ERR_HIP, the pool's
+    error text, the out handle untouched and no device bytes counted as live."""
+    for create, dims, n in _four_creates():
+        rc, msg, out = _call_create(create, dims, [0x1000 + 64 * i for i in range(n)], dtype)
+        assert rc == 2 and "hipMalloc failed for" in msg and msg.endswith("weights"), (create.__name__, rc, msg)
+        assert out == 0x5a5a
+        assert _lib.lib().pd_live_device_bytes() == 0
+
+
+def test_create_names_a_null_parameter():
+    """A null entry in the parameter list is refused before anything is allocated or launched,
+    by the same check in all four components: PD_ERR_ARG and the entry's index."""
+    for create, dims, n in _four_creates():
+        ptrs = [0x1000 + 64 * i for i in range(n)]
+        ptrs[3] = None
+        rc, msg, out = _call_create(create, dims, ptrs, _lib.PD_DTYPE_F32)
+        assert rc == 1 and msg == "argument: null parameter 3", (create.__name__, rc, msg)
+        assert out == 0x5a5a
+        assert _lib.lib().pd_live_device_bytes() == 0
+
+
+def test_unknown_options_and_dtypes_are_refused():
+    for name, m, _ in _four_modules():
+        with pytest.raises(ValueError):
+            m.set_compute_dtype("fp16")
+        assert m.set_compute_dtype("bf16") is m
+        if hasattr(m, "set_options"):
+            with pytest.raises(ValueError, match=f"unknown {name} option 'nope'"):
+                m.set_options(nope=1)
+            assert m.set_options() is m
+    assert [hasattr(m, "set_options") for _, m, _ in _four_modules()] == [True, True, True, False]
+
+
+def test_cpu_parameters_fail_loudly_in_handle():
+    for name, m, handle in _four_modules():
+        with pytest.raises(_lib.HipError, match=f"{name} parameters must live on the GPU"):
+            handle()
