@@ -455,6 +455,120 @@ typedef struct {
 int pd_cond_forward(const pd_cond* h, const pd_cond_inputs* in, float* cond, float* enc_out, int B,
                     int T_txt, int T_mel, void* workspace, size_t ws_bytes, void* stream);
 
+/* ============================================================ variance predictors
+ * The encoders of the pitch and duration predictors, the two models that run before the teacher
+ * when a segment carries no f0 / phoneme durations (handler/infer/handler.py:218-234,262-278).
+ * Both are built on the FFT-block stack of the condition encoder (same kernels, their own widths).
+ *
+ * pd_pitch_cond -- everything of PitchPredictor.forward (modules/variance_predictor/
+ * pitch_predictor.py:57-121) that builds the rectified-flow sampler's `cond`: the phoneme
+ * FastspeechEncoder, the NoteEncoder (tts_modules.py:332-365), note_encode_out_linear, the two
+ * length-regulator gathers and the speaker / retake / delta-pitch embeddings.  The sampler itself is
+ * pd_reflow_sample over the predictor's WaveNet.
+ */
+typedef struct pd_pitch_cond pd_pitch_cond;
+
+typedef struct {
+  int vocab_size;             /* len(ph_encoder); embed_tokens has vocab_size + 1 rows (pitch_predictor.py:14) */
+  int hidden_size;            /* H: 256, multiple of 64                                                        */
+  int enc_layers;             /* 4                                                                             */
+  int enc_ffn_kernel_size;    /* 9 (odd, <= 11)                                                                */
+  int num_heads;              /* 2; head dim in {64, 128, 256}                                                 */
+  int note_hidden_size;       /* Hn: 128 (handler/base_config.yaml:141-145), multiple of 64                    */
+  int note_layers;            /* 4                                                                             */
+  int note_ffn_kernel_size;   /* 9                                                                             */
+  int note_heads;             /* 2                                                                             */
+  int num_spk;                /* spk_embed rows = len(hparams['datasets'])                                     */
+  int use_spk_id;
+} pd_pitch_cond_dims;
+
+/* Parameter order = the reference state-dict order (buffers and `diffusion.*` skipped), fp32:
+ *   encoder.layers.l.op.* (the ten of pd_cond) for l < enc_layers, encoder.layer_norm.{weight,bias},
+ *   encoder.embed_tokens.weight [V+1,H], dur_embed.{weight [H,1],bias},
+ *   note_encoder.layers.l.op.* for l < note_layers, note_encoder.layer_norm.{weight,bias},
+ *   note_encoder.note_midi_embed.{weight [Hn,1],bias}, note_encoder.note_dur_embed.{weight [Hn,1],bias},
+ *   note_encode_out_linear.{weight [H,Hn],bias}, [spk_embed.weight [num_spk,H]],
+ *   delta_pitch_embed.{weight [H,1],bias}, pitch_retake_embed.weight [2,H]. */
+int pd_pitch_cond_num_params(const pd_pitch_cond_dims* dims);
+int pd_pitch_cond_create(const pd_pitch_cond_dims* dims, const float* const* params, int dtype, void* stream,
+                         pd_pitch_cond** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
+void pd_pitch_cond_destroy(pd_pitch_cond* h);
+size_t pd_pitch_cond_workspace_size(const pd_pitch_cond* h, int B, int T_txt, int T_note, int T_mel);
+
+/* PitchPredictor.forward's inputs, device pointers, NULL when absent:
+ *   txt_tokens [B,T_txt] int64 (0 = padding), mel2ph [B,T_mel] int64 (0 = padding frame, else token + 1),
+ *   note_midi [B,T_note] float (< 0 = padding note), note_rest [B,T_note] bytes (torch.bool),
+ *   mel2note [B,T_mel] int64 (0 = padding frame, else note + 1), spk_id [B] int64 (required with
+ *   use_spk_id), pitch_expr [B] float, pitch / base_pitch [B,T_mel] float and pitch_retake [B,T_mel]
+ *   bytes (torch.bool).  With r = pitch_retake (1 everywhere when it is NULL):
+ *     retake = pitch_expr ? E[1] e + E[0] (1 - e), e = pitch_expr[b] r   :   E[r]       (E = pitch_retake_embed)
+ *     delta  = pitch_retake ? (pitch - base_pitch) [!r] : 0             (pitch and base_pitch then required)
+ *   txt_lens / note_lens: ragged batches (B ints each, or NULL) as pd_cond_inputs.txt_lens -- every row then
+ *   equals the segment encoded alone.
+ * Ids outside their tables are clamped; mel2ph / mel2note values outside [1, T_txt] / [1, T_note] gather a zero
+ * row: a malformed input cannot fault the GPU. */
+typedef struct {
+  const long long* txt_tokens;
+  const long long* mel2ph;
+  const float* note_midi;
+  const unsigned char* note_rest;
+  const long long* mel2note;
+  const long long* spk_id;
+  const float* pitch_expr;
+  const float* pitch;
+  const float* base_pitch;
+  const unsigned char* pitch_retake;
+  const int* txt_lens;
+  const int* note_lens;
+} pd_pitch_cond_inputs;
+
+/* cond [B,T_mel,H] time-major (what pd_reflow_sample takes):
+ *   cond[f] = pad0(enc)[mel2ph[f]] + pad0(note_lin)[mel2note[f]] + spk + retake + (delta w + b)
+ * with no final mel2ph > 0 mask (the reference has none: padding frames keep spk + retake + delta). */
+int pd_pitch_cond_forward(const pd_pitch_cond* h, const pd_pitch_cond_inputs* in, float* cond, int B, int T_txt,
+                          int T_note, int T_mel, void* workspace, size_t ws_bytes, void* stream);
+
+/* pd_dur -- DurPredictor.forward (modules/variance_predictor/dur_predictor.py:31-36): the
+ * FastspeechEncoder with extra_embed = onset_embed(onset) + word_dur_embed(word_dur), then
+ * DurationPredictor (tts_modules.py:59-132): n_layers x (k-tap conv, ReLU, LayerNorm eps 1e-12,
+ * padding mask), a Linear to one value per token, the mask again, and out2dur. */
+typedef struct pd_dur pd_dur;
+
+typedef struct {
+  int vocab_size;
+  int hidden_size, enc_layers, enc_ffn_kernel_size, num_heads;   /* as pd_cond_dims */
+  int n_layers;               /* 5   (handler/base_config.yaml:120-126) */
+  int n_chans;                /* 512, multiple of 32                     */
+  int kernel_size;            /* 3 (odd, <= 11)                          */
+  float log_offset;           /* 1.0                                     */
+} pd_dur_dims;
+
+/* Parameter order = the reference state-dict order: the encoder's (as above, embed_tokens [V,H]),
+ * onset_embed.weight [2,H], word_dur_embed.{weight [H,1],bias}, for i < n_layers:
+ * dur_pred.conv.i.1.{weight [C,Cin,k],bias}, dur_pred.conv.i.3.{weight,bias}, then
+ * dur_pred.linear.{weight [1,C],bias}. */
+int pd_dur_num_params(const pd_dur_dims* dims);
+int pd_dur_create(const pd_dur_dims* dims, const float* const* params, int dtype, void* stream, pd_dur** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
+void pd_dur_destroy(pd_dur* h);
+size_t pd_dur_workspace_size(const pd_dur* h, int B, int T_txt);
+
+/* txt_tokens [B,T_txt] int64 (0 = padding), onset [B,T_txt] int64 in {0,1} (clamped), word_dur [B,T_txt]
+ * float, txt_lens as pd_cond_inputs.txt_lens. */
+typedef struct {
+  const long long* txt_tokens;
+  const long long* onset;
+  const float* word_dur;
+  const int* txt_lens;
+} pd_dur_inputs;
+
+/* log_out [B,T_txt]: the log-domain prediction (linear output times the padding mask, tts_modules.py:126-127);
+ * dur_out [B,T_txt]: max(exp(log_out) - log_offset, 0), DurationPredictor.forward(infer=True).  Either may be
+ * NULL, not both. */
+int pd_dur_forward(const pd_dur* h, const pd_dur_inputs* in, float* log_out, float* dur_out, int B, int T_txt,
+                   void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

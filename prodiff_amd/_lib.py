@@ -62,6 +62,31 @@ class pd_cond_inputs(C.Structure):
                 ("voicing", C.c_void_p), ("breath", C.c_void_p), ("txt_lens", C.c_void_p)]
 
 
+class pd_pitch_cond_dims(C.Structure):
+    _fields_ = [("vocab_size", C.c_int), ("hidden_size", C.c_int), ("enc_layers", C.c_int),
+                ("enc_ffn_kernel_size", C.c_int), ("num_heads", C.c_int), ("note_hidden_size", C.c_int),
+                ("note_layers", C.c_int), ("note_ffn_kernel_size", C.c_int), ("note_heads", C.c_int),
+                ("num_spk", C.c_int), ("use_spk_id", C.c_int)]
+
+
+class pd_pitch_cond_inputs(C.Structure):
+    _fields_ = [("txt_tokens", C.c_void_p), ("mel2ph", C.c_void_p), ("note_midi", C.c_void_p),
+                ("note_rest", C.c_void_p), ("mel2note", C.c_void_p), ("spk_id", C.c_void_p),
+                ("pitch_expr", C.c_void_p), ("pitch", C.c_void_p), ("base_pitch", C.c_void_p),
+                ("pitch_retake", C.c_void_p), ("txt_lens", C.c_void_p), ("note_lens", C.c_void_p)]
+
+
+class pd_dur_dims(C.Structure):
+    _fields_ = [("vocab_size", C.c_int), ("hidden_size", C.c_int), ("enc_layers", C.c_int),
+                ("enc_ffn_kernel_size", C.c_int), ("num_heads", C.c_int), ("n_layers", C.c_int),
+                ("n_chans", C.c_int), ("kernel_size", C.c_int), ("log_offset", C.c_float)]
+
+
+class pd_dur_inputs(C.Structure):
+    _fields_ = [("txt_tokens", C.c_void_p), ("onset", C.c_void_p), ("word_dur", C.c_void_p),
+                ("txt_lens", C.c_void_p)]
+
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -104,6 +129,17 @@ _SIGS = {
     "pd_cond_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
     "pd_cond_forward": (C.c_int, [_VP, C.POINTER(pd_cond_inputs), _VP, _VP, C.c_int, C.c_int, C.c_int, _VP,
                                   C.c_size_t, _VP]),
+    "pd_pitch_cond_num_params": (C.c_int, [C.POINTER(pd_pitch_cond_dims)]),
+    "pd_pitch_cond_create": (C.c_int, [C.POINTER(pd_pitch_cond_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
+    "pd_pitch_cond_destroy": (None, [_VP]),
+    "pd_pitch_cond_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pd_pitch_cond_forward": (C.c_int, [_VP, C.POINTER(pd_pitch_cond_inputs), _VP, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_dur_num_params": (C.c_int, [C.POINTER(pd_dur_dims)]),
+    "pd_dur_create": (C.c_int, [C.POINTER(pd_dur_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
+    "pd_dur_destroy": (None, [_VP]),
+    "pd_dur_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "pd_dur_forward": (C.c_int, [_VP, C.POINTER(pd_dur_inputs), _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "nsf_num_params": (C.c_int, [C.POINTER(nsf_dims)]),
     "nsf_create": (C.c_int, [C.POINTER(nsf_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
     "nsf_destroy": (None, [_VP]),

@@ -17,20 +17,22 @@
 //                -> FFN linear GEMM (+ residual)
 //   enc_ln (final LayerNorm * mask) -> enc_cond (length-regulator gather + variance sums)
 // The GEMMs are the implicit-GEMM Conv1d engine (gemm.h) -- MFMA fp32 or bf16.
+// The embedding launcher, the per-layer sequence and its weights / workspace are the shared
+// FFT-block stack of fft_stack.h (defined here), which variance.hip instantiates at its own
+// widths; the padding mask is a per-token array the embedding kernel writes.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "../../include/prodiff_hip.h"
 #include "common.h"
+#include "fft_stack.h"
 #include "gemm.h"
 #include "kernels.h"
 
 using namespace pd;
 
 namespace {
-
-enum EncUse { U_ENC_QKV = 30, U_ENC_OUT = 31, U_ENC_FFN1 = 32, U_ENC_FFN2 = 33 };
 
 // ---------------------------------------------------------------- embeddings
 // FastspeechEncoder.forward_embedding (tts_modules.py:319-330) with the teacher's
@@ -46,13 +48,21 @@ enum EncUse { U_ENC_QKV = 30, U_ENC_OUT = 31, U_ENC_FFN1 = 32, U_ENC_FFN2 = 33 }
 //    q = max(P, T) - 1 - t (reversed positions; P = the rows of the reference's table, 5000 at
 //    first and the longest input seen since: pd_cond_dims.rel_pos), g_i = exp(2i (-ln(1e4)/H))
 //    (espnet_positional_embedding.py:24-45,108-115; FFTBlocks masks the padding, tts_modules.py:274).
+//  * the duration predictor's front end (TokEmbedArgs.onset_emb): extra = onset_emb[onset] + (word_dur w + b).
+//  * mask[t] = [tok != 0], the padding mask the FFT-block stack reads.
 constexpr int EMB_TOK = 8;
 
-__global__ __launch_bounds__(256) void enc_embed_kernel(
-    const long long* __restrict__ tok, const long long* __restrict__ lang, const long long* __restrict__ mel2ph,
-    int Tt, int Tm, int H, const float* __restrict__ emb, int V, float scale, const float* __restrict__ dur_w,
-    const float* __restrict__ dur_b, const float* __restrict__ lang_emb, int NL, float neg_freq, int rel_pos,
-    float neg_rel, float* __restrict__ x) {
+__global__ __launch_bounds__(256) void enc_embed_kernel(const TokEmbedArgs a, float scale, float neg_freq,
+                                                        float neg_rel) {
+  const long long* __restrict__ tok = a.tok;
+  const long long* __restrict__ lang = a.lang;
+  const long long* __restrict__ mel2ph = a.mel2ph;
+  const int Tt = a.Tt, Tm = a.Tm, H = a.H, V = a.V, NL = a.NL, rel_pos = a.rel_pos;
+  const float* __restrict__ emb = a.emb;
+  const float* __restrict__ dur_w = a.dur_w;
+  const float* __restrict__ dur_b = a.dur_b;
+  const float* __restrict__ lang_emb = a.lang_emb;
+  float* __restrict__ x = a.x;
   const int b = blockIdx.y, t0 = blockIdx.x * EMB_TOK, tid = threadIdx.x;
   __shared__ int cnt[EMB_TOK];
   __shared__ int npre;
@@ -95,6 +105,10 @@ __global__ __launch_bounds__(256) void enc_embed_kernel(
     // clamped so a bad input cannot fault the device
     const float* er = emb + min(max(id, 0ll), (long long)V - 1) * H;
     const float* lr = lang ? lang_emb + min(max(lang[(long long)b * Tt + t], 0ll), (long long)NL - 1) * H : nullptr;
+    // DurPredictor's extra_embed (dur_predictor.py:32-33): onset_embed(onset) + word_dur_embed(word_dur)
+    const float* orow = a.onset_emb ? a.onset_emb + min(max(a.onset[(long long)b * Tt + t], 0ll), 1ll) * H : nullptr;
+    const float wd = a.onset_emb ? a.word_dur[(long long)b * Tt + t] : 0.f;
+    if (tid == 0) a.mask[(long long)b * Tt + t] = np;
     const float d = (float)cnt[j];
     const float p = (float)pos[j];
     float* xr = x + ((long long)b * Tt + t) * H;
@@ -102,6 +116,7 @@ __global__ __launch_bounds__(256) void enc_embed_kernel(
       float extra = 0.f;
       if (dur_w) extra = d * dur_w[c] + dur_b[c];
       if (lr) extra = extra + lr[c];
+      if (orow) extra = orow[c] + (wd * a.wd_w[c] + a.wd_b[c]);
       float v;
       if (rel_pos) {
         const int P = rel_pos > 5000 ? rel_pos : 5000;   // the reference table never has fewer than 5000 rows
@@ -125,11 +140,11 @@ __global__ __launch_bounds__(256) void enc_embed_kernel(
 // previous sub-layer (:666,673, tts_modules.py:285) -- then y = LN(x).  mode 1 (FFTBlocks'
 // final norm, :286-287): y = LN(x) * mask.  Two-pass fp32 moments, eps as the module's.
 __global__ __launch_bounds__(256) void enc_ln_kernel(float* __restrict__ x, const float* __restrict__ g,
-                                                     const float* __restrict__ bta, const long long* __restrict__ tok,
+                                                     const float* __restrict__ bta, const int* __restrict__ mask,
                                                      float* __restrict__ y, int rows, int H, float eps, int mode) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (r >= rows) return;
-  const bool pad = tok[r] == 0;
+  const bool pad = mask[r] == 0;
   float* xr = x + (long long)r * H;
   float* yr = y + (long long)r * H;
   if (mode == 1 && pad) {
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(256) void enc_ln_kernel(float* __restrict__ x, cons
 constexpr int AQ = 32, AK = 32;
 
 template <int D>
-__global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__ qkv, const long long* __restrict__ tok,
+__global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ mask,
                                                        float* __restrict__ out, int Tt, int H, float qscale) {
   constexpr int LD = D + 4;
   constexpr int ND4 = D / 4;
@@ -211,7 +226,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const float* __restrict__
       *reinterpret_cast<float4*>(Ks + r * LD + 4 * c4) = kv;
       *reinterpret_cast<float4*>(Vs + r * LD + 4 * c4) = vv;
     }
-    if (tid < AK) kval[tid] = (k0 + tid < Tt) && tok[row0 + k0 + tid] != 0;
+    if (tid < AK) kval[tid] = (k0 + tid < Tt) && mask[row0 + k0 + tid] != 0;
     __syncthreads();
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     const float* qr = Qs + q * LD;
@@ -334,65 +349,189 @@ __global__ __launch_bounds__(256) void enc_cond_kernel(const CondArgs a) {
   }
 }
 
-// GEMM tile by grid size: 128 x 64 tiles once they give every CU a block, else 32 x 128 tiles
-// with the K axis split over up to 8 blocks (the B = 1 encoder has a few hundred rows: its
-// 32-deep K steps run back to back on ~30 blocks otherwise, latency-bound).
-bool enc_big_tile(long long rows, int N) { return (long long)cdiv(rows, 128) * cdiv(N, 64) >= 256; }
-int enc_ksplit(long long rows, int N, int K) {
-  if (enc_big_tile(rows, N)) return 1;
-  const long long gxy = (long long)cdiv(rows, 32) * cdiv(N, 128);
-  int ks = (int)std::min<long long>(8, (256 + gxy - 1) / gxy);
-  ks = std::min(ks, std::max(1, K / GEMM_BK / 4));   // >= 4 K steps per block
-  return std::max(ks, 1);
-}
-
-template <int EPI, int ID>
-int enc_gemm(GemmArgs a, float* part, hipStream_t st, const char* tag) {
-  const long long rows = (long long)a.B * a.T;
-  if (enc_big_tile(rows, a.N)) return launch_gemm<1, 2, 4, 1, EPI, ID>(a, st, tag);
-  a.ksplit = enc_ksplit(rows, a.N, a.ldw);
-  a.part = part;
-  return launch_gemm<1, 1, 1, 4, EPI, ID>(a, st, tag);
-}
-
 }  // namespace
+
+// ---------------------------------------------------------------- the shared stack (fft_stack.h)
+namespace pd {
+
+int FftStack::init(int hidden, int layers, int ffn_kernel, int num_heads, const char* who) {
+  const std::string w(who);
+  PD_CHECK_ARG(hidden > 0 && hidden % 64 == 0, w + ": hidden_size must be a positive multiple of 64");
+  PD_CHECK_ARG(num_heads > 0 && hidden % num_heads == 0, w + ": hidden_size % num_heads != 0");
+  const int d = hidden / num_heads;
+  if (d != 64 && d != 128 && d != 256) {
+    set_error(w + ": head dim (hidden_size / num_heads) must be 64, 128 or 256");
+    return PD_ERR_UNSUPPORTED;
+  }
+  PD_CHECK_ARG(ffn_kernel % 2 == 1 && ffn_kernel > 0 && ffn_kernel <= MAX_SEGS,
+               w + ": ffn kernel size must be odd and <= 11 (SAME padding)");
+  PD_CHECK_ARG(layers >= 0, w + ": bad layer count");
+  H = hidden; L = layers; K = ffn_kernel; heads = num_heads; D = d; F = 4 * hidden;
+  return PD_OK;
+}
+
+void FftStack::plan(WeightPool& wp) {
+  ln1g.resize(L); ln1b.resize(L); Wqkv.resize(L); Wo.resize(L); ln2g.resize(L);
+  ln2b.resize(L); W1.resize(L); b1.resize(L); W2.resize(L); b2.resize(L);
+  // GEMM weights packed as W[n][k]
+  for (int l = 0; l < L; ++l) {
+    wp.add(&ln1g[l], H); wp.add(&ln1b[l], H);
+    wp.add(&Wqkv[l], (size_t)3 * H * H); wp.add(&Wo[l], (size_t)H * H);
+    wp.add(&ln2g[l], H); wp.add(&ln2b[l], H);
+    wp.add(&W1[l], (size_t)F * K * H); wp.add(&b1[l], F);
+    wp.add(&W2[l], (size_t)H * F); wp.add(&b2[l], H);
+  }
+  wp.add(&lnfg, H); wp.add(&lnfb, H);
+}
+
+int FftStack::pack(const float* const* params, int& p, hipStream_t st) {
+  auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
+  for (int l = 0; l < L; ++l) {
+    PD_TRY(cp(ln1g[l], params[p++], H));
+    PD_TRY(cp(ln1b[l], params[p++], H));
+    PD_TRY(cp(Wqkv[l], params[p++], (size_t)3 * H * H));   // in_proj_weight [3H, H] = W[n][k]
+    PD_TRY(cp(Wo[l], params[p++], (size_t)H * H));
+    PD_TRY(cp(ln2g[l], params[p++], H));
+    PD_TRY(cp(ln2b[l], params[p++], H));
+    PD_TRY(pack_conv(W1[l], K * H, 0, 0, H, params[p++], F, H, K, st));   // ffn_1 [F, H, K]
+    PD_TRY(cp(b1[l], params[p++], F));
+    PD_TRY(cp(W2[l], params[p++], (size_t)H * F));
+    PD_TRY(cp(b2[l], params[p++], H));
+  }
+  PD_TRY(cp(lnfg, params[p++], H));
+  PD_TRY(cp(lnfb, params[p++], H));
+  return PD_OK;
+}
+
+FftWs fft_ws(const FftStack& s, size_t R, size_t base) {
+  auto al = [](size_t n) { return (n + 63) / 64 * 64; };
+  FftWs w{};
+  size_t o = base;
+  w.mask = o; o += al(R);
+  w.x = o; o += al(R * s.H);
+  w.h = o; o += al(R * s.H);
+  w.qkv = o; o += al(R * 3 * s.H);
+  w.att = o; o += al(R * s.H);
+  w.f = o; o += al(R * s.F);
+  // split-K partial sums: the largest ksplit * rows * N over the four GEMMs
+  const int H = s.H, F = s.F;
+  size_t part = 0;
+  const int NK[4][2] = {{3 * H, H}, {H, H}, {F, s.K * H}, {H, F}};
+  for (auto& nk : NK) part = std::max(part, enc_part_floats(R, nk[0], nk[1]));
+  w.part = o; o += al(part);
+  w.end = o;
+  return w;
+}
+
+int fft_layer_norm(float* x, const float* g, const float* b, const int* mask, float* y, int rows, int H, float eps,
+                   int mode, hipStream_t st) {
+  {
+    ProfScope ps("enc_ln", st);
+    hipLaunchKernelGGL(enc_ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, g, b, mask, y, rows, H, eps, mode);
+  }
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+int fft_embed_tokens(TokEmbedArgs a, int B, hipStream_t st) {
+  const int H = a.H;
+  const float neg_freq = (float)(-(std::log(10000.0) / (H / 2 - 1)));
+  const float neg_rel = (float)(-(std::log(10000.0) / H));
+  {
+    ProfScope ps("enc_embed", st);
+    hipLaunchKernelGGL(enc_embed_kernel, dim3(cdiv(a.Tt, EMB_TOK), B), dim3(256), 0, st, a,
+                       (float)std::sqrt((double)H), neg_freq, neg_rel);
+  }
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+template <int ID0>
+int fft_stack_forward(const FftStack& s, float* ws, const FftWs& w, const int* lens, float* out, int B, int T,
+                      hipStream_t st) {
+  const int H = s.H, F = s.F, K = s.K;
+  const int rows = B * T;
+  const long long bs = (long long)T;
+  const int* mask = reinterpret_cast<const int*>(ws + w.mask);
+  float* x = ws + w.x;
+  float* hn = ws + w.h;
+  float* qkv = ws + w.qkv;
+  float* att = ws + w.att;
+  float* ff = ws + w.f;
+  float* part = ws + w.part;
+  const float eps = 1e-5f;
+  const float qscale = (float)std::sqrt(1.0 / (double)s.D);
+  for (int l = 0; l < s.L; ++l) {
+    PD_TRY(fft_layer_norm(x, s.ln1g[l], s.ln1b[l], mask, hn, rows, H, eps, 0, st));
+    {
+      GemmArgs a = make_gemm(B, T, 3 * H, s.Wqkv[l], H, nullptr, qkv, bs * 3 * H, 3 * H);
+      add_seg(a, make_seg(hn, bs * H, H, H, 0));
+      PD_TRY((enc_gemm<EPI_STORE, ID0>(a, part, st, "enc_qkv")));
+    }
+    {
+      ProfScope ps("enc_attn", st);
+      dim3 grid(cdiv(T, AQ), s.heads, B);
+      if (s.D == 64)
+        hipLaunchKernelGGL(enc_attn_kernel<64>, grid, dim3(256), 0, st, qkv, mask, att, T, H, qscale);
+      else if (s.D == 128)
+        hipLaunchKernelGGL(enc_attn_kernel<128>, grid, dim3(256), 0, st, qkv, mask, att, T, H, qscale);
+      else
+        hipLaunchKernelGGL(enc_attn_kernel<256>, grid, dim3(256), 0, st, qkv, mask, att, T, H, qscale);
+    }
+    PD_LAUNCH_CHECK();
+    {   // x = x + attn Wo^T   (out_proj, bias=False; residual, common_layers.py:658-665)
+      GemmArgs a = make_gemm(B, T, H, s.Wo[l], H, nullptr, x, bs * H, H);
+      add_seg(a, make_seg(att, bs * H, H, H, 0));
+      a.res = x; a.res_bs = bs * H; a.res_ld = H;
+      PD_TRY((enc_gemm<EPI_STORE, ID0 + 1>(a, part, st, "enc_outproj")));
+    }
+    PD_TRY(fft_layer_norm(x, s.ln2g[l], s.ln2b[l], mask, hn, rows, H, eps, 0, st));
+    {   // f = gelu(k^-0.5 (conv_k(hn) + b1))   (TransformerFFNLayer, common_layers.py:570-576)
+      GemmArgs a = make_gemm(B, T, F, s.W1[l], K * H, s.b1[l], ff, bs * F, F);
+      for (int tap = 0; tap < K; ++tap) add_seg(a, make_seg(hn, bs * H, H, H, tap - K / 2));
+      a.lens = lens; a.lens_mul = 1;   // ragged token batch: zero past each row's own tokens
+      a.act = ACT_GELU;
+      a.alpha = (float)std::pow((double)K, -0.5);
+      PD_TRY((enc_gemm<EPI_STORE, ID0 + 2>(a, part, st, "enc_ffn1")));
+    }
+    {   // x = x + (f W2^T + b2)   (ffn_2, residual, :667-672)
+      GemmArgs a = make_gemm(B, T, H, s.W2[l], F, s.b2[l], x, bs * H, H);
+      add_seg(a, make_seg(ff, bs * F, F, F, 0));
+      a.res = x; a.res_bs = bs * H; a.res_ld = H;
+      PD_TRY((enc_gemm<EPI_STORE, ID0 + 3>(a, part, st, "enc_ffn2")));
+    }
+  }
+  return fft_layer_norm(x, s.lnfg, s.lnfb, mask, out, rows, H, eps, 1, st);
+}
+
+template int fft_stack_forward<U_ENC_BASE>(const FftStack&, float*, const FftWs&, const int*, float*, int, int, hipStream_t);
+template int fft_stack_forward<U_PITCH_PH_BASE>(const FftStack&, float*, const FftWs&, const int*, float*, int, int, hipStream_t);
+template int fft_stack_forward<U_PITCH_NOTE_BASE>(const FftStack&, float*, const FftWs&, const int*, float*, int, int, hipStream_t);
+template int fft_stack_forward<U_DUR_ENC_BASE>(const FftStack&, float*, const FftWs&, const int*, float*, int, int, hipStream_t);
+
+}  // namespace pd
 
 struct pd_cond {
   pd_cond_dims d;
-  int H, L, K, heads, D, F;
-  WeightPool weights;   // every float* below points into it
-  // per layer
-  std::vector<float*> ln1g, ln1b, Wqkv, Wo, ln2g, ln2b, W1, b1, W2, b2;
-  float *lnfg = nullptr, *lnfb = nullptr, *emb = nullptr, *dur_w = nullptr, *dur_b = nullptr;
+  int H;
+  WeightPool weights;   // every float* below, and the stack's, points into it
+  FftStack enc;
+  float *emb = nullptr, *dur_w = nullptr, *dur_b = nullptr;
   float *spk = nullptr, *gender = nullptr, *lang = nullptr, *pw = nullptr, *pb = nullptr;
   float *vw = nullptr, *vb = nullptr, *bw = nullptr, *bb = nullptr;
 };
 
 namespace {
 struct CondWs {
-  size_t x, h, qkv, att, f, enc, part, total;
+  FftWs s;
+  size_t enc, total;
 };
 CondWs cond_ws(const pd_cond* h, int B, int Tt) {
   const size_t R = (size_t)B * Tt;
-  auto al = [](size_t n) { return (n + 63) / 64 * 64; };
   CondWs w{};
-  size_t o = 0;
-  w.x = o; o += al(R * h->H);
-  w.h = o; o += al(R * h->H);
-  w.qkv = o; o += al(R * 3 * h->H);
-  w.att = o; o += al(R * h->H);
-  w.f = o; o += al(R * h->F);
-  w.enc = o; o += al(R * h->H);
-  // split-K partial sums: the largest ksplit * rows * N over the four GEMMs
-  const int H = h->H, F = h->F;
-  size_t part = 0;
-  const int NK[4][2] = {{3 * H, H}, {H, H}, {F, h->K * H}, {H, F}};
-  for (auto& nk : NK) {
-    const int ks = enc_ksplit((long long)R, nk[0], nk[1]);
-    if (ks > 1) part = std::max(part, (size_t)ks * R * nk[0]);
-  }
-  w.part = o; o += al(part);
-  w.total = o * sizeof(float);
+  w.s = fft_ws(h->enc, R, 0);
+  w.enc = w.s.end;
+  w.total = (w.enc + (R * h->H + 63) / 64 * 64) * sizeof(float);
   return w;
 }
 }  // namespace
@@ -409,17 +548,12 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
   PD_CHECK_ARG(dims && params && out, "null pointer");
   const pd_cond_dims& d = *dims;
   PD_CHECK_ARG(dtype == PD_DTYPE_F32 || dtype == PD_DTYPE_BF16, "dtype must be PD_DTYPE_F32 or PD_DTYPE_BF16");
-  PD_CHECK_ARG(d.hidden_size > 0 && d.hidden_size % 64 == 0, "hidden_size must be a positive multiple of 64");
-  PD_CHECK_ARG(d.num_heads > 0 && d.hidden_size % d.num_heads == 0, "hidden_size % num_heads != 0");
-  PD_CHECK_ARG(d.rel_pos >= 0, "rel_pos must be >= 0 (0: sinusoid; > 0: table of max(rel_pos, 5000) rows)");
-  const int D = d.hidden_size / d.num_heads;
-  if (D != 64 && D != 128 && D != 256) {
-    set_error("pd_cond: head dim (hidden_size / num_heads) must be 64, 128 or 256");
-    return PD_ERR_UNSUPPORTED;
+  {
+    FftStack probe;
+    PD_TRY(probe.init(d.hidden_size, d.enc_layers, d.enc_ffn_kernel_size, d.num_heads, "pd_cond"));
   }
-  PD_CHECK_ARG(d.enc_ffn_kernel_size % 2 == 1 && d.enc_ffn_kernel_size <= MAX_SEGS,
-               "enc_ffn_kernel_size must be odd and <= 11 (SAME padding)");
-  PD_CHECK_ARG(d.enc_layers >= 0 && d.vocab_size > 0, "bad enc_layers / vocab_size");
+  PD_CHECK_ARG(d.rel_pos >= 0, "rel_pos must be >= 0 (0: sinusoid; > 0: table of max(rel_pos, 5000) rows)");
+  PD_CHECK_ARG(d.vocab_size > 0, "bad vocab_size");
   PD_CHECK_ARG(!d.use_spk_id || d.num_spk > 0, "num_spk must be positive with use_spk_id");
   PD_CHECK_ARG(!d.use_lang_id || d.num_langs > 0, "num_langs must be positive with use_lang_id");
   // add_gender_embed looks the ids up in lang_embed (prodiff_teacher.py:91-95), so gender ids need it
@@ -428,21 +562,12 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
   hipStream_t st = (hipStream_t)stream;
   pd_cond* h = new pd_cond();
   h->d = d;
-  h->H = d.hidden_size; h->L = d.enc_layers; h->K = d.enc_ffn_kernel_size;
-  h->heads = d.num_heads; h->D = D; h->F = 4 * d.hidden_size;
-  const int H = h->H, F = h->F, K = h->K, L = h->L;
-  // pool layout (floats, 64-aligned); GEMM weights packed as W[n][k]
+  h->H = d.hidden_size;
+  h->enc.init(d.hidden_size, d.enc_layers, d.enc_ffn_kernel_size, d.num_heads, "pd_cond");   // checked above
+  const int H = h->H;
+  // pool layout (floats, 64-aligned)
   WeightPool& wp = h->weights;
-  h->ln1g.resize(L); h->ln1b.resize(L); h->Wqkv.resize(L); h->Wo.resize(L); h->ln2g.resize(L);
-  h->ln2b.resize(L); h->W1.resize(L); h->b1.resize(L); h->W2.resize(L); h->b2.resize(L);
-  for (int l = 0; l < L; ++l) {
-    wp.add(&h->ln1g[l], H); wp.add(&h->ln1b[l], H);
-    wp.add(&h->Wqkv[l], (size_t)3 * H * H); wp.add(&h->Wo[l], (size_t)H * H);
-    wp.add(&h->ln2g[l], H); wp.add(&h->ln2b[l], H);
-    wp.add(&h->W1[l], (size_t)F * K * H); wp.add(&h->b1[l], F);
-    wp.add(&h->W2[l], (size_t)H * F); wp.add(&h->b2[l], H);
-  }
-  wp.add(&h->lnfg, H); wp.add(&h->lnfb, H);
+  h->enc.plan(wp);
   wp.add(&h->emb, (size_t)d.vocab_size * H);
   if (d.use_dur_embed) { wp.add(&h->dur_w, H); wp.add(&h->dur_b, H); }
   if (d.use_spk_id) wp.add(&h->spk, (size_t)d.num_spk * H);
@@ -455,20 +580,7 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
     PD_TRY(wp.commit(st, "condition-encoder"));
     auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
     int p = 0;
-    for (int l = 0; l < L; ++l) {
-      PD_TRY(cp(h->ln1g[l], params[p++], H));
-      PD_TRY(cp(h->ln1b[l], params[p++], H));
-      PD_TRY(cp(h->Wqkv[l], params[p++], (size_t)3 * H * H));   // in_proj_weight [3H, H] = W[n][k]
-      PD_TRY(cp(h->Wo[l], params[p++], (size_t)H * H));
-      PD_TRY(cp(h->ln2g[l], params[p++], H));
-      PD_TRY(cp(h->ln2b[l], params[p++], H));
-      PD_TRY(pack_conv(h->W1[l], K * H, 0, 0, H, params[p++], F, H, K, st));   // ffn_1 [F, H, K]
-      PD_TRY(cp(h->b1[l], params[p++], F));
-      PD_TRY(cp(h->W2[l], params[p++], (size_t)H * F));
-      PD_TRY(cp(h->b2[l], params[p++], H));
-    }
-    PD_TRY(cp(h->lnfg, params[p++], H));
-    PD_TRY(cp(h->lnfb, params[p++], H));
+    PD_TRY(h->enc.pack(params, p, st));
     PD_TRY(cp(h->emb, params[p++], (size_t)d.vocab_size * H));
     if (d.use_dur_embed) { PD_TRY(cp(h->dur_w, params[p++], H)); PD_TRY(cp(h->dur_b, params[p++], H)); }
     if (d.use_spk_id) PD_TRY(cp(h->spk, params[p++], (size_t)d.num_spk * H));
@@ -516,84 +628,17 @@ int pd_cond_forward(const pd_cond* h, const pd_cond_inputs* in, float* cond, flo
   if (ws_bytes < w.total) { set_error("workspace too small"); return PD_ERR_WORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  const int H = h->H, F = h->F, K = h->K;
-  const int rows = B * T_txt;
-  const long long bs = (long long)T_txt;
-  float* x = ws + w.x;
-  float* hn = ws + w.h;
-  float* qkv = ws + w.qkv;
-  float* att = ws + w.att;
-  float* ff = ws + w.f;
+  const int H = h->H;
   float* enc = enc_out ? enc_out : ws + w.enc;
-  float* part = ws + w.part;
-  const float neg_freq = (float)(-(std::log(10000.0) / (H / 2 - 1)));
-  const float neg_rel = (float)(-(std::log(10000.0) / H));
   {
-    ProfScope ps("enc_embed", st);
-    hipLaunchKernelGGL(enc_embed_kernel, dim3(cdiv(T_txt, EMB_TOK), B), dim3(256), 0, st, in->txt_tokens,
-                       d.use_lang_id ? in->lang_seq : nullptr, in->mel2ph, T_txt, T_mel, H, h->emb, d.vocab_size,
-                       (float)std::sqrt((double)H), h->dur_w, h->dur_b, h->lang, d.num_langs, neg_freq, d.rel_pos,
-                       neg_rel, x);
+    TokEmbedArgs e{};
+    e.tok = in->txt_tokens; e.lang = d.use_lang_id ? in->lang_seq : nullptr; e.mel2ph = in->mel2ph;
+    e.Tt = T_txt; e.Tm = T_mel; e.H = H; e.emb = h->emb; e.V = d.vocab_size;
+    e.dur_w = h->dur_w; e.dur_b = h->dur_b; e.lang_emb = h->lang; e.NL = d.num_langs; e.rel_pos = d.rel_pos;
+    e.x = ws + w.s.x; e.mask = reinterpret_cast<int*>(ws + w.s.mask);
+    PD_TRY(fft_embed_tokens(e, B, st));
   }
-  PD_LAUNCH_CHECK();
-  const float eps = 1e-5f;
-  const float qscale = (float)std::sqrt(1.0 / (double)h->D);
-  for (int l = 0; l < h->L; ++l) {
-    {
-      ProfScope ps("enc_ln", st);
-      hipLaunchKernelGGL(enc_ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, h->ln1g[l], h->ln1b[l],
-                         in->txt_tokens, hn, rows, H, eps, 0);
-    }
-    PD_LAUNCH_CHECK();
-    {
-      GemmArgs a = make_gemm(B, T_txt, 3 * H, h->Wqkv[l], H, nullptr, qkv, bs * 3 * H, 3 * H);
-      add_seg(a, make_seg(hn, bs * H, H, H, 0));
-      PD_TRY((enc_gemm<EPI_STORE, U_ENC_QKV>(a, part, st, "enc_qkv")));
-    }
-    {
-      ProfScope ps("enc_attn", st);
-      dim3 grid(cdiv(T_txt, AQ), h->heads, B);
-      if (h->D == 64)
-        hipLaunchKernelGGL(enc_attn_kernel<64>, grid, dim3(256), 0, st, qkv, in->txt_tokens, att, T_txt, H, qscale);
-      else if (h->D == 128)
-        hipLaunchKernelGGL(enc_attn_kernel<128>, grid, dim3(256), 0, st, qkv, in->txt_tokens, att, T_txt, H, qscale);
-      else
-        hipLaunchKernelGGL(enc_attn_kernel<256>, grid, dim3(256), 0, st, qkv, in->txt_tokens, att, T_txt, H, qscale);
-    }
-    PD_LAUNCH_CHECK();
-    {   // x = x + attn Wo^T   (out_proj, bias=False; residual, common_layers.py:658-665)
-      GemmArgs a = make_gemm(B, T_txt, H, h->Wo[l], H, nullptr, x, bs * H, H);
-      add_seg(a, make_seg(att, bs * H, H, H, 0));
-      a.res = x; a.res_bs = bs * H; a.res_ld = H;
-      PD_TRY((enc_gemm<EPI_STORE, U_ENC_OUT>(a, part, st, "enc_outproj")));
-    }
-    {
-      ProfScope ps("enc_ln", st);
-      hipLaunchKernelGGL(enc_ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, h->ln2g[l], h->ln2b[l],
-                         in->txt_tokens, hn, rows, H, eps, 0);
-    }
-    PD_LAUNCH_CHECK();
-    {   // f = gelu(k^-0.5 (conv_k(hn) + b1))   (TransformerFFNLayer, common_layers.py:570-576)
-      GemmArgs a = make_gemm(B, T_txt, F, h->W1[l], K * H, h->b1[l], ff, bs * F, F);
-      for (int tap = 0; tap < K; ++tap) add_seg(a, make_seg(hn, bs * H, H, H, tap - K / 2));
-      a.lens = in->txt_lens; a.lens_mul = 1;   // ragged token batch: zero past each row's own tokens
-      a.act = ACT_GELU;
-      a.alpha = (float)std::pow((double)K, -0.5);
-      PD_TRY((enc_gemm<EPI_STORE, U_ENC_FFN1>(a, part, st, "enc_ffn1")));
-    }
-    {   // x = x + (f W2^T + b2)   (ffn_2, residual, :667-672)
-      GemmArgs a = make_gemm(B, T_txt, H, h->W2[l], F, h->b2[l], x, bs * H, H);
-      add_seg(a, make_seg(ff, bs * F, F, F, 0));
-      a.res = x; a.res_bs = bs * H; a.res_ld = H;
-      PD_TRY((enc_gemm<EPI_STORE, U_ENC_FFN2>(a, part, st, "enc_ffn2")));
-    }
-  }
-  {
-    ProfScope ps("enc_ln", st);
-    hipLaunchKernelGGL(enc_ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, h->lnfg, h->lnfb, in->txt_tokens,
-                       enc, rows, H, eps, 1);
-  }
-  PD_LAUNCH_CHECK();
+  PD_TRY(fft_stack_forward<U_ENC_BASE>(h->enc, ws, w.s, in->txt_lens, enc, B, T_txt, st));
   if (!cond || T_mel == 0) return PD_OK;
   CondArgs a{};
   a.enc = enc; a.mel2ph = in->mel2ph; a.f0 = in->f0; a.pw = h->pw; a.pb = h->pb;

@@ -317,3 +317,162 @@ def synth_svs_utterance(seed, frames, n_tokens, vocab_size, num_langs=3, hidden=
                 spk_mix_embed=(0.3 * rng.standard_normal((1, hidden))).astype(np.float32),
                 voicing=rng.uniform(-1.5, 1.0, frames).astype(np.float32),
                 breath=rng.uniform(-1.5, 1.0, frames).astype(np.float32))
+
+
+# --------------------------------------------------------------------------
+# Variance predictors (modules/variance_predictor/{pitch,dur}_predictor.py; encoders
+# modules/fastspeech/tts_modules.py:291-365, DurationPredictor :59-100)
+# --------------------------------------------------------------------------
+PITCH_DEFAULTS = dict(hidden_size=256, enc_layers=4, enc_ffn_kernel_size=9, num_heads=2, note_hidden_size=128,
+                      note_layers=4, note_ffn_kernel_size=9, note_heads=2, num_spk=1, use_spk_id=True)
+DUR_DEFAULTS = dict(hidden_size=256, enc_layers=4, enc_ffn_kernel_size=9, num_heads=2, n_layers=5, n_chans=512,
+                    kernel_size=3, log_offset=1.0)
+
+
+def _fft_shapes(s, prefix, H, k, layers):
+    """FFTBlocks parameters (layers then the final LayerNorm) in state-dict order."""
+    for l in range(layers):
+        p = f"{prefix}layers.{l}.op."
+        s[p + "layer_norm1.weight"] = (H,)
+        s[p + "layer_norm1.bias"] = (H,)
+        s[p + "self_attn.in_proj_weight"] = (3 * H, H)
+        s[p + "self_attn.out_proj.weight"] = (H, H)
+        s[p + "layer_norm2.weight"] = (H,)
+        s[p + "layer_norm2.bias"] = (H,)
+        s[p + "ffn.ffn_1.weight"] = (4 * H, H, k)
+        s[p + "ffn.ffn_1.bias"] = (4 * H,)
+        s[p + "ffn.ffn_2.weight"] = (H, 4 * H)
+        s[p + "ffn.ffn_2.bias"] = (H,)
+    s[prefix + "layer_norm.weight"] = (H,)
+    s[prefix + "layer_norm.bias"] = (H,)
+
+
+def pitch_param_shapes(vocab_size, hidden_size=256, enc_layers=4, enc_ffn_kernel_size=9, note_hidden_size=128,
+                       note_layers=4, note_ffn_kernel_size=9, num_spk=1, use_spk_id=True, **_):
+    """Ordered ``{state-dict key: shape}`` of the reference PitchPredictor minus ``diffusion.*`` and buffers."""
+    H, Hn = hidden_size, note_hidden_size
+    s = OrderedDict()
+    _fft_shapes(s, "encoder.", H, enc_ffn_kernel_size, enc_layers)
+    s["encoder.embed_tokens.weight"] = (vocab_size + 1, H)
+    s["dur_embed.weight"] = (H, 1)
+    s["dur_embed.bias"] = (H,)
+    _fft_shapes(s, "note_encoder.", Hn, note_ffn_kernel_size, note_layers)
+    s["note_encoder.note_midi_embed.weight"] = (Hn, 1)
+    s["note_encoder.note_midi_embed.bias"] = (Hn,)
+    s["note_encoder.note_dur_embed.weight"] = (Hn, 1)
+    s["note_encoder.note_dur_embed.bias"] = (Hn,)
+    s["note_encode_out_linear.weight"] = (H, Hn)
+    s["note_encode_out_linear.bias"] = (H,)
+    if use_spk_id:
+        s["spk_embed.weight"] = (num_spk, H)
+    s["delta_pitch_embed.weight"] = (H, 1)
+    s["delta_pitch_embed.bias"] = (H,)
+    s["pitch_retake_embed.weight"] = (2, H)
+    return s
+
+
+def dur_param_shapes(vocab_size, hidden_size=256, enc_layers=4, enc_ffn_kernel_size=9, n_layers=5, n_chans=512,
+                     kernel_size=3, **_):
+    """Ordered ``{state-dict key: shape}`` of the reference DurPredictor minus buffers."""
+    H, C = hidden_size, n_chans
+    s = OrderedDict()
+    _fft_shapes(s, "encoder.", H, enc_ffn_kernel_size, enc_layers)
+    s["encoder.embed_tokens.weight"] = (vocab_size, H)
+    s["onset_embed.weight"] = (2, H)
+    s["word_dur_embed.weight"] = (H, 1)
+    s["word_dur_embed.bias"] = (H,)
+    for i in range(n_layers):
+        s[f"dur_pred.conv.{i}.1.weight"] = (C, H if i == 0 else C, kernel_size)
+        s[f"dur_pred.conv.{i}.1.bias"] = (C,)
+        s[f"dur_pred.conv.{i}.3.weight"] = (C,)
+        s[f"dur_pred.conv.{i}.3.bias"] = (C,)
+    s["dur_pred.linear.weight"] = (1, C)
+    s["dur_pred.linear.bias"] = (1,)
+    return s
+
+
+def synth_variance_params(shapes, seed, dur_bias=None):
+    """synth_cond_params (the zero padding row of embed_tokens), the duration predictor's LayerNorm gamma
+    near 1 (``conv.i.3.weight``), the note embeddings at the scale of their inputs (MIDI numbers reach 80,
+    durations tens of frames) and, for the duration fixtures, a chosen ``dur_pred.linear.bias``: synthetic
+    weights otherwise put exp(log) - 1 below 0 on almost every token and the clamp hides the head."""
+    P = synth_cond_params(shapes, seed)
+    for k in P:
+        if k.startswith("dur_pred.conv.") and k.endswith(".3.weight"):
+            P[k] = (1.0 + 0.1 * _rng(seed, k).standard_normal(size=P[k].shape, dtype=np.float32)).astype(np.float32)
+        if k in ("note_encoder.note_midi_embed.weight", "note_encoder.note_dur_embed.weight"):
+            P[k] = (P[k] * np.float32(0.02)).astype(np.float32)
+    if dur_bias is not None:
+        P["dur_pred.linear.bias"] = np.full((1,), dur_bias, np.float32)
+    return P
+
+
+def _spans(rng, counts, max_dur, Tm=None):
+    """mel2x rows: item i+1 repeated dur[i] times, 0-padded to the longest row (or Tm)."""
+    durs = [rng.integers(1, max_dur + 1, n) for n in counts]
+    Tm = Tm or max(int(d.sum()) for d in durs)
+    out = np.zeros((len(counts), Tm), np.int64)
+    for b, d in enumerate(durs):
+        seq = np.repeat(np.arange(1, len(d) + 1), d)[:Tm]
+        out[b, :len(seq)] = seq
+    return out
+
+
+def synth_pitch_inputs(seed, lengths, note_lengths, vocab_size, num_spk=1, pad_tokens=0, pad_notes=0, frames=None,
+                       retake=False, max_dur=6):
+    """PitchPredictor.forward's inputs for a ragged batch: ``lengths[b]`` phonemes (ids in [1, vocab_size])
+    and ``note_lengths[b]`` notes (MIDI 48..76, about a fifth of them rests) per row, padded with token 0 /
+    midi -1; mel2ph and mel2note cover the same frames of a row (the first ``frames``, or the row's phoneme
+    durations) and are 0 after them.  ``retake``: pitch, pitch_retake (about half the frames) instead of
+    pitch_expr (one value per row)."""
+    rng = np.random.default_rng([int(seed), 0x917C])
+    B = len(lengths)
+    Tt, Tn = max(lengths) + pad_tokens, max(note_lengths) + pad_notes
+    tok = np.zeros((B, Tt), np.int64)
+    midi = np.full((B, Tn), -1.0, np.float32)
+    rest = np.zeros((B, Tn), bool)
+    for b, (n, m) in enumerate(zip(lengths, note_lengths)):
+        tok[b, :n] = rng.integers(1, vocab_size + 1, n)
+        midi[b, :m] = rng.integers(48, 77, m).astype(np.float32) + rng.integers(0, 2, m) * np.float32(0.5)
+        rest[b, :m] = rng.random(m) < 0.2
+    if frames is None:
+        mel2ph = _spans(rng, lengths, max_dur)
+    else:
+        mel2ph = np.zeros((B, frames), np.int64)
+        for b, n in enumerate(lengths):
+            cuts = np.sort(rng.choice(np.arange(1, frames), n - 1, replace=False))
+            mel2ph[b] = np.repeat(np.arange(1, n + 1), np.diff(np.concatenate([[0], cuts, [frames]])))
+    Tm = mel2ph.shape[1]
+    mel2note = np.zeros((B, Tm), np.int64)
+    for b, m in enumerate(note_lengths):
+        nf = int((mel2ph[b] > 0).sum())
+        cuts = np.sort(rng.choice(np.arange(1, nf), m - 1, replace=False))
+        mel2note[b, :nf] = np.repeat(np.arange(1, m + 1), np.diff(np.concatenate([[0], cuts, [nf]])))
+    base = np.take_along_axis(np.concatenate([np.full((B, 1), -1.0, np.float32), midi], 1), mel2note, 1)
+    x = dict(txt_tokens=tok, mel2ph=mel2ph, note_midi=midi, note_rest=rest, mel2note=mel2note,
+             base_pitch=base.astype(np.float32), spk_id=rng.integers(0, num_spk, B).astype(np.int64))
+    if retake:
+        x["pitch"] = (base + rng.uniform(-1.5, 1.5, (B, Tm))).astype(np.float32)
+        x["pitch_retake"] = rng.random((B, Tm)) < 0.5
+    else:
+        x["pitch_expr"] = rng.uniform(0.0, 1.0, (B, 1)).astype(np.float32)
+    return x
+
+
+def synth_dur_inputs(seed, lengths, vocab_size, pad_tokens=0):
+    """DurPredictor.forward's inputs: ``lengths[b]`` phonemes (ids in [1, vocab_size)) then token 0; onset 1
+    on the first phoneme of a word (about every third), word_dur the word's length in seconds on each of its
+    phonemes (handler/infer/handler.py:219-227), 0 on padding."""
+    rng = np.random.default_rng([int(seed), 0xD0B])
+    B, Tt = len(lengths), max(lengths) + pad_tokens
+    tok = np.zeros((B, Tt), np.int64)
+    onset = np.zeros((B, Tt), np.int64)
+    wd = np.zeros((B, Tt), np.float32)
+    for b, n in enumerate(lengths):
+        tok[b, :n] = rng.integers(1, vocab_size, n)
+        on = (rng.random(n) < 0.35).astype(np.int64)
+        on[0] = 1
+        onset[b, :n] = on
+        word = np.cumsum(on) - 1
+        wd[b, :n] = rng.uniform(0.1, 1.2, int(word.max()) + 1).astype(np.float32)[word]
+    return dict(txt_tokens=tok, onset=onset, word_dur=wd)
