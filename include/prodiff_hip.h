@@ -252,7 +252,18 @@ size_t fd_workspace_size(const fd_model* m, int B, int Tc, int S);
 #define FD_OPT_LVC_PS 14      /* 1 (r06): the final (fused, prefetching, 384-sample) LVC block as a persistent kernel whose
                                * next tile's audio / x_prev / biases arrive by LDS-DMA under the current tile's layers */
 /* 13: reserved (r04's multi-tile fused-DBlock blocks, removed: measured slower) */
+#define FD_OPT_LVC_CARRY 15   /* 1 (default): a persistent LVC block walks runs of consecutive tiles of one utterance and
+                               * carries the left halo from tile to tile (448 output rows per 512-row window
+                               * instead of 384); 0: 384-row tiles v, v + grid, ... with both halos recomputed */
+#define FD_OPT_LVC_PS_GRID 16 /* n > 0: at most n blocks in a persistent LVC launch (default 0 = one per CU) */
 int fd_set_option(fd_model* m, int option, int value);
+
+/* The run partition of a persistent LVC launch (FD_OPT_LVC_CARRY) over `batch` utterances of `rows` rows (a
+ * multiple of 64) on `grid` blocks: *nruns = the number of runs (0: no more 384-row tiles than blocks, every
+ * block takes one tile and nothing is carried), and runs[3 i ..] = (utterance, first row, end row) of run i
+ * for i < min(*nruns, cap) (runs may be NULL).  Block v walks runs v, v + grid, ...; a run's first tile yields
+ * 384 rows (448 at row 0), every later one 448. */
+int fd_lvc_ps_partition(int rows, int batch, int grid, int* runs, int cap, int* nruns);
 
 /* w[co,:] = g[co] * v[co,:] / ||v[co,:]||  (torch.nn.utils.weight_norm, dim 0). */
 int fd_fold_weight_norm(float* w, const float* g, const float* v, int cout, int per_row,

@@ -16,7 +16,7 @@ PD_DTYPE_BF16 = 1
 PD_REFLOW = {"euler": 0, "rk2": 1, "rk4": 2, "rk5": 3}
 # fd_set_option / nsf_set_option ids (include/prodiff_hip.h)
 FD_OPTIONS = {"lvc_ts": 0, "lvc_ts_sub": 1, "lvc_fuse": 2, "lvc_pf": 3, "lvc_sub": 4, "kp_side": 5, "kp_chunk": 7,
-               "lvc_tpw": 10, "lvc_prio": 11, "lvc_ps": 14}
+               "lvc_tpw": 10, "lvc_prio": 11, "lvc_ps": 14, "lvc_carry": 15, "lvc_ps_grid": 16}
 NSF_OPTIONS = {"small_max": 0, "wconv": 1, "pair": 2, "pair16": 3, "ups_nc": 4, "rb16": 5, "rb32": 6, "rb64": 7, "c256": 8, "nc_mfma": 9}
 WN_OPTIONS = {"layer": 0, "ksplit": 1, "l2pf": 2, "stack": 3, "stack_ro": 4, "stack_fuse": 6, "f32_layer": 7}
 
@@ -114,6 +114,7 @@ _SIGS = {
     "fd_hop": (C.c_int, [_VP]),
     "fd_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
     "fd_set_option": (C.c_int, [_VP, C.c_int, C.c_int]),
+    "fd_lvc_ps_partition": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "fd_fold_weight_norm": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP]),
     "fd_forward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "fd_sample": (C.c_int, [_VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -163,7 +164,18 @@ def lib():
                            "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
-            f = getattr(l, name)
+            try:
+                f = getattr(l, name)
+            except AttributeError:
+                # an A/B run against an older build (PRODIFF_HIP_LIB, tools/build_rev_lib.sh) that predates
+                # this entry point: calling it raises.  The in-tree library must export everything.
+                if "PRODIFF_HIP_LIB" not in os.environ:
+                    raise
+
+                def f(*_a, _name=name):
+                    raise HipError(f"{LIB_PATH} does not export {_name}")
+                setattr(l, name, f)
+                continue
             f.restype = res
             f.argtypes = args
         _lib = l

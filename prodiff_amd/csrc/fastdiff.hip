@@ -72,6 +72,8 @@ struct fd_model {
   int lvc_tpw = 2;    // FD_OPT_LVC_TPW: 32-row tiles per wave of the 384-sample hop >= 32 blocks (2 or 1)
   int lvc_prio = 0;   // FD_OPT_LVC_PRIO: 1 = s_setprio(1) for the second half of an LVC block's waves
   int lvc_ps = 1;     // FD_OPT_LVC_PS (r06): the final block as a persistent kernel with LDS-DMA prefetch
+  int lvc_carry = 1;  // FD_OPT_LVC_CARRY: the persistent blocks walk runs of tiles and carry the left halo
+  int lvc_ps_grid = 0;   // FD_OPT_LVC_PS_GRID: cap of the persistent grid (0 = one block per CU)
 
   mutable hipStream_t side = nullptr;
   mutable hipEvent_t ev_hidden = nullptr, ev_kp[4] = {}, ev_lvc[4] = {};
@@ -1116,13 +1118,40 @@ void lvc_block_bf16_kernel(const LvcBlockArgs P) {
 // flight (vmcnt retires in order): it is issued right after a tile's layer-0 MFMAs, before the layer-1
 // kernel fragments, and waited for explicitly (vmcnt at the next tile's top).  The asm sets M0, which hipcc
 // treats as reserved: this kernel has no other M0 use (no LDS-DMA builtin, no indirect register indexing).
+// M0 is named in the clobber lists all the same, so the asm states what it writes; hipcc answers that a
+// reserved register's clobber changes nothing (-Winline-asm), which is silenced for these two functions.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 __device__ __forceinline__ void lds_dma16(const void* g, void* lds) {
   const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds);
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(g) : "memory");
+  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(g) : "memory", "m0");
 }
 __device__ __forceinline__ void lds_dma4(const void* g, void* lds) {
   const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds);
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" ::"s"(l), "v"(g) : "memory");
+  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" ::"s"(l), "v"(g) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+// FD_OPT_LVC_CARRY: the persistent launch as `nruns` runs, each a contiguous, time-ascending range of rows
+// [t0, t1) of one utterance that one block walks tile by tile.  Utterance b owns runs [b nruns / batch,
+// (b + 1) nruns / batch) (nruns >= batch), which split its 64-row units evenly: every boundary is a multiple
+// of 64 (a 64-row tile pair shares one frame), no run is empty (a run count per utterance never exceeds its
+// 384-row tile count), and the runs of an utterance differ by at most one unit, so the longest run sets the
+// launch's makespan.  A run's first tile yields 384 rows (448 at an utterance's first row), every later one 448.
+__host__ __device__ inline void lvc_ps_run(int rn, int nruns, int batch, int rows, int& b, int& t0, int& t1) {
+  b = ((rn + 1) * batch - 1) / nruns;
+  const int first = b * nruns / batch, n = (b + 1) * nruns / batch - first, i = rn - first;
+  const long long units = (rows + 63) / 64;
+  t0 = (int)(i * units / n) * 64;
+  t1 = i + 1 == n ? rows : (int)((i + 1) * units / n) * 64;
+}
+// the persistent grid of a launch of `batch` utterances of `rows` rows on `ncu` CUs (cap > 0: FD_OPT_LVC_PS_GRID)
+// and its run count: 0 = no carry (no more 384-row tiles than blocks: one tile per block, as before)
+static inline int lvc_ps_grid(int rows, int batch, int ncu, int cap, int* nruns_carry) {
+  const int ntiles = (int)cdiv(rows, 384) * batch;
+  int grid = ntiles <= ncu ? ntiles : ncu >= 8 ? ncu / 8 * 8 : ncu;
+  if (cap > 0 && cap < grid) grid = cap;
+  *nruns_carry = ntiles > grid ? (grid > batch ? grid : batch) : 0;
+  return grid;
 }
 // lvc_block_bf16_kernel<384, UPS, AUD, FIN, PF> as a persistent kernel (FD_OPT_LVC_PS): one 8-wave block
 // per CU walks the launch's tiles in the same XCD-aware order.  Each tile's prologue loads -- the audio
@@ -1149,9 +1178,24 @@ __device__ __forceinline__ void lds_dma4(const void* g, void* lds) {
 #endif
 // FINAL = the sampler's last block (upsample r = 4, first conv, final conv + sampler update; hop 256); !FINAL
 // (r06) = the hop-64 block (upsample r = 8, audio_down from HBM, x out), the one-tile kernel's <384, UPS, PF>.
+//
+// The tile walk.  nb == 0: block v takes the 384-row tiles v, v + gridDim.x, ... of the launch's `nruns` tiles,
+// each with a 64-row halo on both sides of its 512-row window (origin T - 64).  nb > 0 (FD_OPT_LVC_CARRY): block
+// v takes the runs v, v + gridDim.x, ... (lvc_ps_run) of the launch's nb utterances and walks each in time.  A
+// run's first tile has the geometry above; every later tile -- and a tile at an utterance's first row -- is
+// CARRIED: window origin T, rows [0, 448) are output, and what the layers need from rows left of T comes from
+// the tile before it instead of a recomputed left halo:
+//   CUL  layer l's bf16 u rows T - d_l - 1 .. T - 1 (the previous tile's window rows 448 - d_l - 1 .. 447,
+//        copied out of U in its pre-conv phase; restored into U's left margin in this tile's u phase -- the
+//        barrier between the two phases orders the old carry's read before the new carry's write).  Row -1 of
+//        y is then the pre-conv of those rows: the same MFMA chain on the same values as the tile before ran.
+//   EB[0][1]  FINAL: the per-tap partial sums of the final conv's three x rows before T (the previous tile's
+//        EB slot of window rows 445 .. 447), read by wave 0 where the other waves read their left neighbour's.
+// At an utterance's first row both are zero: the convs' zero padding.  Every value is computed by the chain
+// that computed it before; only the tile that computes it changes.
 template <bool FINAL>
-__global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, int ntx, int ntiles) {
-  constexpr int TS = 384, TPW = 2;
+__global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, int ntx, int nruns, int nb) {
+  constexpr int TS = 384, TPW = 2, TSC = TS + 64;     // output rows of a plain and of a carried tile
   using G = LbGeo<TS, TPW>;
   constexpr int NW = G::NW, NG = G::NG, UOFF = G::UOFF, GR = NG * 32, EX = FINAL ? 3 : 0, NT = G::NT;
   constexpr int BFR = GR / (FINAL ? 256 : 64) + 2;      // frames a tile touches at hop 256 / 64 (host-checked)
@@ -1168,7 +1212,9 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
   __shared__ __attribute__((aligned(16))) float BUL[32];
   __shared__ __attribute__((aligned(16))) bf16x8 WCL[NLY * 6 * 64];
   __shared__ __attribute__((aligned(16))) float BCL[NLY * CI];
-  __shared__ float EB[FA ? 8 : 1][2][3][8];                                  // FIN: pairs' outer E rows
+  __shared__ float EB[FA ? NW + 1 : 1][2][3][8];   // FIN: pairs' outer E rows, wave w's in slot w + 1; [0][1] carried
+  __shared__ __attribute__((aligned(16))) __bf16 CUL[44 * CI];               // carried u rows: layer l's d_l + 1
+  static_assert(NW == 8 && NLY == 4, "the carry slots (CUL offsets, EB[NW - 1] = window rows 384 .. 447)");
   __bf16* U = reinterpret_cast<__bf16*>(smem);
   __bf16* Y = U + G::UROWS * LB_LD;
   float* XS = reinterpret_cast<float*>(smem);
@@ -1196,19 +1242,27 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
   }
   if (tid < NLY * CI) BCL[tid] = P.bc[tid / CI][tid % CI];
   const float bfin = FINAL ? P.bfin[0] : 0.f;
-  // tile v -> (utterance, time tile): the one-tile kernel's XCD-aware order (gridDim.x % 8 == 0, so tile v
-  // runs on the XCD of block v % gridDim.x, as block v did there)
-  auto coords = [&](int v, int& b, int& bx) {
-    const int xcd = v & 7, slot = v >> 3, per = ntiles >> 3, rem = ntiles & 7;
+  // run slot v -> (utterance, first output row, end of the run), in the one-tile kernel's XCD-aware order
+  // (gridDim.x % 8 == 0: slot v runs on the XCD of block v % gridDim.x, as block v did there; a bijection of
+  // [0, nruns) for every grid).  nb == 0: a run is one 384-row tile.
+  auto decode = [&](int v, int& b, int& T, int& tend) {
+    const int xcd = v & 7, slot = v >> 3, per = nruns >> 3, rem = nruns & 7;
     const int logical = xcd < rem ? xcd * (per + 1) + slot : rem * (per + 1) + (xcd - rem) * per + slot;
-    b = __builtin_amdgcn_readfirstlane(logical / ntx);   // (uniform: scalar loads of lens / uid)
-    bx = __builtin_amdgcn_readfirstlane(logical - b * ntx);
+    int bb, t0, t1;
+    if (nb) {
+      lvc_ps_run(logical, nruns, nb, Lh, bb, t0, t1);
+    } else {
+      bb = logical / ntx;
+      t0 = (logical - bb * ntx) * TS;
+      t1 = t0 + TS;
+    }
+    b = __builtin_amdgcn_readfirstlane(bb);   // (uniform: scalar loads of lens / uid)
+    T = __builtin_amdgcn_readfirstlane(t0);
+    tend = __builtin_amdgcn_readfirstlane(t1);
   };
-  // a tile's loads straight into LDS (buffer s of AS / BFL, and XPN)
-  auto dma = [&](int v, int s, int wave, int lane) {
-    int b, bx;
-    coords(v, b, bx);
-    const int tg = bx * TS - 64, jb = floordiv(tg + pp, r) - 2, fbase = (tg > 0 ? tg : 0) / hop;
+  // a tile's loads straight into LDS (buffer s of AS / BFL, and XPN); tg = the window's first row
+  auto dma = [&](int b, int tg, int s, int wave, int lane) {
+    const int jb = floordiv(tg + pp, r) - 2, fbase = (tg > 0 ? tg : 0) / hop;
     const long long base = (long long)b * Lh;
     if constexpr (FINAL) {
 #pragma unroll
@@ -1250,28 +1304,30 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
   // (raw values only: used -- and so waited for -- at the next tile's top, both loads in flight together;
   // r06 probe: computed at the load, they cost two serial round trips inside layer 0)
   int lv_n = 0, uv_n = 0;
-  float zn_n = 0.f;     // the explicit sampler draw of thread tq's sample tq - 64 (P.noise; unconditional load)
-  auto tile_scalars = [&](int v, int tq) {
-    int b, bx;
-    coords(v, b, bx);
+  float zn_n = 0.f;     // the explicit sampler draw of thread tq's window row tq (P.noise; unconditional load)
+  auto tile_scalars = [&](int b, int tg, int tq) {
     lv_n = *(P.lens ? P.lens + b : reinterpret_cast<const int*>(P.Bf));
     if constexpr (FINAL) {
       uv_n = *(P.uid ? P.uid + b + P.b_off : reinterpret_cast<const int*>(P.Bf));
-      zn_n = (P.noise ? P.noise : P.audio)[(long long)b * Lh + min(max(bx * TS + tq - 64, 0), Lh - 1)];
+      zn_n = (P.noise ? P.noise : P.audio)[(long long)b * Lh + min(max(tg + tq, 0), Lh - 1)];
     }
   };
-  const int v0 = blockIdx.x;
+  // the tile in hand: run slot v, utterance b, first output row T of the run's rows [.., tend), cf = carried
+  int v = blockIdx.x, b = 0, T = 0, tend = 0, cf = 0;
+  bool has = v < nruns;
   __syncthreads();                                         // the invariant operands are staged
-  if (v0 < ntiles) {
+  if (has) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    int b, bx;
-    coords(v0, b, bx);
-    tile_scalars(v0, tid);
-    dma(v0, 0, wave, lane);
-    kload(b, fpair_of(bx * TS - 64, wave), 0, lane);
+    decode(v, b, T, tend);
+    cf = nb && T == 0;
+    const int tg = T - (cf ? 0 : 64);
+    tile_scalars(b, tg, tid);
+    dma(b, tg, 0, wave, lane);
+    kload(b, fpair_of(tg, wave), 0, lane);
   }
   int it = 0;
-  for (int v = v0; v < ntiles; v += gridDim.x, ++it) {
+  int nst = 0;   // global stores this wave issued after its last kernel-fragment loads (the previous tile's)
+  for (; has; ++it) {
     const int cur = it & 1;
     // thread ids through an opaque copy: addresses derived from them are recomputed per tile instead of
     // hoisted out of the loop and spilled
@@ -1279,28 +1335,54 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
     asm volatile("" : "+v"(tq));
     const int lane = tq & 63, n = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tq >> 6);
-    // the next tile, pinned in an SGPR here: rematerialised where it is used, its kernarg load waited
-    // lgkmcnt(0) -- for the LDS reads in flight -- inside the layer-0 MFMAs
-    int vnext = v + (int)gridDim.x;
-    asm volatile("" : "+s"(vnext));
+    // the next tile -- the run's next 448 rows, or the first tile of the block's next run -- pinned in SGPRs
+    // here: rematerialised where it is used, its kernarg loads waited lgkmcnt(0) -- for the LDS reads in
+    // flight -- inside the layer-0 MFMAs
+    int vn = v, bn = b, Tn = T + (cf ? TSC : TS), tendn = tend, cfn = 1;
+    if (!(nb && Tn < tend)) {
+      vn = v + (int)gridDim.x;
+      cfn = 0;
+      if (vn < nruns) {
+        decode(vn, bn, Tn, tendn);
+        cfn = nb && Tn == 0;
+      }
+    }
+    int tgn = Tn - (cfn ? 0 : 64);
+    vn = __builtin_amdgcn_readfirstlane(vn); bn = __builtin_amdgcn_readfirstlane(bn);
+    Tn = __builtin_amdgcn_readfirstlane(Tn); tendn = __builtin_amdgcn_readfirstlane(tendn);
+    cfn = __builtin_amdgcn_readfirstlane(cfn); tgn = __builtin_amdgcn_readfirstlane(tgn);
+    asm volatile("" : "+s"(vn), "+s"(bn), "+s"(Tn), "+s"(tendn), "+s"(cfn), "+s"(tgn));
+    const bool hasn = vn < nruns;
     PS_STAMP(0);
-    int b, bx;
-    coords(v, b, bx);
     const int Le = P.lens ? min(__builtin_amdgcn_readfirstlane(lv_n), Tc) * hop : Lh;
     const unsigned uidv = !FINAL ? 0u : P.uid ? (unsigned)__builtin_amdgcn_readfirstlane(uv_n) : (unsigned)(b + P.b_off);
-    const int t0 = bx * TS, tg = t0 - 64;
+    // the window: rows [olo, TSC) are output (times tg + row, below the run's end), rows from rlo on are computed
+    const int olo = cf ? 0 : 64, tg = T - olo, tout = min(tend, Lh);
+    const int rlo = cf ? 0 : RLO;
     const long long base = (long long)b * Lh;
     const int Tin_e = Le / r;
     const int fbase = (tg > 0 ? tg : 0) / hop;
     const int jb = floordiv(tg + pp, r) - 2;
     const int fpair = fpair_of(tg, wave);
-    // this tile's DMA (issued a tile ago) has landed for every wave: each waits for its own pieces -- the
-    // 12 younger kernel-fragment loads (and at most one audio_out store; !FINAL: 8 x stores) may stay in
-    // flight -- then a barrier
-    constexpr int VMY = FINAL ? 12 : 20;
-    __builtin_amdgcn_s_waitcnt((VMY & 15) | ((VMY >> 4) << 14) | 0x0F70);   // vmcnt(VMY)
+    // this tile's DMA (issued a tile ago) has landed for every wave: each waits for its own pieces -- only what
+    // it issued after them may stay in flight, the 12 kernel-fragment loads and the nst stores of the previous
+    // tile's output (none ahead of the block's first tile; FINAL: one audio_out store, !FINAL: four x stores
+    // per output row tile of the wave; vmcnt retires in order, so a count above what was issued would let
+    // the DMA itself stay in flight) -- then a barrier
+    constexpr int SPT = FINAL ? 1 : 4;
+#define PS_VMCNT(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (((N) >> 4) << 14) | 0x0F70)
+    if (nst == 0) PS_VMCNT(12);
+    else if (nst == SPT) PS_VMCNT(12 + SPT);
+    else PS_VMCNT(12 + 2 * SPT);
+#undef PS_VMCNT
+    static_assert(TPW == 2, "at most two output row tiles per wave");
     __syncthreads();
     PS_STAMP(1);
+    // FINAL: the carried outer rows of the final conv's partial sums (the previous tile's window rows 445 .. 447
+    // are its wave 6's; that slot is next written at this tile's end, past the barriers below)
+    if constexpr (FINAL) {
+      if (cf && tq < 21) EB[0][1][tq / 7][tq % 7] = T == 0 ? 0.f : EB[NW - 1][1][tq / 7][tq % 7];
+    }
     // phase-GEMM weights (NW % r == 0: wave w computes phase w % r), FIN noise
     bf16x8 wfj[4];
     {
@@ -1323,12 +1405,11 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
     // (the explicit draw loaded a tile ahead, unconditionally: under `P.noise ?` the waitcnt pass waited for
     // every outstanding load -- the next tile's kernel fragments included -- at the join)
     const float znz = zn_n;
-    // (thread tq writes sample s = tq - 64: lane (n, h) of wave w holds row 64 w + 32 h + n of the window)
-    const int so = tq - 64;
+    // (thread tq writes the sample of window row tq: lane (n, h) of wave w holds row 64 w + 32 h + n)
     float zr = 0.f;
     if constexpr (FINAL) {
-      const float zph = philox_normal_u(P.seed, uidv, (unsigned)(t0 + so), P.stream);
-      zr = (so >= 0 && so < TS && t0 + so < Lh && P.sig != 0.f) ? (P.noise ? znz : zph) : 0.f;
+      const float zph = philox_normal_u(P.seed, uidv, (unsigned)(tg + tq), P.stream);
+      zr = (tq >= olo && tq < TSC && tg + tq < Lh && P.sig != 0.f) ? (P.noise ? znz : zph) : 0.f;
       // audio samples outside the utterance -> 0 in place (the one-tile kernel's masked staging: the DMA
       // lands raw values; only the out-of-range ones are rewritten, so no LDS read)
 #pragma unroll
@@ -1378,7 +1459,7 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfj[kk], xb, acc, 0, 0, 0);
           }
           const int j0 = jb + 1 + jt * 32 + n, row = r * j0 + k - pp - tg;
-          if (row >= RLO && row < RHI) {
+          if (row >= rlo && row < RHI) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
               const float4 bv = *reinterpret_cast<const float4*>(&BUL[8 * g + 4 * h]);
@@ -1400,7 +1481,7 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
       const int k = 2 * wave + j, row = k * 32 + n, t = tg + row;
-      const bool ok = row >= RLO && row < RHI && t >= 0 && t < Le;
+      const bool ok = row >= rlo && row < RHI && t >= 0 && t < Le;
       if constexpr (!FINAL) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1444,9 +1525,19 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
     for (int l = 0; l < NLY; ++l) {
       const int d = l == 0 ? 1 : l == 1 ? 3 : l == 2 ? 9 : 27;
       const int e = (l == 0 ? 42 : l == 1 ? 38 : l == 2 ? 28 : 0) + EX;
-      const int kf = (64 - e) / 32, kl = (64 + TS + e - 1) / 32;
+      const int kf = cf ? 0 : (64 - e) / 32, kl = (64 + TS + e - 1) / 32;   // (carried: every row from 0 on)
       const int kpl = kl + 1 < NG - 1 ? kl + 1 : NG - 1;
-      // (1) u = lrelu(z) of the owned tiles the pre-conv reads
+      // the carry's d + 1 u rows of this layer (64 B each, 16 B per thread of the last two waves)
+      const int coff = l == 0 ? 0 : l == 1 ? 2 : l == 2 ? 6 : 16;
+      const int ci = tq - (NT - 128), crow = ci >> 2, cq = (ci & 3) * 8;
+      const bool cmine = ci >= 0 && ci < (d + 1) * 4;
+      static_assert(16 + 28 == 44 && 28 * 4 <= 128 && 27 + 1 == UOFF, "carry rows of the last layer");
+      // (1) u = lrelu(z) of the owned tiles the pre-conv reads; carried: the rows left of the window too
+      if (cf && cmine) {
+        bf16x8 cv = *reinterpret_cast<const bf16x8*>(&CUL[(coff + crow) * CI + cq]);
+        if (T == 0) cv = bf16x8{};
+        *reinterpret_cast<bf16x8*>(&U[(UOFF - (d + 1) + crow) * LB_LD + cq]) = cv;
+      }
 #pragma unroll
       for (int j = 0; j < TPW; ++j) {
         const int k = 2 * wave + j;
@@ -1468,6 +1559,11 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
       __syncthreads();
       PS_STAMP(5 + 3 * l);
       // (2) y^T = lrelu(W_c . [u(t-d); u(t); u(t+d)]^T + b)
+      // the carry for the run's next tile first: this tile's last d + 1 u rows before window row TSC (U is only
+      // read in this phase; the carry was read in phase (1), before the barrier)
+      if (nb && cmine)
+        *reinterpret_cast<bf16x8*>(&CUL[(coff + crow) * CI + cq]) =
+            *reinterpret_cast<const bf16x8*>(&U[(TSC - (d + 1) + crow + UOFF) * LB_LD + cq]);
       {
         bf16x8 wf[6];
 #pragma unroll
@@ -1480,6 +1576,7 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
         }
         // a wave's pre-conv tiles kp0 = kf + wave and kp1 = kp0 + NW (NG <= 2 NW: no third), their
         // MFMA chains interleaved -- the same per-tile MFMA order, so the same values
+        // (carried: tile 0's first row is y row -1, from the carried u rows)
         auto pre_epi = [&](int kp, const f32x16& acc) {
           f32x2 vv[8];
 #pragma unroll
@@ -1556,16 +1653,14 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
       // the next tile's DMA after layer 0's MFMAs (its XPN was read in this tile's prologue, its AS / BFL
       // buffer cur ^ 1 by the previous tile), ahead of the kernel-fragment loads
       if (l == 0) PS_STAMP(18);
-      if (l == 0 && vnext < ntiles) {                 // (the scalars' loads first: waiting for them is not
-        tile_scalars(vnext, tq);                       // waiting for the DMA)
-        dma(vnext, cur ^ 1, wave, lane);
+      if (l == 0 && hasn) {                           // (the scalars' loads first: waiting for them is not
+        tile_scalars(bn, tgn, tq);                     // waiting for the DMA)
+        dma(bn, tgn, cur ^ 1, wave, lane);
       }
       if (l + 1 < NLY) {
         kload(b, fpair, l + 1, lane);
-      } else if (vnext < ntiles) {                         // the next tile's layer-0 fragments
-        int b2, bx2;
-        coords(vnext, b2, bx2);
-        kload(b2, fpair_of(bx2 * TS - 64, wave), 0, lane);
+      } else if (hasn) {                                   // the next tile's layer-0 fragments
+        kload(bn, fpair_of(tgn, wave), 0, lane);
       }
       if (l == 0) PS_STAMP(19);
 #pragma unroll
@@ -1586,12 +1681,15 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
     }
     if (P.prio && wave >= NW / 2) __builtin_amdgcn_s_setprio(0);
     if constexpr (!FINAL) {
-      // centre tiles [2, 2 + TS/32) -> x out (plain stores: they stay in flight into the next tile, whose
-      // top waits for at most 20 younger operations -- these 8 and the 12 kernel-fragment loads)
+      // output row tiles [olo / 32, TSC / 32) below the run's end -> x out (plain stores: they stay in flight
+      // into the next tile, whose top counts them -- nst -- beside the 12 kernel-fragment loads).  A row tile
+      // is stored whole or not at all (tout is a multiple of 64), under a wave-uniform branch: the count is exact
+      nst = 0;
 #pragma unroll
       for (int j = 0; j < TPW; ++j) {
         const int k = 2 * wave + j, t = tg + k * 32 + n;
-        if (k >= 2 && k < 2 + TS / 32 && t < Lh) {
+        if (k * 32 >= olo && k * 32 < TSC && tg + k * 32 < tout) {
+          nst += SPT;
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             *reinterpret_cast<float4*>(P.xout + (base + t) * CI + 8 * i + 4 * h) =
@@ -1630,11 +1728,11 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
     // the pair's rows 0..2 (tile 2w) and 61..63 (tile 2w + 1) for the neighbouring waves
     if (h == 0 && n < 3) {
 #pragma unroll
-      for (int tap = 0; tap < 7; ++tap) EB[wave][0][n][tap] = ev[0][tap];
+      for (int tap = 0; tap < 7; ++tap) EB[wave + 1][0][n][tap] = ev[0][tap];
     }
     if (h == 0 && n >= 29) {
 #pragma unroll
-      for (int tap = 0; tap < 7; ++tap) EB[wave][1][n - 29][tap] = ev[1][tap];
+      for (int tap = 0; tap < 7; ++tap) EB[wave + 1][1][n - 29][tap] = ev[1][tap];
     }
     __syncthreads();
     {
@@ -1645,19 +1743,24 @@ __global__ __launch_bounds__(512, 1) void lvc_ps_kernel(const LvcBlockArgs P, in
         const int src = rho + tap - 3;             // source row within the pair, [-3, 67)
         const int sl = src & 31;
         const float v0 = __shfl(ev[0][tap], sl), v1 = __shfl(ev[1][tap], sl);
-        const float vl = EB[wave > 0 ? wave - 1 : 0][1][min(max(src + 3, 0), 2)][tap];        // wave w - 1, rows 61..63
-        const float vr = EB[wave < NW - 1 ? wave + 1 : NW - 1][0][min(max(src - 64, 0), 2)][tap];   // wave w + 1, rows 0..2
+        // wave w - 1, rows 61..63 (slot w; wave 0: slot 0, the rows carried from the tile before)
+        const float vl = EB[wave][1][min(max(src + 3, 0), 2)][tap];
+        const float vr = EB[(wave < NW - 1 ? wave + 1 : NW - 1) + 1][0][min(max(src - 64, 0), 2)][tap];   // wave w + 1, rows 0..2
         e += src < 0 ? vl : src < 32 ? v0 : src < 64 ? v1 : vr;
       }
-      const int t = t0 + so;
-      if (so >= 0 && so < TS && t < Lh) {
-        float vv = (as[67 + so] - P.ce * e) / P.den;
+      // the wave's 64 rows are output whole or not at all (olo, TSC and tout are multiples of 64): one store,
+      // counted for the next tile's top, under a wave-uniform branch
+      nst = 0;
+      if (64 * wave >= olo && 64 * wave < TSC && tg + 64 * wave < tout) {
+        nst = SPT;
+        float vv = (as[3 + tq] - P.ce * e) / P.den;
         if (P.sig != 0.f) vv += P.sig * zr;
-        P.audio_out[base + t] = vv;
+        P.audio_out[base + tg + tq] = vv;
       }
     }
     PS_STAMP(17);
     }
+    v = vn; b = bn; T = Tn; tend = tendn; cf = cfn; has = hasn;
   }
 }
 #undef PS_STAMP
@@ -2763,10 +2866,15 @@ int fd_net(const fd_model* m, float* ws, const FdWs& W, const float* xa, const f
           int dev = 0, ncu = 0;
           PD_HIP(hipGetDevice(&dev));
           PD_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+          // FD_OPT_LVC_CARRY: with more tiles than blocks, a block walks runs of consecutive tiles and carries
+          // the left halo from tile to tile (lvc_ps_run); otherwise one tile per block, as before
           const int ntx = (int)cdiv(Tout, 384), ntiles = ntx * nbk;
-          const int grid = ntiles <= ncu ? ntiles : ncu >= 8 ? ncu / 8 * 8 : ncu;
-          if (ps_fin) hipLaunchKernelGGL(lvc_ps_kernel<true>, dim3(grid), dim3(512), 0, st, la, ntx, ntiles);
-          else hipLaunchKernelGGL(lvc_ps_kernel<false>, dim3(grid), dim3(512), 0, st, la, ntx, ntiles);
+          int nruns = 0;
+          const int grid = lvc_ps_grid((int)Tout, nbk, ncu, m->lvc_ps_grid, &nruns);
+          const int nb = m->lvc_carry && nruns ? nbk : 0;
+          if (!nb) nruns = ntiles;
+          if (ps_fin) hipLaunchKernelGGL(lvc_ps_kernel<true>, dim3(grid), dim3(512), 0, st, la, ntx, nruns, nb);
+          else hipLaunchKernelGGL(lvc_ps_kernel<false>, dim3(grid), dim3(512), 0, st, la, ntx, nruns, nb);
           PD_LAUNCH_CHECK();
         } else if (ts == 256) PD_TRY(launch_lvc_block_ts<256>(la, ups, last && aud, fuse_fin, pf, Tout, nbk, st));
         else if (ts == 384 && m->lvc_tpw == 1 && hop >= 32 && ups && (last && aud) == fuse_fin)
@@ -3032,10 +3140,28 @@ int fd_set_option(fd_model* m, int option, int value) {
       PD_CHECK_ARG(value == 1 || value == 2, "FD_OPT_LVC_TPW in {1,2}");
       m->lvc_tpw = value;
       return PD_OK;
+    case FD_OPT_LVC_CARRY:
+      PD_CHECK_ARG(value == 0 || value == 1, "FD_OPT_LVC_CARRY in {0,1}");
+      m->lvc_carry = value;
+      return PD_OK;
+    case FD_OPT_LVC_PS_GRID:
+      PD_CHECK_ARG(value >= 0, "FD_OPT_LVC_PS_GRID >= 0");
+      m->lvc_ps_grid = value;
+      return PD_OK;
     default: break;
   }
   set_error("fd_set_option: unknown option " + std::to_string(option));
   return PD_ERR_ARG;
+}
+
+int fd_lvc_ps_partition(int rows, int batch, int grid, int* runs, int cap, int* nruns) {
+  PD_CHECK_ARG(nruns && rows > 0 && rows % 64 == 0 && batch > 0 && grid > 0,
+               "rows (a multiple of 64), batch and grid must be positive");
+  PD_CHECK_ARG((long long)batch * (rows / 64) < (1ll << 24), "launch too large");
+  lvc_ps_grid(rows, batch, 1 << 30, grid, nruns);   // (as many CUs as tiles: `grid` alone bounds the blocks)
+  for (int i = 0; runs && i < *nruns && i < cap; ++i)
+    lvc_ps_run(i, *nruns, batch, rows, runs[3 * i], runs[3 * i + 1], runs[3 * i + 2]);
+  return PD_OK;
 }
 
 int fd_forward(const fd_model* m, const float* audio, const float* cond, const float* steps, float* eps,
