@@ -580,6 +580,52 @@ typedef struct {
 int pd_dur_forward(const pd_dur* h, const pd_dur_inputs* in, float* log_out, float* dur_out, int B, int T_txt,
                    void* workspace, size_t ws_bytes, void* stream);
 
+/* ================================================================ mel analysis
+ * pd_mel -- STFT.get_mel (modules/nsf_hifigan/nvSTFT.py:48-98), the analysis half of the vocoder contract
+ * (component/vocoder/nsf_hifigan.py:93-110 wav2spec): reflect padding, a center=False STFT with a periodic
+ * Hann window, the magnitude, the key-shift rescaling of the bins, the mel filterbank and
+ * log(clamp(., clip_val)), in one kernel.  fp32 only.  With
+ *   f = 2^(keyshift/12), nf = round(n_fft f), wn = round(win_size f), hn = round(hop_size speed)
+ * (round half to even, as numpy) a signal of L samples is padded by (wn - hn)/2 on the left and
+ * (wn - hn + 1)/2 on the right and gives T = 1 + (L + wn - hn - nf) / hn frames; frame t covers the padded
+ * samples [t hn, t hn + nf), the window sits centred in it.  Of the n_fft/2 + 1 output bins the first
+ * nb = min(n_fft/2, nf/2) + 1 are DFT bins of the nf-point frame (times win_size / wn when keyshift != 0),
+ * the rest are zero.  center=True is not offered.  A handle serves one (keyshift, speed). */
+typedef struct pd_mel pd_mel;
+
+typedef struct {
+  int n_fft;       /* 2048 (SVS), 1024; <= 65536                                        */
+  int win_size;    /* <= n_fft                                                          */
+  int hop_size;
+  int n_mels;      /* <= 128                                                            */
+  float keyshift;  /* semitones, 0 = none                                               */
+  float speed;     /* 1 = none                                                          */
+  float clip_val;  /* 1e-5, > 0                                                         */
+} pd_mel_dims;
+
+/* mel_basis: device, [n_mels][n_fft/2 + 1] row-major (librosa.filters.mel's layout), read on `stream`.
+ * Builds the two windowed DFT tables on the device (double precision, phase reduced as the integer
+ * (n k) mod nf, rounded once to f32) into the handle's weight pool.  Dimensions whose 31 hops + one
+ * frame exceed the 160 KiB LDS, or n_mels > 128, return PD_ERR_UNSUPPORTED. */
+int pd_mel_create(const pd_mel_dims* dims, const float* mel_basis, void* stream, pd_mel** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
+void pd_mel_destroy(pd_mel* h);
+/* T for a signal of n_samples; 0 below pd_mel_min_samples. */
+int pd_mel_frames(const pd_mel* h, int n_samples);
+/* The shortest legal signal: the larger pad + 1 (reflect padding needs L > pad), and at least one
+ * whole frame (nf - wn + hn, which only exceeds the former when win_size < n_fft). */
+int pd_mel_min_samples(const pd_mel* h);
+/* 0: the kernel needs no scratch (`workspace` may be NULL). */
+size_t pd_mel_workspace_size(const pd_mel* h, int B, int L);
+/* wav [B][L] -> out [B][T][n_mels] time-major = out_scale * log(max(mel, clip_val)), T = pd_mel_frames(h, L);
+ * spec_out [B][T][n_fft/2 + 1] (the magnitude spectrum) or NULL.  lens: int32 [B] samples per row or NULL;
+ * row b then equals the signal of lens[b] samples analysed alone, its frames past pd_mel_frames(h, lens[b])
+ * are unspecified; a lens[b] outside [pd_mel_min_samples, L] is clamped into it (that row's output is
+ * unspecified, every access stays inside the row).  A frame's values do not depend on its batch row, on B
+ * or on where it falls in a block.  L < pd_mel_min_samples returns PD_ERR_ARG. */
+int pd_mel_forward(const pd_mel* h, const float* wav, const int* lens, float out_scale, float* out, float* spec_out,
+                   int B, int L, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

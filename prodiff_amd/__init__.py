@@ -13,6 +13,8 @@ Drop-in replacements for the reference hot path (see DESIGN.md / INTEGRATION.md)
         <- modules/variance_predictor/pitch_predictor.py, dur_predictor.py
   * prodiff_amd.nsf_hifigan.Generator / NsfHifiGAN (registered vocoder)
         <- modules/nsf_hifigan/models.py, component/vocoder/nsf_hifigan.py
+  * prodiff_amd.mel.STFT / mel_filterbank (get_mel on the GPU; NsfHifiGAN.wav2spec)
+        <- modules/nsf_hifigan/nvSTFT.py:STFT, librosa.filters.mel
 All compute runs in libprodiff_hip.so (hand-written gfx950 HIP kernels).
 """
 from .prodiff import GaussianDiffusion, WaveNet  # noqa: F401
@@ -21,6 +23,8 @@ from .reflow import PitchRectifiedFlow, RectifiedFlow  # noqa: F401
 from .nsf_hifigan import Generator as NsfGenerator, NsfHifiGAN  # noqa: F401
 from .teacher import ProDiffTeacher  # noqa: F401
 from .variance import DurPredictor, PitchPredictor  # noqa: F401
+from .mel import STFT, mel_filterbank  # noqa: F401
 
 __all__ = ["WaveNet", "GaussianDiffusion", "FastDiff", "sampling_given_noise_schedule", "RectifiedFlow",
-           "PitchRectifiedFlow", "NsfGenerator", "NsfHifiGAN", "ProDiffTeacher", "PitchPredictor", "DurPredictor"]
+           "PitchRectifiedFlow", "NsfGenerator", "NsfHifiGAN", "ProDiffTeacher", "PitchPredictor", "DurPredictor",
+           "STFT", "mel_filterbank"]

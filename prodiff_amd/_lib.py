@@ -87,6 +87,11 @@ class pd_dur_inputs(C.Structure):
                 ("txt_lens", C.c_void_p)]
 
 
+class pd_mel_dims(C.Structure):
+    _fields_ = [("n_fft", C.c_int), ("win_size", C.c_int), ("hop_size", C.c_int), ("n_mels", C.c_int),
+                ("keyshift", C.c_float), ("speed", C.c_float), ("clip_val", C.c_float)]
+
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -149,6 +154,12 @@ _SIGS = {
     "nsf_set_option": (C.c_int, [_VP, C.c_int, C.c_int]),
     "nsf_forward": (C.c_int, [_VP, _VP, C.c_float, _VP, _VP, _VP, C.c_ulonglong, _VP, _VP, _VP, C.c_int, C.c_int,
                               _VP, C.c_size_t, _VP]),
+    "pd_mel_create": (C.c_int, [C.POINTER(pd_mel_dims), _VP, _VP, C.POINTER(_VP)]),
+    "pd_mel_destroy": (None, [_VP]),
+    "pd_mel_frames": (C.c_int, [_VP, C.c_int]),
+    "pd_mel_min_samples": (C.c_int, [_VP]),
+    "pd_mel_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "pd_mel_forward": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -239,10 +250,8 @@ class NativeHandle:
         if self._num_params is not None and getattr(L, self._num_params)(C.byref(dims)) != len(tensors):
             raise HipError(f"{self.name}: parameter count does not match {self._num_params}")
         dev = tensors[0].device
-        arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
         h = C.c_void_p()
-        dt = PD_DTYPE_BF16 if self.dtype == "bf16" else PD_DTYPE_F32
-        check(getattr(L, self._create)(C.byref(dims), arr, dt, stream_ptr(dev), C.byref(h)))
+        check(self._call_create(getattr(L, self._create), dims, tensors, stream_ptr(dev), h))
         for k, v in self.options.items():
             rc = getattr(L, self._set_option)(h, self.option_ids[k], v)
             if rc != 0:
@@ -251,6 +260,12 @@ class NativeHandle:
         self.close()
         self.h, self.sig, self._keep, self._device = h, signature, tensors, dev
         return h
+
+    def _call_create(self, create, dims, tensors, stream, h):
+        """The library's create call (a handle whose create takes other arguments overrides this)."""
+        arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        dt = PD_DTYPE_BF16 if self.dtype == "bf16" else PD_DTYPE_F32
+        return create(C.byref(dims), arr, dt, stream, C.byref(h))
 
     def _destroy_idle(self, h, dev):
         import torch

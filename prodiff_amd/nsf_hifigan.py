@@ -18,6 +18,7 @@ utterances.
 from __future__ import annotations
 
 import json
+import os
 import pathlib
 
 import numpy as np
@@ -28,6 +29,7 @@ from . import _lib
 from .vocoder import BaseVocoder, register_vocoder
 
 LOG10_TO_LN = 2.30259     # component/vocoder/nsf_hifigan.py:53
+LN_TO_LOG10 = 0.434294    # component/vocoder/nsf_hifigan.py:109
 
 
 def _get(h, k, default=None):
@@ -242,3 +244,24 @@ class NsfHifiGAN(BaseVocoder):
         f0 = kwargs.get("f0")
         f0 = None if f0 is None else torch.as_tensor(np.asarray(f0, np.float32), device=dev)[None]
         return self.spec2wav_torch(c, f0=f0).cpu().numpy()
+
+    @staticmethod
+    def wav2spec(inp, hparams=None, keyshift=0, speed=1, device=None):
+        """nsf_hifigan.py:93-110: -> (wav numpy [L], log10 mel numpy [T, bins]).  ``inp``: a float array or
+        tensor [L], or the path of a mono / multi-channel PCM16, PCM32 or float32 WAV whose rate must be
+        ``audio_sample_rate`` (the reference resamples through librosa; there is no resampler here)."""
+        from .mel import STFT, read_wav
+        hp = hparams
+        stft = STFT(hp["audio_sample_rate"], hp["audio_num_mel_bins"], hp["fft_size"], hp["win_size"], hp["hop_size"],
+                    hp["fmin"], hp["fmax"])
+        if isinstance(inp, (str, os.PathLike)):
+            wav = torch.from_numpy(read_wav(inp, stft.target_sr))
+        else:
+            wav = torch.as_tensor(inp).detach().float().reshape(-1).cpu()
+        dev = torch.device(device if device is not None else "cuda")
+        try:
+            mel = stft.get_mel_time_major(wav[None].to(dev), keyshift=keyshift, speed=speed, out_scale=LN_TO_LOG10)[0]
+            mel = mel.cpu().numpy()
+        finally:
+            stft.close()
+        return wav.numpy(), mel

@@ -133,3 +133,10 @@ class FastDiff(BaseVocoder):
         c = torch.as_tensor(np.asarray(mel), dtype=torch.float32, device=self.device)[None]
         wav = self.spec2wav_batch(c, x_T=kwargs.get("x_T"), noise=kwargs.get("noise"), seed=kwargs.get("seed"))
         return wav[:, None].cpu().numpy()
+
+    @staticmethod
+    def wav2spec(wav_fn, hparams=None, return_linear=False):
+        raise NotImplementedError(
+            "FastDiff.wav2spec is not implemented: the reference goes through process_utterance (a librosa STFT "
+            "plus loudness normalisation, component/vocoder/fastdiff.py:128-142), which this library does not "
+            "restate; NsfHifiGAN.wav2spec and prodiff_amd.STFT are the native analysis path")
