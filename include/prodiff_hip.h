@@ -626,6 +626,56 @@ size_t pd_mel_workspace_size(const pd_mel* h, int B, int L);
 int pd_mel_forward(const pd_mel* h, const float* wav, const int* lens, float out_scale, float* out, float* spec_out,
                    int B, int L, void* workspace, size_t ws_bytes, void* stream);
 
+/* ================================================================ sample-rate conversion
+ * pd_resample -- the polyphase windowed-sinc resampler that torchaudio.functional.resample defines, which the
+ * reference reaches as torchaudio.transforms.Resample(sr, 16000, lowpass_filter_width=128) in front of the
+ * RMVPE pitch extractor (component/pe/rmvpe.py:49); its other two resamplers, librosa.load(sr=) in wav2spec
+ * (component/vocoder/nsf_hifigan.py:96) and librosa.resample(..., 'kaiser_best') (utils/data_gen_utils.py:51),
+ * are soxr / resampy filters that this one replaces but does not reproduce sample for sample.  fp32 only.  With
+ *   g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g, base = min(o, n) rolloff,
+ *   W = ceil(lowpass_filter_width o / base), K = 2 W + o,
+ *   t = clamp(((k - W) / o - p / n) base, -lowpass_filter_width, lowpass_filter_width),
+ *   h[p][k] = sinc(t) w(t) base / o,   w = cos(pi t / (2 width))^2 (hann), I0(beta sqrt(1 - (t / width)^2)) / I0(beta) (kaiser)
+ * (float64, rounded once to f32) a row of L samples gives ceil(n L / o) outputs
+ *   y[q n + p] = sum_{k < K} h[p][k] x[q o + k - W],   x zero outside [0, L),
+ * each one f32 fmaf chain from zero over k ascending. */
+typedef struct pd_resample pd_resample;
+
+#define PD_RESAMPLE_HANN 0    /* sinc_interp_hann   */
+#define PD_RESAMPLE_KAISER 1  /* sinc_interp_kaiser */
+
+typedef struct {
+  int orig_freq, new_freq;   /* Hz, > 0 (only their ratio matters)                         */
+  int lowpass_filter_width;  /* zero crossings of the sinc kept on each side: 6, 64, 128   */
+  double rolloff;            /* 0.99: cutoff as a fraction of the lower Nyquist frequency  */
+  int method;                /* PD_RESAMPLE_HANN / PD_RESAMPLE_KAISER                      */
+  double beta;               /* Kaiser only, in [0, 256]: 14.769656459379492               */
+} pd_resample_dims;
+
+/* Builds the table on the device (double precision, one rounding) into the handle's weight pool, stream-ordered.
+ * Null or non-positive arguments return PD_ERR_ARG before anything is allocated.  A block keeps the samples of
+ * 32 output frames and their 32 n outputs in LDS: a pair with 32 (o + n) + 4 W floats beyond the 160 KiB LDS
+ * (or a table beyond 64 MiB) returns PD_ERR_UNSUPPORTED.  Every pair of common audio rates (8 to 192 kHz, o and
+ * n <= 640) fits at the widths above. */
+int pd_resample_create(const pd_resample_dims* dims, void* stream, pd_resample** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
+void pd_resample_destroy(pd_resample* h);
+/* ceil(n n_samples / o), in 64-bit integers; 0 for a null handle or n_samples <= 0. */
+size_t pd_resample_out_samples(const pd_resample* h, int n_samples);
+/* The reduced rates and the half width W (K = 2 W + o taps per phase); any pointer may be NULL. */
+int pd_resample_taps(const pd_resample* h, int* o, int* n, int* W);
+/* table_out: device f32 [n][K], the table h as the kernel uses it, written on `stream`. */
+int pd_resample_kernel(const pd_resample* h, float* table_out, void* stream);
+/* 0: the kernel needs no scratch (`workspace` may be NULL). */
+size_t pd_resample_workspace_size(const pd_resample* h, int B, int L);
+/* wav [B][L] -> out [B][pd_resample_out_samples(h, L)].  lens: int32 [B] samples per row or NULL; row b then
+ * equals its first lens[b] samples resampled alone, its outputs past pd_resample_out_samples(h, lens[b]) are
+ * unspecified (not written); a lens[b] outside [0, L] is clamped into it.  An output's value does not depend on
+ * its batch row, on B or on where its frame falls in a block.  Samples must be finite (the table's zero padding
+ * multiplies neighbouring samples).  One launch, stream-ordered, no allocation. */
+int pd_resample_forward(const pd_resample* h, const float* wav, const int* lens, float* out, int B, int L,
+                        void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

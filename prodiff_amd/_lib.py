@@ -92,6 +92,11 @@ class pd_mel_dims(C.Structure):
                 ("keyshift", C.c_float), ("speed", C.c_float), ("clip_val", C.c_float)]
 
 
+class pd_resample_dims(C.Structure):
+    _fields_ = [("orig_freq", C.c_int), ("new_freq", C.c_int), ("lowpass_filter_width", C.c_int),
+                ("rolloff", C.c_double), ("method", C.c_int), ("beta", C.c_double)]
+
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -160,6 +165,13 @@ _SIGS = {
     "pd_mel_min_samples": (C.c_int, [_VP]),
     "pd_mel_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "pd_mel_forward": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_resample_create": (C.c_int, [C.POINTER(pd_resample_dims), _VP, C.POINTER(_VP)]),
+    "pd_resample_destroy": (None, [_VP]),
+    "pd_resample_out_samples": (C.c_size_t, [_VP, C.c_int]),
+    "pd_resample_taps": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pd_resample_kernel": (C.c_int, [_VP, _VP, _VP]),
+    "pd_resample_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "pd_resample_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -237,10 +249,11 @@ class NativeHandle:
         if not t.is_cuda:
             raise HipError(f"{self.name} parameters must live on the GPU (call .cuda())")
 
-    def get(self, signature, build):
+    def get(self, signature, build, device=None):
         """The handle for ``signature``: the live one if it was built for the same signature, else a
         new one from ``build() -> (dims struct, contiguous float32 tensors in the C-ABI order)``; the
-        old handle is closed once the new one stands."""
+        old handle is closed once the new one stands.  ``device``: where a handle that takes no
+        tensors is created."""
         if self.h is not None and signature == self.sig:
             return self.h
         L = lib()
@@ -249,7 +262,7 @@ class NativeHandle:
             self.require_gpu(t)
         if self._num_params is not None and getattr(L, self._num_params)(C.byref(dims)) != len(tensors):
             raise HipError(f"{self.name}: parameter count does not match {self._num_params}")
-        dev = tensors[0].device
+        dev = tensors[0].device if tensors else device
         h = C.c_void_p()
         check(self._call_create(getattr(L, self._create), dims, tensors, stream_ptr(dev), h))
         for k, v in self.options.items():

@@ -159,7 +159,17 @@ class STFT:
 # ---------------------------------------------------------------- WAV files
 def read_wav(path, expect_sr=None):
     """A PCM16 / PCM32 / float32 RIFF WAV, mono or multi-channel -> float32 [n] in [-1, 1), channels
-    averaged.  ``expect_sr``: raise if the file's rate differs (there is no resampler here)."""
+    averaged.  ``expect_sr``: raise if the file's rate differs (there is no resampler here: read_wav_rate
+    returns the file's rate, prodiff_amd.resample converts)."""
+    return _read_wav(path, expect_sr)[0]
+
+
+def read_wav_rate(path):
+    """``read_wav`` of a file at any rate -> (float32 [n], sample_rate)."""
+    return _read_wav(path, None)
+
+
+def _read_wav(path, expect_sr):
     import struct
     with open(path, "rb") as f:
         data = f.read()
@@ -193,4 +203,4 @@ def read_wav(path, expect_sr=None):
     if channels < 1:
         raise ValueError(f"{path}: no channels")
     x = x[:len(x) // channels * channels].reshape(-1, channels)
-    return np.ascontiguousarray(x.mean(axis=1, dtype=np.float64).astype(np.float32) if channels > 1 else x[:, 0])
+    return np.ascontiguousarray(x.mean(axis=1, dtype=np.float64).astype(np.float32) if channels > 1 else x[:, 0]), int(sr)

@@ -246,22 +246,42 @@ class NsfHifiGAN(BaseVocoder):
         return self.spec2wav_torch(c, f0=f0).cpu().numpy()
 
     @staticmethod
-    def wav2spec(inp, hparams=None, keyshift=0, speed=1, device=None):
+    def wav2spec(inp, hparams=None, keyshift=0, speed=1, device=None, resample=False, orig_sr=None):
         """nsf_hifigan.py:93-110: -> (wav numpy [L], log10 mel numpy [T, bins]).  ``inp``: a float array or
         tensor [L], or the path of a mono / multi-channel PCM16, PCM32 or float32 WAV whose rate must be
-        ``audio_sample_rate`` (the reference resamples through librosa; there is no resampler here)."""
-        from .mel import STFT, read_wav
+        ``audio_sample_rate`` (the reference resamples through librosa; there is no resampler here unless
+        ``resample=True`` asks for one).  With ``resample=True`` a file at another rate -- or an array
+        whose rate ``orig_sr`` names -- is converted on the GPU by prodiff_amd.resample with KAISER_BEST
+        before the mel, and the returned wav is the converted signal.  That is a windowed-sinc filter of
+        resampy's 'kaiser_best' design, NOT the reference's ``librosa.load`` (soxr): the result is not
+        sample-equal to the reference's, whose resampler cannot be reproduced here."""
+        from .mel import STFT, read_wav, read_wav_rate
+        from .resample import KAISER_BEST, Resample
         hp = hparams
         stft = STFT(hp["audio_sample_rate"], hp["audio_num_mel_bins"], hp["fft_size"], hp["win_size"], hp["hop_size"],
                     hp["fmin"], hp["fmax"])
+        sr = int(stft.target_sr)
         if isinstance(inp, (str, os.PathLike)):
-            wav = torch.from_numpy(read_wav(inp, stft.target_sr))
+            if resample:
+                wav, sr = read_wav_rate(inp)
+                wav = torch.from_numpy(wav)
+            else:
+                wav = torch.from_numpy(read_wav(inp, stft.target_sr))
         else:
             wav = torch.as_tensor(inp).detach().float().reshape(-1).cpu()
+            if resample and orig_sr is not None:
+                sr = int(orig_sr)
         dev = torch.device(device if device is not None else "cuda")
+        rs = Resample(sr, int(stft.target_sr), **KAISER_BEST) if sr != int(stft.target_sr) else None
         try:
-            mel = stft.get_mel_time_major(wav[None].to(dev), keyshift=keyshift, speed=speed, out_scale=LN_TO_LOG10)[0]
+            y = wav[None].to(dev)
+            if rs is not None:
+                y = rs(y)
+                wav = y[0].cpu()
+            mel = stft.get_mel_time_major(y, keyshift=keyshift, speed=speed, out_scale=LN_TO_LOG10)[0]
             mel = mel.cpu().numpy()
         finally:
             stft.close()
+            if rs is not None:
+                rs.close()
         return wav.numpy(), mel
