@@ -676,6 +676,75 @@ size_t pd_resample_workspace_size(const pd_resample* h, int B, int L);
 int pd_resample_forward(const pd_resample* h, const float* wav, const int* lens, float* out, int B, int L,
                         void* workspace, size_t ws_bytes, void* stream);
 
+/* ================================================================ pitch extraction
+ * pd_mel_create_centered -- a second constructor of pd_mel with the framing of torch.stft(center=True), which
+ * the RMVPE front end uses (modules/rmvpe/spec.py:48-56): reflect padding of nf/2 samples on both sides,
+ * T = 1 + L / hn frames, frame t centred on sample t hn.  Everything else (window, key shift, bins, basis, log)
+ * is as pd_mel_create; pd_mel_frames and pd_mel_min_samples (nf/2 + 1) follow the handle's framing. */
+int pd_mel_create_centered(const pd_mel_dims* dims, const float* mel_basis, void* stream, pd_mel** out);
+
+/* pd_rmvpe -- E2E0 (modules/rmvpe/model.py:8-32): the log-mel as a one-channel image [B,1,T,F] through
+ * encoder.bn (eval BatchNorm on the input, applied to the in-range pixels only: the first conv's zero padding
+ * comes after it), en_de_layers encoder levels of n_blocks ConvBlockRes at en_out_channels * 2^i channels, each
+ * followed by AvgPool2d(2,2) (the unpooled output is the level's skip), inter_layers * n_blocks ConvBlockRes at
+ * the bottom, en_de_layers decoder levels (ConvTranspose2d 3x3 stride 2 padding 1 output_padding 1 without
+ * bias + BN + ReLU, cat with the skip, n_blocks ConvBlockRes), cnn = Conv2d(en_out_channels, 3, 3x3) with bias,
+ * feat[b][t][c * n_mels + f], then a bidirectional one-layer GRU (gate order r, z, n; h_0 = 0) and
+ * Linear + Sigmoid, or with n_gru = 0 Linear + Sigmoid on feat (deepunet.py, seq.py).
+ *   ConvBlockRes(x) = ReLU(BN(conv3x3(ReLU(BN(conv3x3(x)))))) + s(x), s = identity, or a 1x1 conv with bias
+ * when the channel count changes.  Every BatchNorm is the eval form (eps 1e-5); create folds each post-conv one
+ * into its conv in double precision (w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps)), rounded
+ * once.  fp32 only. */
+typedef struct pd_rmvpe pd_rmvpe;
+
+typedef struct {
+  int n_blocks;         /* 4; 1..16                                                        */
+  int n_gru;            /* 1; 0 (Linear head on feat) or 1                                 */
+  int en_de_layers;     /* 5; 1..5, n_mels a multiple of 2^en_de_layers                    */
+  int inter_layers;     /* 4; 1..16                                                        */
+  int en_out_channels;  /* 16; a multiple of 16, <= 256                                    */
+  int n_mels;           /* 128; 3 n_mels a multiple of 32                                  */
+  int n_class;          /* 360                                                             */
+  int gru_hidden;       /* 256 (the only size the recurrence kernel is built for)          */
+} pd_rmvpe_dims;
+
+/* Parameter order = the reference state-dict order without any num_batches_tracked and without unet.tf.* (the
+ * TimbreFilter is built but never called).  With bn(p) = p.{weight,bias,running_mean,running_var} and
+ * block(p) = p.conv.0.weight [Co,Ci,3,3], bn(p.conv.1), p.conv.3.weight [Co,Co,3,3], bn(p.conv.4), and where
+ * Ci != Co p.shortcut.{weight [Co,Ci,1,1],bias}:
+ *   bn(unet.encoder.bn);
+ *   for i < en_de_layers, j < n_blocks: block(unet.encoder.layers.i.conv.j)       (Ci = 1 for i = j = 0);
+ *   for i < inter_layers, j < n_blocks: block(unet.intermediate.layers.i.conv.j);
+ *   for i < en_de_layers: unet.decoder.layers.i.conv1.0.weight [Ci,Co,3,3], bn(unet.decoder.layers.i.conv1.1),
+ *       for j < n_blocks: block(unet.decoder.layers.i.conv2.j)                    (Ci = 2 Co for j = 0);
+ *   cnn.{weight [3,C,3,3],bias};
+ *   n_gru = 1: fc.0.gru.{weight_ih_l0 [768,3 n_mels],weight_hh_l0 [768,256],bias_ih_l0,bias_hh_l0}, the same four
+ *       with the suffix _reverse, fc.1.{weight [n_class,512],bias};  n_gru = 0: fc.0.{weight [n_class,3 n_mels],bias}.
+ * 0 for dimensions outside the supported set. */
+int pd_rmvpe_num_params(const pd_rmvpe_dims* dims);
+/* Folds and packs every parameter into the handle's weight pool on `stream` (the caller's tensors are not read
+ * after the stream has passed the call).  A dtype other than PD_DTYPE_F32, or dimensions outside the ranges
+ * above, return PD_ERR_UNSUPPORTED before anything is allocated. */
+int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int dtype, void* stream, pd_rmvpe** out);
+/* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
+void pd_rmvpe_destroy(pd_rmvpe* h);
+size_t pd_rmvpe_workspace_size(const pd_rmvpe* h, int B, int T);
+/* mel [B][T][n_mels] time-major natural-log mel (what pd_mel_forward writes) -> hidden [B][T][n_class], the
+ * salience in [0, 1]; feat [B][T][3 n_mels] (the cnn output, feature index c n_mels + f) or NULL.  T must be a
+ * positive multiple of 2^en_de_layers (PD_ERR_ARG otherwise; the caller pads with the value 0.0 as
+ * component/pe/rmvpe.py:29-33 does, those frames are network input).  All rows share T.  Stream-ordered, no
+ * allocation, no synchronisation, capturable.  An output row depends neither on B nor on its batch position. */
+int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* feat, int B, int T, void* workspace,
+                     size_t ws_bytes, void* stream);
+/* to_local_average_f0 (modules/rmvpe/utils.py:8-23): hidden [B][T][n_class] -> f0 [B][T] in Hz.  c = the first
+ * index of the row maximum, or center[b][t] (int64 [B][T], device) when center is non-NULL, clamped into
+ * [0, n_class); over i in [max(c - 4, 0), min(c + 5, n_class)): cents = sum h_i (20 i + cents_const) /
+ * (sum h_i + [sum h_i == 0]), f0 = 10 * 2^(cents / 1200), and f0 = 0 where the row maximum is < thred.  The sums
+ * run in double precision; cents_const is the reference's CONST = 1997.3794084376191, passed as a double so that
+ * it is not rounded to f32 on the way. */
+int pd_rmvpe_decode(const float* hidden, float* f0, int B, int T, int n_class, float thred, const long long* center,
+                    double cents_const, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

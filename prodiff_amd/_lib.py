@@ -97,6 +97,11 @@ class pd_resample_dims(C.Structure):
                 ("rolloff", C.c_double), ("method", C.c_int), ("beta", C.c_double)]
 
 
+class pd_rmvpe_dims(C.Structure):
+    _fields_ = [("n_blocks", C.c_int), ("n_gru", C.c_int), ("en_de_layers", C.c_int), ("inter_layers", C.c_int),
+                ("en_out_channels", C.c_int), ("n_mels", C.c_int), ("n_class", C.c_int), ("gru_hidden", C.c_int)]
+
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -172,6 +177,13 @@ _SIGS = {
     "pd_resample_kernel": (C.c_int, [_VP, _VP, _VP]),
     "pd_resample_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "pd_resample_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_mel_create_centered": (C.c_int, [C.POINTER(pd_mel_dims), _VP, _VP, C.POINTER(_VP)]),
+    "pd_rmvpe_num_params": (C.c_int, [C.POINTER(pd_rmvpe_dims)]),
+    "pd_rmvpe_create": (C.c_int, [C.POINTER(pd_rmvpe_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
+    "pd_rmvpe_destroy": (None, [_VP]),
+    "pd_rmvpe_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "pd_rmvpe_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_rmvpe_decode": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_double, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -323,18 +323,24 @@ struct pd_mel {
   MelPlan p;
   WeightPool weights;   // the two DFT tables and the packed mel basis
   float *tc = nullptr, *ts = nullptr, *bt = nullptr;
+  bool centered = false;   // torch.stft(center=True) framing (pd_mel_create_centered)
 };
 
-extern "C" {
+namespace {
 
-int pd_mel_create(const pd_mel_dims* dims, const float* mel_basis, void* stream, pd_mel** out) {
+int mel_create(const pd_mel_dims* dims, const float* mel_basis, bool centered, void* stream, pd_mel** out) {
   PD_CHECK_ARG(dims && mel_basis && out, "null pointer");
   MelPlan p;
   PD_TRY(make_plan(*dims, &p));
+  if (centered) {   // reflect nf/2 on both sides: frame t is centred on sample t hn
+    p.pad_l = p.pad_r = p.nf / 2;
+    p.min_len = p.nf / 2 + 1;
+  }
   hipStream_t st = (hipStream_t)stream;
   pd_mel* h = new pd_mel();
   h->d = *dims;
   h->p = p;
+  h->centered = centered;
   WeightPool& wp = h->weights;
   const size_t tab = (size_t)p.nrows * p.nbp;
   wp.add(&h->tc, tab);
@@ -356,12 +362,25 @@ int pd_mel_create(const pd_mel_dims* dims, const float* mel_basis, void* stream,
   return PD_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int pd_mel_create(const pd_mel_dims* dims, const float* mel_basis, void* stream, pd_mel** out) {
+  return mel_create(dims, mel_basis, false, stream, out);
+}
+
+int pd_mel_create_centered(const pd_mel_dims* dims, const float* mel_basis, void* stream, pd_mel** out) {
+  return mel_create(dims, mel_basis, true, stream, out);
+}
+
 void pd_mel_destroy(pd_mel* h) { delete h; }
 
 int pd_mel_min_samples(const pd_mel* h) { return h ? h->p.min_len : 0; }
 
 int pd_mel_frames(const pd_mel* h, int n_samples) {
   if (!h || n_samples < h->p.min_len) return 0;
+  if (h->centered) return 1 + n_samples / h->p.hn;
   const long long T = 1 + ((long long)n_samples + h->p.wn - h->p.hn - h->p.nf) / h->p.hn;
   return T > 0x7fffffffll ? 0 : (int)T;
 }

@@ -1,0 +1,885 @@
+// RMVPE pitch extractor (include/prodiff_hip.h, "pitch extraction"): E2E0 of modules/rmvpe/model.py -- the deep
+// U-Net of deepunet.py, the 3-channel output conv, the BiGRU of seq.py and the 360-class sigmoid head -- and
+// to_local_average_f0 of modules/rmvpe/utils.py.  fp32 only.
+//
+// Activations are channels-last images [B][T][F][C] (T = frames, F = mel bins), so the time-major log-mel
+// that pd_mel_forward writes already is the one-channel input image.
+//
+//   conv3x3_kernel    every 3x3 conv with C_in a multiple of 16 as an implicit GEMM on v_mfma_f32_32x32x2_f32:
+//                     M = 128 pixels of one image tile per block (32 per wave), N = 32 output channels,
+//                     K = C_in in chunks of 16 channels x 9 taps x 16, ascending.  A chunk's (rows + 2) x
+//                     (cols + 2) x 16 window is staged in LDS once for all nine taps (zero outside the image).
+//                     The K axis may run over two source tensors (the decoder's cat is never materialised).
+//                     SC: the block's 1x1 shortcut from the same staged centre pixels into a second
+//                     accumulator, written to its own tensor, which the block's second conv adds as residual.
+//                     `stuffed`: the source is read as its zero-stuffed 2x upsampling, which makes the kernel
+//                     the stride-2 transposed conv (weights flipped at pack time); a product with a stuffed
+//                     zero leaves the fmaf chain's value unchanged, so each output is the chain over its own
+//                     1, 2 or 4 taps.
+//   conv_in_kernel    the first conv (C_in = 1, K = 9) and its 1x1 shortcut on the VALU, encoder.bn applied to
+//                     the in-range pixels as they are read (its shift must not reach the zero padding).
+//   conv_out_kernel   the `cnn` conv (C_out = 3) on the VALU, writing feat[b][t][c * F + f].
+//   avgpool_kernel    AvgPool2d(2, 2).
+//   gru_kernel        the recurrence, one block per direction and group of 16 batch rows (the M side of
+//                     v_mfma_f32_16x16x4_f32), 8 waves x 32 hidden units x the three gates; W_hh streams from
+//                     L2 every step, h lives in LDS.  No block waits on another; the time loop has T trips.
+//   the GRU input projection and the Linear head run on the implicit-GEMM engine (gemm.h).
+//
+// Every output element is one f32 fmaf chain in a fixed order that does not depend on B, on the batch row
+// or on the tile position.
+#include <cmath>
+#include <vector>
+
+#include "../../include/prodiff_hip.h"
+#include "common.h"
+#include "gemm.h"
+#include "kernels.h"
+
+using namespace pd;
+
+namespace {
+
+constexpr int CV_CK = 16;          // channels per K chunk
+constexpr int CV_LD = 20;          // LDS floats per window pixel (16 + 4: rows stay 16-byte aligned)
+constexpr int CV_PIX = 128;        // pixels per block
+constexpr int CV_MAXWIN = 208;     // (32 + 2) x (4 + 2) = 204 is the largest window
+constexpr int GRU_H = 256;
+constexpr int GRU_LD = GRU_H + 4;
+constexpr int GRU_ROWS = 16;        // batch rows per recurrence block: the M side of the 16x16x4 MFMA
+constexpr int U_RMVPE_XPROJ = 30, U_RMVPE_HEAD = 31;
+
+// ------------------------------------------------------------------ create-time kernels
+// BN fold factor of channel co in double: gamma / sqrt(var + eps)
+__device__ __forceinline__ double bn_scale(const float* g, const float* var, int co) {
+  return (double)g[co] / sqrt((double)var[co] + 1e-5);
+}
+
+// dst[((ct * nchunk + chunk) * taps + tap) * 32 + n][16] = w(co = ct * 32 + n, ci = chunk * 16 + q, tap) * scale(co)
+// src is Conv2d's [Cout][Cin][taps], or (transposed) ConvTranspose2d's [Cin][Cout][taps] read with the taps flipped.
+__global__ __launch_bounds__(256) void pack_conv2d_kernel(float* __restrict__ dst, const float* __restrict__ src,
+                                                          const float* g, const float* var, int cout, int cin,
+                                                          int taps, int transposed, long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int q = (int)(idx & 15), n = (int)((idx >> 4) & 31);
+  long long rest = idx >> 9;
+  const int tap = (int)(rest % taps);
+  rest /= taps;
+  const int nchunk = cin / CV_CK;
+  const int chunk = (int)(rest % nchunk), ct = (int)(rest / nchunk);
+  const int co = ct * 32 + n, ci = chunk * CV_CK + q;
+  float v = 0.f;
+  if (co < cout) {
+    const float w = transposed ? src[((long long)ci * cout + co) * taps + (taps - 1 - tap)]
+                               : src[((long long)co * cin + ci) * taps + tap];
+    v = g ? (float)((double)w * bn_scale(g, var, co)) : w;
+  }
+  dst[idx] = v;
+}
+
+// dst[co][k] = src[co][k] * scale(co), k < per
+__global__ __launch_bounds__(256) void fold_rows_kernel(float* __restrict__ dst, const float* __restrict__ src,
+                                                        const float* g, const float* var, int cout, int per) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= cout * per) return;
+  dst[idx] = (float)((double)src[idx] * bn_scale(g, var, idx / per));
+}
+
+// dst[co] = beta - mean * scale(co)
+__global__ __launch_bounds__(256) void fold_bias_kernel(float* __restrict__ dst, const float* g, const float* beta,
+                                                        const float* mean, const float* var, int cout) {
+  const int co = blockIdx.x * 256 + threadIdx.x;
+  if (co >= cout) return;
+  dst[co] = (float)((double)beta[co] - (double)mean[co] * bn_scale(g, var, co));
+}
+
+// encoder.bn on the single input channel: dst = {scale, shift}
+__global__ void input_bn_kernel(float* dst, const float* g, const float* beta, const float* mean, const float* var) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const double s = bn_scale(g, var, 0);
+    dst[0] = (float)s;
+    dst[1] = (float)((double)beta[0] - (double)mean[0] * s);
+  }
+}
+
+// W_hh [768][256] -> [24 tiles][16 chunks][32 rows][16]
+__global__ __launch_bounds__(256) void pack_whh_kernel(float* __restrict__ dst, const float* __restrict__ src) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= 3 * GRU_H * GRU_H) return;
+  const int q = idx & 15, n = (idx >> 4) & 31, chunk = (idx >> 9) & 15, tile = idx >> 13;
+  dst[idx] = src[(tile * 32 + n) * GRU_H + chunk * 16 + q];
+}
+
+// ------------------------------------------------------------------ forward kernels
+struct ConvArgs {
+  const float* src0;   // [B][Hs][Ws][c0]
+  const float* src1;   // [B][Hs][Ws][c1] or null (c1 = 0)
+  int c0, c1;
+  int H, W;            // output image; the source is H x W, or H/2 x W/2 when stuffed
+  int stuffed;
+  const float* wp;     // packed [ctiles][nchunk][9][32][16]
+  const float* bias;   // [ctiles * 32]
+  int relu;
+  const float* wsp;    // SC: packed 1x1 [ctiles][nchunk][32][16]
+  const float* bsc;    // SC: [ctiles * 32]
+  float* sc_out;       // SC: [B][H][W][cout]
+  const float* resid;  // [B][H][W][cout] or null, added after the ReLU
+  float* out;          // [B][H][W][cout]
+  int cout;
+  int tc, tr, tiles_x; // tile columns and rows (tc * tr = 128), tiles per image row
+};
+
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p);
+  const float4 b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+template <bool SC>
+__global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
+  __shared__ __attribute__((aligned(16))) float xs[CV_MAXWIN * CV_LD];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int b = blockIdx.z, ct = blockIdx.y;
+  const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+  const int y0 = ty * a.tr, x0 = tx * a.tc;
+  const int wc = a.tc + 2, winpix = (a.tr + 2) * wc;
+  const int Hs = a.stuffed ? a.H >> 1 : a.H, Ws = a.stuffed ? a.W >> 1 : a.W;
+  // the A operand of this lane: pixel m of the tile, channels 8 h .. 8 h + 7 of the chunk
+  const int m = wave * 32 + r, pr = m / a.tc, pc = m - pr * a.tc;
+  const float* abase = xs + (pr * wc + pc) * CV_LD + h * 8;
+  const int nchunk = (a.c0 + a.c1) / CV_CK;
+  const float* wrow = a.wp + ((long long)ct * nchunk * 9 * 32 + r) * 16 + h * 8;
+  const float* wsrow = SC ? a.wsp + ((long long)ct * nchunk * 32 + r) * 16 + h * 8 : nullptr;
+
+  f32x16 acc, acc2;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
+
+  for (int chunk = 0; chunk < nchunk; ++chunk) {
+    const int cb = chunk * CV_CK;
+    const bool first = cb < a.c0;
+    const float* src = first ? a.src0 : a.src1;
+    const int cs = first ? a.c0 : a.c1, coff = first ? cb : cb - a.c0;
+    // the chunk's weights are requested first: their L2 latency passes under the staging of the window
+    const float* wch = wrow + (long long)chunk * 9 * 512;
+    float wf[9][8], sf[8];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) load8(wch + tap * 512, wf[tap]);
+    if (SC) load8(wsrow + (long long)chunk * 512, sf);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();   // the previous chunk's reads are done
+    for (int idx = tid; idx < winpix * 4; idx += 256) {
+      const int p = idx >> 2, q = idx & 3;
+      const int wy = p / wc, wx = p - wy * wc;
+      const int gy = y0 - 1 + wy, gx = x0 - 1 + wx;
+      bool ok = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+      int sy = gy, sx = gx;
+      if (a.stuffed) { ok = ok && !(gy & 1) && !(gx & 1); sy = gy >> 1; sx = gx >> 1; }
+      sy = min(max(sy, 0), Hs - 1);
+      sx = min(max(sx, 0), Ws - 1);
+      float4 v = *reinterpret_cast<const float4*>(src + (((long long)b * Hs + sy) * Ws + sx) * cs + coff + q * 4);
+      if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(xs + p * CV_LD + q * 4) = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      float af[8];
+      load8(abase + ((tap / 3) * wc + (tap % 3)) * CV_LD, af);
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], wf[tap][kk], acc, 0, 0, 0);
+      if (SC && tap == 4) {
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], sf[kk], acc2, 0, 0, 0);
+      }
+    }
+  }
+
+  // D layout: column (output channel) = lane & 31, row (pixel) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+  const int n = ct * 32 + r;
+  if (n >= a.cout) return;
+  const float bv = a.bias[n];
+  const float bs = SC ? a.bsc[n] : 0.f;
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int mm = wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    const int qr = mm / a.tc, qc = mm - qr * a.tc;
+    const int gy = y0 + qr, gx = x0 + qc;
+    if (gy >= a.H || gx >= a.W) continue;
+    const long long o = (((long long)b * a.H + gy) * a.W + gx) * a.cout + n;
+    float v = acc[reg] + bv;
+    if (a.relu) v = fmaxf(v, 0.f);
+    if (a.resid) v += a.resid[o];
+    a.out[o] = v;
+    if (SC) a.sc_out[o] = acc2[reg] + bs;
+  }
+}
+
+// First conv: out[b][y][x][co] = relu(sum_tap w[co][tap] * bn(mel)[y + dy - 1][x + dx - 1] + bias[co]) and the
+// 1x1 shortcut sc[..][co] = ws[co] * bn(mel)[y][x] + bs[co]; bn(mel) is zero outside the image.
+__global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ mel, const float* __restrict__ inbn,
+                                                      const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const float* __restrict__ ws, const float* __restrict__ bs,
+                                                      float* __restrict__ out, float* __restrict__ sc, int H, int W,
+                                                      int cout, long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int co = (int)(idx % cout);
+  const long long pix = idx / cout;
+  const int x = (int)(pix % W);
+  const long long by = pix / W;
+  const int y = (int)(by % H);
+  const long long b = by / H;
+  const float scale = inbn[0], shift = inbn[1];
+  float acc = 0.f, centre = 0.f;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const int gy = y + tap / 3 - 1, gx = x + tap % 3 - 1;
+    const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
+    const float raw = mel[(b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)];
+    const float v = ok ? __builtin_fmaf(raw, scale, shift) : 0.f;
+    if (tap == 4) centre = v;
+    acc = __builtin_fmaf(w[co * 9 + tap], v, acc);
+  }
+  out[idx] = fmaxf(acc + bias[co], 0.f);
+  sc[idx] = __builtin_fmaf(ws[co], centre, bs[co]);
+}
+
+// cnn: Conv2d(cin, 3, 3x3, padding 1) with bias; feat[b][t][c * F + f], the K order is tap, then channel
+__global__ __launch_bounds__(256) void conv_out_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                       const float* __restrict__ bias, float* __restrict__ feat,
+                                                       int H, int W, int cin, long long total) {
+  const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= total) return;
+  const int f = (int)(pix % W);
+  const long long by = pix / W;
+  const int y = (int)(by % H);
+  const long long b = by / H;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int tap = 0; tap < 9; ++tap) {
+    const int gy = y + tap / 3 - 1, gx = f + tap % 3 - 1;
+    const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
+    const float* px = x + ((b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)) * cin;
+    for (int ci = 0; ci < cin; ci += 4) {
+      float4 v = *reinterpret_cast<const float4*>(px + ci);
+      if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float* wr = w + ((long long)c * cin + ci) * 9 + tap;
+        acc[c] = __builtin_fmaf(wr[0], v.x, acc[c]);
+        acc[c] = __builtin_fmaf(wr[9], v.y, acc[c]);
+        acc[c] = __builtin_fmaf(wr[18], v.z, acc[c]);
+        acc[c] = __builtin_fmaf(wr[27], v.w, acc[c]);
+      }
+    }
+  }
+  float* o = feat + (b * H + y) * (3ll * W) + f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[(long long)c * W] = acc[c] + bias[c];
+}
+
+// AvgPool2d(2, 2): [B][H][W][C] -> [B][H/2][W/2][C], four channels per thread
+__global__ __launch_bounds__(256) void avgpool_kernel(const float* __restrict__ x, float* __restrict__ out, int H,
+                                                      int W, int C, long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c4 = C >> 2, Ho = H >> 1, Wo = W >> 1;
+  const int c = (int)(idx % c4) * 4;
+  long long rest = idx / c4;
+  const int xo = (int)(rest % Wo);
+  rest /= Wo;
+  const int yo = (int)(rest % Ho);
+  const long long b = rest / Ho;
+  const float* p = x + (((b * H + 2 * yo) * W) + 2 * xo) * C + c;
+  const float4 v0 = *reinterpret_cast<const float4*>(p);
+  const float4 v1 = *reinterpret_cast<const float4*>(p + C);
+  const float4 v2 = *reinterpret_cast<const float4*>(p + (long long)W * C);
+  const float4 v3 = *reinterpret_cast<const float4*>(p + (long long)W * C + C);
+  float4 o;
+  o.x = ((v0.x + v1.x) + (v2.x + v3.x)) * 0.25f;
+  o.y = ((v0.y + v1.y) + (v2.y + v3.y)) * 0.25f;
+  o.z = ((v0.z + v1.z) + (v2.z + v3.z)) * 0.25f;
+  o.w = ((v0.w + v1.w) + (v2.w + v3.w)) * 0.25f;
+  *reinterpret_cast<float4*>(out + idx * 4) = o;
+}
+
+struct GruArgs {
+  const float* xp;    // [B][T][2 * 768]: W_ih x + b_ih, forward gates r z n then the reverse direction's
+  const float* whh;   // [2][24][16][32][16] packed
+  const float* bhh;   // [2][768]
+  float* out;         // [B][T][512]
+  int B, T;
+};
+
+__device__ __forceinline__ float sigmoid_exp(float v) { return 1.f / (1.f + expf(-v)); }
+__device__ __forceinline__ float tanh_exp(float v) { return 2.f / (1.f + expf(-2.f * v)) - 1.f; }
+
+// grid (2 directions, ceil(B / 16)), 8 waves.  Wave w owns hidden units 32 w .. 32 w + 31 of all three gates as two
+// 16-unit column tiles of v_mfma_f32_16x16x4_f32, the block's 16 batch rows on the M side: six independent
+// accumulators.  Lane (r = lane & 15, g = lane >> 4) supplies k = 4 g + j of a 16-deep chunk in step j (A: h of
+// row r from LDS, B: W_hh of unit r), one 16-byte read per operand, chunk and tile; the weights of the next chunk
+// (at a step's end: of the next step's first chunk) are in flight under the current chunk's MFMAs.  D: column =
+// lane & 15, row = 4 g + register, so a lane holds r, z and n of the same eight (row, unit) pairs.
+__global__ __launch_bounds__(512) void gru_kernel(const GruArgs a) {
+  __shared__ __attribute__((aligned(16))) float hs[GRU_ROWS * GRU_LD];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
+  const int dir = blockIdx.x, b0 = blockIdx.y * GRU_ROWS, nb = min(GRU_ROWS, a.B - b0);
+  for (int i = tid; i < GRU_ROWS * GRU_LD; i += 512) hs[i] = 0.f;
+  const float* bh = a.bhh + dir * 3 * GRU_H;
+  float bhr[2], bhz[2], bhn[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int n = wave * 32 + s * 16 + r;
+    bhr[s] = bh[n]; bhz[s] = bh[GRU_H + n]; bhn[s] = bh[2 * GRU_H + n];
+  }
+  // packed W_hh [dir][gate * 8 + wave][chunk][32][16]: this lane reads [..][s * 16 + r][4 g .. 4 g + 3]
+  // (a wave-uniform base in scalar registers plus one 32-bit lane offset: 96 precomputed per-lane pointers would not fit)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const float* wdir = a.whh + (long long)dir * 24 * 16 * 512;
+  const unsigned loff = r * 16 + 4 * g;
+  const float* arow = hs + r * GRU_LD + 4 * g;
+  auto load_w = [&](f32x4 (&w)[6], int chunk) {
+#pragma unroll
+    for (int gate = 0; gate < 3; ++gate)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const float* tile = wdir + ((gate * 8 + wave_u) * 16 + chunk) * 512 + s * 256;
+        w[gate * 2 + s] = *reinterpret_cast<const f32x4*>(tile + loff);
+      }
+  };
+  f32x4 acc[6];
+  auto run_chunk = [&](const f32x4 (&w)[6], int chunk) {
+    const f32x4 h4 = *reinterpret_cast<const f32x4*>(arow + chunk * 16);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(h4[k], w[j][k], acc[j], 0, 0, 0);
+  };
+  f32x4 w0[6], w1[6];
+  load_w(w0, 0);
+  __syncthreads();
+  for (int step = 0; step < a.T; ++step) {
+    const int t = dir ? a.T - 1 - step : step;
+    float xr[8], xz[8], xn[8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * g + i;
+        const float* px = a.xp + ((long long)(b0 + min(row, nb - 1)) * a.T + t) * (6 * GRU_H) + dir * 3 * GRU_H +
+                          wave * 32 + s * 16 + r;
+        xr[s * 4 + i] = px[0];
+        xz[s * 4 + i] = px[GRU_H];
+        xn[s * 4 + i] = px[2 * GRU_H];
+      }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int chunk = 0; chunk < 16; chunk += 2) {
+      load_w(w1, chunk + 1);
+      __builtin_amdgcn_sched_barrier(0);   // the loads stay one chunk ahead of their MFMAs
+      run_chunk(w0, chunk);
+      __builtin_amdgcn_sched_barrier(0);
+      load_w(w0, (chunk + 2) & 15);        // after the last chunk: the next step's first
+      __builtin_amdgcn_sched_barrier(0);
+      run_chunk(w1, chunk + 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    float hnew[8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float hold = hs[(4 * g + i) * GRU_LD + wave * 32 + s * 16 + r];
+        const float rg = sigmoid_exp(xr[s * 4 + i] + (acc[s][i] + bhr[s]));
+        const float zg = sigmoid_exp(xz[s * 4 + i] + (acc[2 + s][i] + bhz[s]));
+        const float ng = tanh_exp(xn[s * 4 + i] + rg * (acc[4 + s][i] + bhn[s]));
+        hnew[s * 4 + i] = (1.f - zg) * ng + zg * hold;
+      }
+    __syncthreads();   // every wave has read h
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * g + i, n = wave * 32 + s * 16 + r;
+        if (row < nb) {
+          hs[row * GRU_LD + n] = hnew[s * 4 + i];
+          a.out[((long long)(b0 + row) * a.T + t) * (2 * GRU_H) + dir * GRU_H + n] = hnew[s * 4 + i];
+        }
+      }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void sigmoid_kernel(const float* __restrict__ x, float* __restrict__ out, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = sigmoid_exp(x[i]);
+}
+
+// to_local_average_f0: one wave per frame
+__global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ hidden, const long long* __restrict__ center,
+                                                     float* __restrict__ f0, long long frames, int n_class, float thred,
+                                                     double cents0) {
+  const long long fr = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (fr >= frames) return;
+  const int lane = threadIdx.x & 63;
+  const float* row = hidden + fr * n_class;
+  float best = row[min(lane, n_class - 1)];
+  int bi = min(lane, n_class - 1);
+  for (int i = lane + 64; i < n_class; i += 64) {
+    const float v = row[i];
+    if (v > best) { best = v; bi = i; }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ov = __shfl_xor(best, off);
+    const int oi = __shfl_xor(bi, off);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  if (lane != 0) return;
+  long long c = center ? center[fr] : (long long)bi;
+  c = c < 0 ? 0 : (c > n_class - 1 ? n_class - 1 : c);
+  const int lo = max((int)c - 4, 0), hi = min((int)c + 5, n_class);
+  double num = 0.0, den = 0.0;
+  for (int i = lo; i < hi; ++i) {
+    const double hv = (double)row[i];
+    num += hv * (20.0 * i + cents0);
+    den += hv;
+  }
+  const double cents = num / (den + (den == 0.0 ? 1.0 : 0.0));
+  const double v = 10.0 * exp2(cents / 1200.0);
+  f0[fr] = best < thred ? 0.f : (float)v;
+}
+
+// ------------------------------------------------------------------ host side
+struct ConvW {
+  float* w = nullptr;    // packed main weights
+  float* b = nullptr;    // folded bias [ctiles * 32]
+  int cin = 0, cout = 0;
+};
+
+struct Block {
+  ConvW c1, c2;
+  float* ws = nullptr;   // packed 1x1 shortcut (cin != cout)
+  float* bs = nullptr;
+  bool sc = false;
+  int cin = 0, cout = 0;
+};
+
+int ctiles(int cout) { return (cout + 31) / 32; }
+size_t packed_conv(int cin, int cout, int taps) { return (size_t)ctiles(cout) * (cin / CV_CK) * taps * 32 * 16; }
+
+bool dims_ok(const pd_rmvpe_dims& d) {
+  if (d.n_gru != 0 && d.n_gru != 1) return false;
+  if (d.n_blocks < 1 || d.n_blocks > 16 || d.inter_layers < 1 || d.inter_layers > 16) return false;
+  if (d.en_de_layers < 1 || d.en_de_layers > 5) return false;
+  if (d.en_out_channels < 16 || d.en_out_channels % 16 != 0 || d.en_out_channels > 256) return false;
+  if (d.n_mels < 4 || d.n_mels > 1024 || d.n_mels % (1 << d.en_de_layers) != 0) return false;
+  if ((d.n_mels * 3) % 32 != 0) return false;          // feat rows feed the GEMM engine
+  if (d.n_class < 1 || d.n_class > 4096) return false;
+  if (d.gru_hidden != GRU_H) return false;
+  return true;
+}
+
+int block_params(int cin, int cout) { return 10 + (cin != cout ? 2 : 0); }
+
+int count_params(const pd_rmvpe_dims& d) {
+  const int L = d.en_de_layers, c0 = d.en_out_channels;
+  int n = 4;
+  for (int i = 0; i < L; ++i) {
+    const int cin = i == 0 ? 1 : c0 << (i - 1), cout = c0 << i;
+    n += block_params(cin, cout) + (d.n_blocks - 1) * block_params(cout, cout);
+  }
+  for (int i = 0; i < d.inter_layers; ++i) {
+    const int cin = i == 0 ? c0 << (L - 1) : c0 << L, cout = c0 << L;
+    n += block_params(cin, cout) + (d.n_blocks - 1) * block_params(cout, cout);
+  }
+  for (int i = 0; i < L; ++i) {
+    const int cout = c0 << (L - 1 - i);
+    n += 5 + block_params(2 * cout, cout) + (d.n_blocks - 1) * block_params(cout, cout);
+  }
+  n += 2;                       // cnn
+  n += d.n_gru ? 8 + 2 : 2;     // fc
+  return n;
+}
+
+}  // namespace
+
+struct pd_rmvpe {
+  pd_rmvpe_dims d;
+  WeightPool weights;
+  float* inbn = nullptr;                 // encoder.bn {scale, shift}
+  float *w_in = nullptr, *b_in = nullptr, *ws_in = nullptr, *bs_in = nullptr;   // first conv [c0][9], shortcut [c0]
+  std::vector<std::vector<Block>> enc, inter, dec;   // enc[0][0].c1 / its shortcut are the *_in tensors above
+  std::vector<ConvW> up;                 // the decoder's transposed convs
+  float *w_cnn = nullptr, *b_cnn = nullptr;
+  float *w_ih = nullptr, *b_ih = nullptr, *w_hh = nullptr, *b_hh = nullptr;   // both directions
+  float *w_fc = nullptr, *b_fc = nullptr;
+  int fc_in = 0;
+};
+
+namespace {
+
+// Workspace layout in floats, every buffer 64-float aligned
+struct WsPlan {
+  size_t skip[5];
+  size_t tmp[4];       // ping, pong, block-internal h1, shortcut
+  size_t feat, xp, gru, logits;
+  size_t total;
+};
+
+WsPlan plan_ws(const pd_rmvpe_dims& d, int B, int T) {
+  WsPlan p{};
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) / 64 * 64; return o; };
+  const size_t big = (size_t)B * T * d.n_mels * d.en_out_channels;   // the largest activation: level 0
+  for (int i = 0; i < d.en_de_layers; ++i) p.skip[i] = take(big >> i);
+  for (int i = 0; i < 4; ++i) p.tmp[i] = take(big);
+  const size_t rows = (size_t)B * T;
+  p.feat = take(rows * 3 * d.n_mels);
+  p.xp = take(d.n_gru ? rows * 6 * GRU_H : 0);
+  p.gru = take(d.n_gru ? rows * 2 * GRU_H : 0);
+  p.logits = take(rows * d.n_class);
+  p.total = off;
+  return p;
+}
+
+// profiling tags by image level (0 = T x F, 5 = T/32 x F/32): plain conv, conv with the 1x1 shortcut, transposed conv
+const char* const TAG_CONV[6] = {"rmvpe_conv_l0", "rmvpe_conv_l1", "rmvpe_conv_l2", "rmvpe_conv_l3", "rmvpe_conv_l4",
+                                 "rmvpe_conv_l5"};
+const char* const TAG_CONV_SC[6] = {"rmvpe_conv_sc_l0", "rmvpe_conv_sc_l1", "rmvpe_conv_sc_l2", "rmvpe_conv_sc_l3",
+                                    "rmvpe_conv_sc_l4", "rmvpe_conv_sc_l5"};
+const char* const TAG_CONVT[6] = {"rmvpe_convT_l0", "rmvpe_convT_l1", "rmvpe_convT_l2", "rmvpe_convT_l3",
+                                  "rmvpe_convT_l4", "rmvpe_convT_l5"};
+
+int launch_conv(const ConvW& cw, const float* src0, int c0, const float* src1, int c1, int B, int H, int W,
+                bool stuffed, const Block* sc, float* sc_out, const float* resid, float* out, hipStream_t st,
+                int lvl) {
+  ConvArgs a{};
+  a.src0 = src0; a.src1 = src1 ? src1 : src0; a.c0 = c0; a.c1 = src1 ? c1 : 0;
+  a.H = H; a.W = W; a.stuffed = stuffed ? 1 : 0;
+  a.wp = cw.w; a.bias = cw.b; a.relu = 1;
+  a.resid = resid; a.out = out; a.cout = cw.cout;
+  a.tc = W >= 16 ? 16 : (W >= 8 ? 8 : 4);   // a narrower image leaves tile columns unused
+  a.tr = CV_PIX / a.tc;
+  a.tiles_x = cdiv(W, a.tc);
+  if (a.c0 + a.c1 != cw.cin || a.c0 % CV_CK || a.c1 % CV_CK) {
+    set_error("rmvpe: conv shape the kernel does not take");
+    return PD_ERR_ARG;
+  }
+  const dim3 grid(a.tiles_x * cdiv(H, a.tr), ctiles(cw.cout), B);
+  ProfScope ps((stuffed ? TAG_CONVT : sc ? TAG_CONV_SC : TAG_CONV)[lvl], st);
+  if (sc) {
+    a.wsp = sc->ws; a.bsc = sc->bs; a.sc_out = sc_out;
+    hipLaunchKernelGGL(conv3x3_kernel<true>, grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(conv3x3_kernel<false>, grid, dim3(256), 0, st, a);
+  }
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// ConvBlockRes: x (c0 [+ c1 from x1] channels) -> out; h1 and scb are scratch, none of the four may alias
+int run_block(const Block& bk, const float* x, int c0, const float* x1, int c1, int B, int H, int W, float* h1,
+              float* scb, float* out, hipStream_t st, int lvl) {
+  if (bk.sc) {
+    PD_TRY(launch_conv(bk.c1, x, c0, x1, c1, B, H, W, false, &bk, scb, nullptr, h1, st, lvl));
+    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, out, st, lvl));
+  } else {
+    PD_TRY(launch_conv(bk.c1, x, c0, nullptr, 0, B, H, W, false, nullptr, nullptr, nullptr, h1, st, lvl));
+    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, x, out, st, lvl));
+  }
+  return PD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pd_rmvpe_num_params(const pd_rmvpe_dims* dims) {
+  if (!dims || !dims_ok(*dims)) return 0;
+  return count_params(*dims);
+}
+
+int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int dtype, void* stream, pd_rmvpe** out) {
+  PD_CHECK_ARG(dims && params && out, "null pointer");
+  if (dtype != PD_DTYPE_F32) { set_error("rmvpe: fp32 only"); return PD_ERR_UNSUPPORTED; }
+  if (!dims_ok(*dims)) { set_error("rmvpe: dimensions outside the supported set (include/prodiff_hip.h)"); return PD_ERR_UNSUPPORTED; }
+  const pd_rmvpe_dims d = *dims;
+  const int np = count_params(d);
+  PD_TRY(check_params(params, np));
+  hipStream_t st = (hipStream_t)stream;
+  pd_rmvpe* h = new pd_rmvpe();
+  h->d = d;
+  WeightPool& wp = h->weights;
+  const int L = d.en_de_layers, c0 = d.en_out_channels;
+
+  // plan: walk the parameter list once, reserving pool slots and remembering what to pack from where
+  struct ConvJob { ConvW* cw; int w, bn; bool transposed; };       // weight index, first BN index
+  struct ScJob { Block* bk; int w; };
+  std::vector<ConvJob> convs;
+  std::vector<ScJob> scs;
+  int p = 0;
+  const int p_inbn = p; p += 4;
+  wp.add(&h->inbn, 2);
+  int p_first = -1;
+  auto plan_convw = [&](ConvW& cw, int cin, int cout, bool transposed) {
+    cw.cin = cin; cw.cout = cout;
+    wp.add(&cw.w, packed_conv(cin, cout, 9));
+    wp.add(&cw.b, (size_t)ctiles(cout) * 32);
+    convs.push_back({&cw, p, p + 1, transposed});
+    p += 5;
+  };
+  auto plan_block = [&](Block& bk, int cin, int cout) {
+    bk.cin = cin; bk.cout = cout; bk.sc = cin != cout;
+    if (cin == 1) {           // the first conv and its shortcut keep the plain layout
+      p_first = p;
+      bk.c1.cin = 1; bk.c1.cout = cout;
+      wp.add(&h->w_in, (size_t)cout * 9);
+      wp.add(&h->b_in, cout);
+      p += 5;
+    } else {
+      plan_convw(bk.c1, cin, cout, false);
+    }
+    plan_convw(bk.c2, cout, cout, false);
+    if (bk.sc) {
+      if (cin == 1) {
+        wp.add(&h->ws_in, cout);
+        wp.add(&h->bs_in, cout);
+      } else {
+        wp.add(&bk.ws, packed_conv(cin, cout, 1));
+        wp.add(&bk.bs, (size_t)ctiles(cout) * 32);
+        scs.push_back({&bk, p});
+      }
+      p += 2;
+    }
+  };
+  auto plan_stage = [&](std::vector<Block>& v, int cin, int cout) {
+    v.resize(d.n_blocks);   // sized before any slot address is taken
+    for (int j = 0; j < d.n_blocks; ++j) plan_block(v[j], j == 0 ? cin : cout, cout);
+  };
+  h->enc.resize(L); h->inter.resize(d.inter_layers); h->dec.resize(L); h->up.resize(L);
+  for (int i = 0; i < L; ++i) plan_stage(h->enc[i], i == 0 ? 1 : c0 << (i - 1), c0 << i);
+  for (int i = 0; i < d.inter_layers; ++i) plan_stage(h->inter[i], i == 0 ? c0 << (L - 1) : c0 << L, c0 << L);
+  for (int i = 0; i < L; ++i) {
+    const int cout = c0 << (L - 1 - i);
+    plan_convw(h->up[i], 2 * cout, cout, true);
+    plan_stage(h->dec[i], 2 * cout, cout);
+  }
+  const int p_cnn = p; p += 2;
+  wp.add(&h->w_cnn, (size_t)3 * c0 * 9);
+  wp.add(&h->b_cnn, 3);
+  const int feat_c = 3 * d.n_mels;
+  const int p_fc0 = p;
+  if (d.n_gru) {
+    wp.add(&h->w_ih, (size_t)6 * GRU_H * feat_c);
+    wp.add(&h->b_ih, 6 * GRU_H);
+    wp.add(&h->w_hh, (size_t)6 * GRU_H * GRU_H);
+    wp.add(&h->b_hh, 6 * GRU_H);
+    p += 8;
+    h->fc_in = 2 * GRU_H;
+  } else {
+    h->fc_in = feat_c;
+  }
+  const int p_fc = p; p += 2;
+  wp.add(&h->w_fc, (size_t)d.n_class * h->fc_in);
+  wp.add(&h->b_fc, d.n_class);
+
+  auto run = [&]() -> int {
+    if (p != np) { set_error("rmvpe: parameter walk does not match pd_rmvpe_num_params"); return PD_ERR_ARG; }
+    PD_TRY(wp.commit(st, "rmvpe"));
+    hipLaunchKernelGGL(input_bn_kernel, dim3(1), dim3(64), 0, st, h->inbn, params[p_inbn], params[p_inbn + 1],
+                       params[p_inbn + 2], params[p_inbn + 3]);
+    PD_LAUNCH_CHECK();
+    {   // first conv: conv.0.weight [c0][1][3][3], conv.1 BN; shortcut after the block's second conv
+      const int q = p_first;
+      hipLaunchKernelGGL(fold_rows_kernel, dim3(cdiv(c0 * 9, 256)), dim3(256), 0, st, h->w_in, params[q],
+                         params[q + 1], params[q + 4], c0, 9);
+      PD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(fold_bias_kernel, dim3(cdiv(c0, 256)), dim3(256), 0, st, h->b_in, params[q + 1],
+                         params[q + 2], params[q + 3], params[q + 4], c0);
+      PD_LAUNCH_CHECK();
+      PD_TRY(copy_f32(h->ws_in, params[q + 10], c0, st));
+      PD_TRY(copy_f32(h->bs_in, params[q + 11], c0, st));
+    }
+    for (const ConvJob& j : convs) {
+      const ConvW& cw = *j.cw;
+      const long long total = (long long)packed_conv(cw.cin, cw.cout, 9);
+      const float* const* bn = params + j.bn;   // weight, bias, running_mean, running_var
+      hipLaunchKernelGGL(pack_conv2d_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, cw.w, params[j.w], bn[0],
+                         bn[3], cw.cout, cw.cin, 9, j.transposed ? 1 : 0, total);
+      PD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(fold_bias_kernel, dim3(cdiv(cw.cout, 256)), dim3(256), 0, st, cw.b, bn[0], bn[1], bn[2],
+                         bn[3], cw.cout);
+      PD_LAUNCH_CHECK();
+    }
+    for (const ScJob& j : scs) {
+      const Block& bk = *j.bk;
+      const long long total = (long long)packed_conv(bk.cin, bk.cout, 1);
+      hipLaunchKernelGGL(pack_conv2d_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, bk.ws, params[j.w],
+                         (const float*)nullptr, (const float*)nullptr, bk.cout, bk.cin, 1, 0, total);
+      PD_LAUNCH_CHECK();
+      PD_TRY(copy_f32(bk.bs, params[j.w + 1], bk.cout, st));
+    }
+    PD_TRY(copy_f32(h->w_cnn, params[p_cnn], (size_t)3 * c0 * 9, st));
+    PD_TRY(copy_f32(h->b_cnn, params[p_cnn + 1], 3, st));
+    if (d.n_gru) {
+      for (int dir = 0; dir < 2; ++dir) {
+        const float* const* g = params + p_fc0 + 4 * dir;   // weight_ih, weight_hh, bias_ih, bias_hh
+        PD_TRY(copy_f32(h->w_ih + (size_t)dir * 3 * GRU_H * feat_c, g[0], (size_t)3 * GRU_H * feat_c, st));
+        hipLaunchKernelGGL(pack_whh_kernel, dim3(cdiv(3 * GRU_H * GRU_H, 256)), dim3(256), 0, st,
+                           h->w_hh + (size_t)dir * 3 * GRU_H * GRU_H, g[1]);
+        PD_LAUNCH_CHECK();
+        PD_TRY(copy_f32(h->b_ih + dir * 3 * GRU_H, g[2], 3 * GRU_H, st));
+        PD_TRY(copy_f32(h->b_hh + dir * 3 * GRU_H, g[3], 3 * GRU_H, st));
+      }
+    }
+    PD_TRY(copy_f32(h->w_fc, params[p_fc], (size_t)d.n_class * h->fc_in, st));
+    PD_TRY(copy_f32(h->b_fc, params[p_fc + 1], d.n_class, st));
+    return PD_OK;
+  };
+  const int rc = run();
+  if (rc != PD_OK) { delete h; return rc; }
+  *out = h;
+  return PD_OK;
+}
+
+void pd_rmvpe_destroy(pd_rmvpe* h) { delete h; }
+
+size_t pd_rmvpe_workspace_size(const pd_rmvpe* h, int B, int T) {
+  if (!h || B <= 0 || T <= 0) return 0;
+  return plan_ws(h->d, B, T).total * sizeof(float);
+}
+
+int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* feat, int B, int T, void* workspace,
+                     size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(h && mel && hidden, "null pointer");
+  PD_CHECK_ARG(B > 0 && B <= 65535, "B must lie in [1, 65535]");
+  const pd_rmvpe_dims& d = h->d;
+  const int L = d.en_de_layers, c0 = d.en_out_channels, F = d.n_mels;
+  PD_CHECK_ARG(T > 0 && T % (1 << L) == 0, "T must be a positive multiple of 2^en_de_layers");
+  PD_CHECK_ARG((long long)B * T * F * c0 < (1ll << 31), "B * T too large for one call");
+  const WsPlan wsp = plan_ws(d, B, T);
+  if (!workspace || ws_bytes < wsp.total * sizeof(float) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+    set_error("rmvpe: workspace smaller than pd_rmvpe_workspace_size (or not 16-byte aligned)");
+    return PD_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  float* skip[5];
+  for (int i = 0; i < L; ++i) skip[i] = ws + wsp.skip[i];
+  float* ping = ws + wsp.tmp[0];
+  float* pong = ws + wsp.tmp[1];
+  float* h1 = ws + wsp.tmp[2];
+  float* scb = ws + wsp.tmp[3];
+  float* featb = feat ? feat : ws + wsp.feat;
+
+  // ---- encoder
+  const float* cur = nullptr;   // the level's input (after the pool), in ping or pong
+  for (int i = 0; i < L; ++i) {
+    const int H = T >> i, W = F >> i, cout = c0 << i;
+    const std::vector<Block>& lv = h->enc[i];
+    for (int j = 0; j < d.n_blocks; ++j) {
+      const bool last = j == d.n_blocks - 1;
+      float* dst = last ? skip[i] : (cur == ping ? pong : ping);
+      if (i == 0 && j == 0) {
+        const long long total = (long long)B * H * W * cout;
+        {
+          ProfScope ps("rmvpe_conv_in", st);
+          hipLaunchKernelGGL(conv_in_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, mel, h->inbn, h->w_in, h->b_in,
+                             h->ws_in, h->bs_in, h1, scb, H, W, cout, total);
+          PD_LAUNCH_CHECK();
+        }
+        PD_TRY(launch_conv(lv[0].c2, h1, cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, dst, st, i));
+      } else {
+        PD_TRY(run_block(lv[j], cur, lv[j].cin, nullptr, 0, B, H, W, h1, scb, dst, st, i));
+      }
+      cur = dst;
+    }
+    float* pooled = (cur == ping) ? pong : ping;   // cur is skip[i] here unless n_blocks chains left it in ping/pong
+    const long long total = (long long)B * (H >> 1) * (W >> 1) * (cout >> 2);
+    {
+      ProfScope ps("rmvpe_pool", st);
+      hipLaunchKernelGGL(avgpool_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, cur, pooled, H, W, cout, total);
+      PD_LAUNCH_CHECK();
+    }
+    cur = pooled;
+  }
+  // ---- intermediate
+  {
+    const int H = T >> L, W = F >> L;
+    for (int i = 0; i < d.inter_layers; ++i)
+      for (int j = 0; j < d.n_blocks; ++j) {
+        const Block& bk = h->inter[i][j];
+        float* dst = cur == ping ? pong : ping;
+        PD_TRY(run_block(bk, cur, bk.cin, nullptr, 0, B, H, W, h1, scb, dst, st, L));
+        cur = dst;
+      }
+  }
+  // ---- decoder
+  for (int i = 0; i < L; ++i) {
+    const int lvl = L - 1 - i, H = T >> lvl, W = F >> lvl, cout = c0 << lvl;
+    float* upb = cur == ping ? pong : ping;
+    PD_TRY(launch_conv(h->up[i], cur, 2 * cout, nullptr, 0, B, H, W, true, nullptr, nullptr, nullptr, upb, st,
+                       lvl));
+    cur = upb;
+    for (int j = 0; j < d.n_blocks; ++j) {
+      const Block& bk = h->dec[i][j];
+      float* dst = cur == ping ? pong : ping;
+      if (j == 0) PD_TRY(run_block(bk, cur, cout, skip[lvl], cout, B, H, W, h1, scb, dst, st, lvl));
+      else PD_TRY(run_block(bk, cur, cout, nullptr, 0, B, H, W, h1, scb, dst, st, lvl));
+      cur = dst;
+    }
+  }
+  // ---- cnn -> feat [B][T][3 F]
+  {
+    const long long total = (long long)B * T * F;
+    ProfScope ps("rmvpe_conv_out", st);
+    hipLaunchKernelGGL(conv_out_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, cur, h->w_cnn, h->b_cnn, featb, T, F,
+                       c0, total);
+    PD_LAUNCH_CHECK();
+  }
+  // ---- fc
+  const int feat_c = 3 * F;
+  const float* fc_src = featb;
+  if (d.n_gru) {
+    float* xp = ws + wsp.xp;
+    float* go = ws + wsp.gru;
+    GemmArgs g = make_gemm(B, T, 6 * GRU_H, h->w_ih, feat_c, h->b_ih, xp, (long long)T * 6 * GRU_H, 6 * GRU_H);
+    add_seg(g, make_seg(featb, (long long)T * feat_c, feat_c, feat_c, 0));
+    PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_RMVPE_XPROJ>(g, st, "rmvpe_gru_xproj")));
+    GruArgs ga{xp, h->w_hh, h->b_hh, go, B, T};
+    {
+      ProfScope ps("rmvpe_gru", st);
+      hipLaunchKernelGGL(gru_kernel, dim3(2, cdiv(B, GRU_ROWS)), dim3(512), 0, st, ga);
+      PD_LAUNCH_CHECK();
+    }
+    fc_src = go;
+  }
+  float* logits = ws + wsp.logits;
+  GemmArgs g = make_gemm(B, T, d.n_class, h->w_fc, h->fc_in, h->b_fc, logits, (long long)T * d.n_class, d.n_class);
+  add_seg(g, make_seg(fc_src, (long long)T * h->fc_in, h->fc_in, h->fc_in, 0));
+  PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_RMVPE_HEAD>(g, st, "rmvpe_head")));
+  {
+    const long long n = (long long)B * T * d.n_class;
+    ProfScope ps("rmvpe_sigmoid", st);
+    hipLaunchKernelGGL(sigmoid_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, logits, hidden, n);
+    PD_LAUNCH_CHECK();
+  }
+  return PD_OK;
+}
+
+int pd_rmvpe_decode(const float* hidden, float* f0, int B, int T, int n_class, float thred, const long long* center,
+                    double cents_const, void* stream) {
+  PD_CHECK_ARG(hidden && f0, "null pointer");
+  PD_CHECK_ARG(B > 0 && T > 0 && n_class > 0, "B, T and n_class must be positive");
+  const long long frames = (long long)B * T;
+  ProfScope ps("rmvpe_decode", (hipStream_t)stream);
+  hipLaunchKernelGGL(decode_kernel, dim3(cdiv(frames, 4)), dim3(256), 0, (hipStream_t)stream, hidden, center, f0,
+                     frames, n_class, thred, cents_const);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+}  // extern "C"

@@ -30,13 +30,25 @@ def mel_to_hz(m):
     return np.where(m >= _MIN_LOG_MEL, _MIN_LOG_HZ * np.exp(_LOGSTEP * (m - _MIN_LOG_MEL)), _F_SP * m)
 
 
-def mel_filterbank64(sr, n_fft, n_mels, fmin=0.0, fmax=None):
+def hz_to_mel_htk(f):
+    """The HTK scale (librosa's htk=True): mel = 2595 log10(1 + f / 700)."""
+    return 2595.0 * np.log10(1.0 + np.asarray(f, np.float64) / 700.0)
+
+
+def mel_to_hz_htk(m):
+    return 700.0 * (10.0 ** (np.asarray(m, np.float64) / 2595.0) - 1.0)
+
+
+def mel_filterbank64(sr, n_fft, n_mels, fmin=0.0, fmax=None, htk=False):
     """float64 [n_mels, n_fft // 2 + 1]: triangles between n_mels + 2 points equally spaced on the Slaney
-    scale from fmin to fmax (sr / 2 when None), each scaled by 2 / (its base in Hz) -- Slaney's area
-    normalisation: every triangle has unit area over frequency."""
+    scale (the HTK scale with ``htk``) from fmin to fmax (sr / 2 when None), each scaled by 2 / (its base in
+    Hz) -- Slaney's area normalisation: every triangle has unit area over frequency."""
     fmax = sr / 2.0 if fmax is None else float(fmax)
     freqs = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
-    pts = mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2))
+    if htk:
+        pts = mel_to_hz_htk(np.linspace(hz_to_mel_htk(fmin), hz_to_mel_htk(fmax), n_mels + 2))
+    else:
+        pts = mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2))
     width = np.diff(pts)
     ramps = pts[:, None] - freqs[None, :]
     lower = -ramps[:-2] / width[:-1, None]
@@ -45,10 +57,10 @@ def mel_filterbank64(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     return w * (2.0 / (pts[2:] - pts[:-2]))[:, None]
 
 
-def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None):
-    """``librosa.filters.mel(sr=, n_fft=, n_mels=, fmin=, fmax=)`` with its defaults (Slaney scale, Slaney
-    norm): computed in float64, returned as float32 [n_mels, n_fft // 2 + 1]."""
-    return mel_filterbank64(sr, n_fft, n_mels, fmin, fmax).astype(np.float32)
+def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None, htk=False):
+    """``librosa.filters.mel(sr=, n_fft=, n_mels=, fmin=, fmax=, htk=)`` with its other defaults (Slaney
+    norm; Slaney scale unless ``htk``): computed in float64, returned as float32 [n_mels, n_fft // 2 + 1]."""
+    return mel_filterbank64(sr, n_fft, n_mels, fmin, fmax, htk).astype(np.float32)
 
 
 # ---------------------------------------------------------------- native handle

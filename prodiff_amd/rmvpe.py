@@ -1,0 +1,289 @@
+"""RMVPE pitch extraction on the GPU: the reference's modules/rmvpe (``E2E0``, ``MelSpectrogram``,
+``to_local_average_f0``) and component/pe/rmvpe.py (``RMVPE``) on pd_rmvpe, the centred pd_mel and pd_resample
+(include/prodiff_hip.h, "pitch extraction").  No librosa, no torchaudio.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib, synth
+from .mel import _MelHandle, derived_sizes, mel_filterbank
+from .resample import Resample
+
+SAMPLE_RATE, N_CLASS, N_MELS = 16000, synth.RMVPE_N_CLASS, synth.RMVPE_N_MELS      # modules/rmvpe/constants.py
+MEL_FMIN, MEL_FMAX, WINDOW_LENGTH = 30, 8000, 1024
+CONST = 1997.3794084376191
+
+PITCH_EXTRACTORS = {}
+
+
+def register_pe(cls):
+    """component/pe/base.py: the registry ``get_pitch_extractor_cls`` reads."""
+    PITCH_EXTRACTORS[cls.__name__.lower()] = cls
+    PITCH_EXTRACTORS[cls.__name__] = cls
+    return cls
+
+
+def get_pitch_extractor_cls(name):
+    if name.lower() not in PITCH_EXTRACTORS:
+        raise ValueError(f"Pitch extractor {name.lower()} not found in PITCH_EXTRACTORS")
+    return PITCH_EXTRACTORS[name.lower()]
+
+
+# ---------------------------------------------------------------- network
+def _attach(root, key, tensor, buffer):
+    """Register ``tensor`` under the dotted state-dict key, creating the modules on the way."""
+    *path, leaf = key.split(".")
+    mod = root
+    for name in path:
+        if name not in mod._modules:
+            mod.add_module(name, nn.Module())
+        mod = mod._modules[name]
+    if buffer:
+        mod.register_buffer(leaf, tensor)
+    else:
+        mod.register_parameter(leaf, nn.Parameter(tensor, requires_grad=False))
+
+
+class E2E0(nn.Module):
+    """modules/rmvpe/model.py:8-32 (inference only).  The module tree carries the reference's parameter and
+    buffer names, so a checkpoint's ``model`` dict loads unchanged; ``unet.tf.*`` (the TimbreFilter, built but
+    never called) and every ``num_batches_tracked`` are accepted and ignored.  ``forward`` runs pd_rmvpe_forward."""
+
+    def __init__(self, n_blocks, n_gru, kernel_size, en_de_layers=5, inter_layers=4, in_channels=1, en_out_channels=16):
+        super().__init__()
+        if tuple(kernel_size) != (2, 2) or in_channels != 1:
+            raise _lib.HipError("E2E0: only kernel_size (2, 2) and in_channels 1 are supported")
+        self.config = dict(n_blocks=int(n_blocks), n_gru=int(n_gru), en_de_layers=int(en_de_layers),
+                           inter_layers=int(inter_layers), en_out_channels=int(en_out_channels))
+        self.param_keys = []
+        for key, shape in synth.rmvpe_param_shapes(**self.config).items():
+            stat = key.endswith(("running_mean", "running_var"))
+            unit = synth._rmvpe_is_bn(key) and key.endswith(("weight", "running_var"))   # BatchNorm's own defaults
+            init = torch.ones(shape) if unit else torch.zeros(shape)
+            _attach(self, key, init, stat)
+            self.param_keys.append(key)
+        self._native = _lib.NativeHandle("E2E0", "pd_rmvpe_create", "pd_rmvpe_destroy", num_params="pd_rmvpe_num_params")
+        self._ws = _lib.Workspace()
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        kept = {k: v for k, v in state_dict.items() if not synth.rmvpe_key_is_skipped(k)}
+        return super().load_state_dict(kept, strict=strict, **kw)
+
+    def dims(self):
+        c = self.config
+        return _lib.pd_rmvpe_dims(c["n_blocks"], c["n_gru"], c["en_de_layers"], c["inter_layers"], c["en_out_channels"],
+                                  N_MELS, N_CLASS, synth.RMVPE_GRU_HIDDEN)
+
+    def ordered_params(self):
+        sd = dict(self.named_parameters())
+        sd.update(dict(self.named_buffers()))
+        return [sd[k] for k in self.param_keys]
+
+    def handle(self):
+        ps = self.ordered_params()
+        return self._native.get(self._native.signature(ps),
+                                lambda: (self.dims(), [p.detach().float().contiguous() for p in ps]))
+
+    def close(self):
+        self._native.close()
+
+    @torch.no_grad()
+    def forward_time_major(self, mel_tm, return_feat=False):
+        """mel_tm [B, T, 128] time-major (what the native mel writes) -> hidden [B, T, 360] (and feat [B, T, 384])."""
+        mel_tm = mel_tm.float().contiguous()
+        B, T, F = mel_tm.shape
+        if F != N_MELS:
+            raise ValueError(f"expected {N_MELS} mel bins, got {F}")
+        h = self.handle()
+        dev = mel_tm.device
+        hidden = torch.empty(B, T, N_CLASS, device=dev, dtype=torch.float32)
+        feat = torch.empty(B, T, 3 * N_MELS, device=dev, dtype=torch.float32) if return_feat else None
+        L = _lib.lib()
+        ws, wsb = self._ws.get(L.pd_rmvpe_workspace_size(h, B, T), dev)
+        _lib.check(L.pd_rmvpe_forward(h, _lib.fptr(mel_tm), _lib.fptr(hidden), _lib.fptr(feat), B, T, ws, wsb,
+                                      _lib.stream_ptr(dev)))
+        return (hidden, feat) if return_feat else hidden
+
+    def forward(self, mel):
+        """mel [B, 128, T] -> salience [B, T, 360]; T must be a multiple of 2^en_de_layers."""
+        return self.forward_time_major(mel.transpose(1, 2))
+
+    def forward_features(self, mel):
+        """-> (hidden [B, T, 360], feat [B, T, 384]): ``feat`` is the ``cnn`` output as model.py:30 flattens it."""
+        return self.forward_time_major(mel.transpose(1, 2), return_feat=True)
+
+
+# ---------------------------------------------------------------- decode
+@torch.no_grad()
+def to_local_average_f0(hidden, center=None, thred=0.03):
+    """modules/rmvpe/utils.py:8-23 on the GPU: hidden [B, T, n_class] -> f0 [B, T] (a device tensor; the
+    reference's ``.squeeze(0).cpu().numpy()`` is left to the caller)."""
+    hidden = hidden.float().contiguous()
+    B, T, n = hidden.shape
+    f0 = torch.empty(B, T, device=hidden.device, dtype=torch.float32)
+    cen = None
+    if center is not None:
+        cen = center.to(hidden.device).long().reshape(B, T).contiguous()
+    _lib.check(_lib.lib().pd_rmvpe_decode(_lib.fptr(hidden), _lib.fptr(f0), B, T, n, float(thred), _lib.lptr(cen),
+                                          CONST, _lib.stream_ptr(hidden.device)))
+    return f0
+
+
+# ---------------------------------------------------------------- front end
+class MelSpectrogram:
+    """modules/rmvpe/spec.py: the HTK-scale log-mel of ``torch.stft(center=True)`` on the centred pd_mel.
+    ``forward`` returns the reference's [B, n_mels, T] (a transposed view of the time-major native output,
+    which ``forward_time_major`` returns as it is); T = 1 + L // hop."""
+
+    def __init__(self, n_mel_channels, sampling_rate, win_length, hop_length, n_fft=None, mel_fmin=0, mel_fmax=None,
+                 clamp=1e-5):
+        self.n_fft = win_length if n_fft is None else n_fft
+        self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
+        self.win_length, self.hop_length, self.clamp = win_length, hop_length, clamp
+        self.mel_basis_host = torch.from_numpy(mel_filterbank(sampling_rate, self.n_fft, n_mel_channels, mel_fmin, mel_fmax,
+                                                              htk=True))
+        self.mel_basis = {}
+        self.handles = {}
+
+    def to(self, device):
+        return self
+
+    def handle(self, keyshift, speed, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.HipError("MelSpectrogram runs on the GPU (got a CPU tensor; there is no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (float(keyshift), float(speed), str(device))
+        nh = self.handles.get(key)
+        if nh is None:
+            if len(self.handles) >= 8:
+                self.handles.pop(next(iter(self.handles))).close()
+            nh = self.handles[key] = _MelHandle("MelSpectrogram", "pd_mel_create_centered", "pd_mel_destroy")
+        basis = self.mel_basis.get(str(device))
+        if basis is None:
+            basis = self.mel_basis[str(device)] = self.mel_basis_host.to(device)
+        dims = _lib.pd_mel_dims(self.n_fft, self.win_length, self.hop_length, self.n_mel_channels, float(keyshift),
+                                float(speed), float(self.clamp))
+        return nh.get(key, lambda: (dims, [basis]))
+
+    def close(self):
+        for nh in self.handles.values():
+            nh.close()
+        self.handles.clear()
+
+    @torch.no_grad()
+    def forward_time_major(self, audio, keyshift=0, speed=1, center=True, return_spec=False):
+        if not center:
+            raise NotImplementedError("center=False is prodiff_amd.mel.STFT's framing")
+        if audio.dim() == 1:
+            audio = audio[None]
+        y = audio.float().contiguous()
+        B, L = y.shape
+        nf = derived_sizes(self.n_fft, self.win_length, self.hop_length, keyshift, speed)[0]
+        if L < nf // 2 + 1:
+            raise ValueError(f"signal of {L} samples is too short: reflect padding needs at least {nf // 2 + 1}")
+        h = self.handle(keyshift, speed, y.device)
+        lib = _lib.lib()
+        T = lib.pd_mel_frames(h, L)
+        out = torch.empty(B, T, self.n_mel_channels, device=y.device, dtype=torch.float32)
+        spec = torch.empty(B, T, self.n_fft // 2 + 1, device=y.device, dtype=torch.float32) if return_spec else None
+        _lib.check(lib.pd_mel_forward(h, _lib.fptr(y), None, 1.0, _lib.fptr(out), _lib.fptr(spec), B, L, None, 0,
+                                      _lib.stream_ptr(y.device)))
+        return (out, spec) if return_spec else out
+
+    def forward(self, audio, keyshift=0, speed=1, center=True):
+        return self.forward_time_major(audio, keyshift, speed, center).transpose(1, 2)
+
+    __call__ = forward
+
+
+# ---------------------------------------------------------------- curves (utils/pitch_utils.py)
+def interp_f0(f0, uv=None):
+    """utils/pitch_utils.py:45-51: unvoiced frames filled by linear interpolation of log2 f0 -> (f0, uv)."""
+    f0 = np.asarray(f0)
+    if uv is None:
+        uv = f0 == 0
+    with np.errstate(divide="ignore"):
+        lf = np.log2(f0 + uv)
+    lf[uv] = -np.inf
+    if uv.any() and not uv.all():
+        lf[uv] = np.interp(np.where(uv)[0], np.where(~uv)[0], lf[~uv])
+    return 2 ** lf, uv
+
+
+def resample_align_curve(points, original_timestep, target_timestep, align_length):
+    """utils/pitch_utils.py:86-98: the curve at another frame period, cut or padded (last value) to align_length."""
+    points = np.asarray(points)
+    t_max = (len(points) - 1) * original_timestep
+    curve = np.interp(np.arange(0, t_max, target_timestep), original_timestep * np.arange(len(points)),
+                      points).astype(points.dtype)
+    delta_l = align_length - len(curve)
+    if delta_l < 0:
+        curve = curve[:align_length]
+    elif delta_l > 0:
+        curve = np.concatenate((curve, np.full(delta_l, fill_value=curve[-1], dtype=curve.dtype)), axis=0)
+    return curve
+
+
+# ---------------------------------------------------------------- extractor
+@register_pe
+class RMVPE:
+    """component/pe/rmvpe.py:13-72.  ``model_path=None`` with no ``pe_ckpt`` in hparams builds the model without
+    weights (load them with ``self.model.load_state_dict``)."""
+
+    def __init__(self, hparams, model_path=None, hop_length=160):
+        self.hparams = hparams
+        self.resample_kernel = {}
+        self.device = "cuda"
+        self.model = E2E0(4, 1, (2, 2)).eval().to(self.device)
+        if model_path is None:
+            model_path = (hparams or {}).get("pe_ckpt")
+        if model_path is not None:
+            ckpt = torch.load(model_path, map_location=self.device)
+            self.model.load_state_dict(ckpt["model"], strict=False)
+        self.mel_extractor = MelSpectrogram(N_MELS, SAMPLE_RATE, WINDOW_LENGTH, hop_length, None, MEL_FMIN, MEL_FMAX)
+
+    @torch.no_grad()
+    def mel2hidden(self, mel):
+        """mel [B, 128, T] -> hidden [B, T, 360]: zero-padded (value 0.0, real network input) to a multiple of 32."""
+        return self._hidden_time_major(mel.transpose(1, 2))
+
+    def _hidden_time_major(self, mel_tm):
+        n_frames = mel_tm.shape[1]
+        pad = 32 * ((n_frames - 1) // 32 + 1) - n_frames
+        if pad:
+            mel_tm = torch.nn.functional.pad(mel_tm, (0, 0, 0, pad))
+        return self.model.forward_time_major(mel_tm)[:, :n_frames]
+
+    def decode(self, hidden, thred=0.03, use_viterbi=False):
+        if use_viterbi:
+            raise NotImplementedError("Viterbi decoding is librosa on the CPU in the reference and is not offered")
+        return to_local_average_f0(hidden, thred=thred).squeeze(0).cpu().numpy()
+
+    def infer_from_audio(self, audio, sample_rate=16000, thred=0.03, use_viterbi=False):
+        audio = torch.from_numpy(np.asarray(audio)).float().unsqueeze(0).to(self.device)
+        if sample_rate != SAMPLE_RATE:
+            key = str(sample_rate)
+            if key not in self.resample_kernel:
+                self.resample_kernel[key] = Resample(sample_rate, SAMPLE_RATE, lowpass_filter_width=128)
+            audio = self.resample_kernel[key](audio)
+        mel_tm = self.mel_extractor.forward_time_major(audio, center=True)
+        return self.decode(self._hidden_time_major(mel_tm), thred=thred, use_viterbi=use_viterbi)
+
+    def get_pitch(self, waveform, samplerate, length, *, hop_size, f0_min=65, f0_max=1100, speed=1, interp_uv=False):
+        f0 = self.infer_from_audio(waveform, sample_rate=samplerate)
+        uv = f0 == 0
+        f0, uv = interp_f0(f0, uv)
+        hop_size = int(np.round(hop_size * speed))
+        time_step = hop_size / samplerate
+        f0_res = resample_align_curve(f0, 0.01, time_step, length)
+        uv_res = resample_align_curve(uv.astype(np.float32), 0.01, time_step, length) > 0.5
+        if not interp_uv:
+            f0_res[uv_res] = 0
+        return f0_res, uv_res

@@ -476,3 +476,102 @@ def synth_dur_inputs(seed, lengths, vocab_size, pad_tokens=0):
         word = np.cumsum(on) - 1
         wd[b, :n] = rng.uniform(0.1, 1.2, int(word.max()) + 1).astype(np.float32)[word]
     return dict(txt_tokens=tok, onset=onset, word_dur=wd)
+
+
+# --------------------------------------------------------------------------
+# RMVPE pitch extractor (modules/rmvpe/model.py E2E0): state-dict order without the
+# num_batches_tracked counters and without unet.tf.* (built, never called)
+# --------------------------------------------------------------------------
+RMVPE_DEFAULTS = dict(n_blocks=4, n_gru=1, en_de_layers=5, inter_layers=4, en_out_channels=16)
+RMVPE_N_MELS, RMVPE_N_CLASS, RMVPE_GRU_HIDDEN = 128, 360, 256
+RMVPE_FC_GAIN = 2.0        # the final Linear: spreads the salience over (0.01, 0.97) without saturating it
+# the convs: about a hundred residual blocks add their ReLU outputs up with no normalisation of the sum; at
+# gain 1 the full model's features reach 3e3 and its salience saturates (torch's own default init is 1/sqrt(3))
+RMVPE_CONV_GAIN = 0.5
+RMVPE_SKIPPED = ("unet.tf.", "num_batches_tracked")
+
+
+def rmvpe_key_is_skipped(key):
+    return key.startswith(RMVPE_SKIPPED[0]) or key.endswith(RMVPE_SKIPPED[1])
+
+
+def _rmvpe_bn(s, p, C):
+    for leaf in ("weight", "bias", "running_mean", "running_var"):
+        s[f"{p}.{leaf}"] = (C,)
+
+
+def _rmvpe_block(s, p, cin, cout):
+    s[p + ".conv.0.weight"] = (cout, cin, 3, 3)
+    _rmvpe_bn(s, p + ".conv.1", cout)
+    s[p + ".conv.3.weight"] = (cout, cout, 3, 3)
+    _rmvpe_bn(s, p + ".conv.4", cout)
+    if cin != cout:
+        s[p + ".shortcut.weight"] = (cout, cin, 1, 1)
+        s[p + ".shortcut.bias"] = (cout,)
+
+
+def rmvpe_param_shapes(n_blocks=4, n_gru=1, en_de_layers=5, inter_layers=4, en_out_channels=16,
+                       n_mels=RMVPE_N_MELS, n_class=RMVPE_N_CLASS, gru_hidden=RMVPE_GRU_HIDDEN):
+    """Ordered ``{key: shape}`` of the parameters pd_rmvpe_create takes (include/prodiff_hip.h)."""
+    L, c0, s = en_de_layers, en_out_channels, OrderedDict()
+    _rmvpe_bn(s, "unet.encoder.bn", 1)
+    for i in range(L):
+        cin, cout = (1 if i == 0 else c0 << (i - 1)), c0 << i
+        for j in range(n_blocks):
+            _rmvpe_block(s, f"unet.encoder.layers.{i}.conv.{j}", cin if j == 0 else cout, cout)
+    for i in range(inter_layers):
+        cin, cout = (c0 << (L - 1) if i == 0 else c0 << L), c0 << L
+        for j in range(n_blocks):
+            _rmvpe_block(s, f"unet.intermediate.layers.{i}.conv.{j}", cin if j == 0 else cout, cout)
+    for i in range(L):
+        cout = c0 << (L - 1 - i)
+        s[f"unet.decoder.layers.{i}.conv1.0.weight"] = (2 * cout, cout, 3, 3)
+        _rmvpe_bn(s, f"unet.decoder.layers.{i}.conv1.1", cout)
+        for j in range(n_blocks):
+            _rmvpe_block(s, f"unet.decoder.layers.{i}.conv2.{j}", 2 * cout if j == 0 else cout, cout)
+    s["cnn.weight"] = (3, c0, 3, 3)
+    s["cnn.bias"] = (3,)
+    if n_gru:
+        for suffix in ("", "_reverse"):
+            s["fc.0.gru.weight_ih_l0" + suffix] = (3 * gru_hidden, 3 * n_mels)
+            s["fc.0.gru.weight_hh_l0" + suffix] = (3 * gru_hidden, gru_hidden)
+            s["fc.0.gru.bias_ih_l0" + suffix] = (3 * gru_hidden,)
+            s["fc.0.gru.bias_hh_l0" + suffix] = (3 * gru_hidden,)
+        s["fc.1.weight"] = (n_class, 2 * gru_hidden)
+        s["fc.1.bias"] = (n_class,)
+    else:
+        s["fc.0.weight"] = (n_class, 3 * n_mels)
+        s["fc.0.bias"] = (n_class,)
+    return s
+
+
+def synth_rmvpe_tensor(name, shape, seed, fc_gain=RMVPE_FC_GAIN):
+    """The RMVPE draw rules: conv / GRU / Linear weights by fan-in (ConvTranspose2d [Cin, Cout, 3, 3]: at most
+    four taps of each input channel reach an output), BatchNorm gamma and running_var uniform in [0.75, 1.25],
+    BatchNorm beta and running_mean 0.1 N(0, 1), other biases 0.02 N(0, 1), the final Linear times ``fc_gain``."""
+    rng = _rng(seed, name)
+    leaf = name.rsplit(".", 1)[-1]
+    is_bn = _rmvpe_is_bn(name)
+    if is_bn and leaf in ("weight", "running_var"):
+        return (0.75 + 0.5 * rng.random(size=shape, dtype=np.float32)).astype(np.float32)
+    z = rng.standard_normal(size=shape, dtype=np.float32)
+    if is_bn:
+        return (0.1 * z).astype(np.float32)
+    if len(shape) == 1:
+        return (0.02 * z).astype(np.float32)
+    if ".conv1.0." in name:
+        fan_in = shape[0] * 4
+    else:
+        fan_in = int(np.prod(shape[1:]))
+    gain = fc_gain if name in ("fc.1.weight", "fc.0.weight") else (RMVPE_CONV_GAIN if len(shape) == 4 else 1.0)
+    return (z * (gain / np.sqrt(fan_in))).astype(np.float32)
+
+
+def _rmvpe_is_bn(name):
+    """The BatchNorms are the children 1 and 4 of a block's conv stack, child 1 of a decoder level's conv1
+    and the encoder's input norm."""
+    return name.rsplit(".", 1)[0].endswith((".conv.1", ".conv.4", ".conv1.1", "encoder.bn"))
+
+
+def synth_rmvpe_params(shapes, seed, fc_gain=RMVPE_FC_GAIN):
+    return OrderedDict((k, synth_rmvpe_tensor(k, v, seed, fc_gain)) for k, v in shapes.items())

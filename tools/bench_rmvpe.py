@@ -1,0 +1,176 @@
+#!/usr/bin/env python
+"""Time the native RMVPE network (prodiff_amd.E2E0, pd_rmvpe_forward) with HIP events: 8 utterances x 10 s at
+16 kHz (1001 frames, zero-padded to 1024 as RMVPE.mel2hidden does), E2E0(4, 1, (2, 2)) with synthetic weights.
+Warm-up, then the median over --calls single calls; the same call replayed from one captured graph; a per-kernel
+table from pd_profile_*; the front end (centred mel) and the decode beside it; and the same network written
+with torch ops (F.conv2d, F.batch_norm, F.conv_transpose2d, nn.GRU) in eager mode on the same GPU.  Prints one
+JSON line.
+
+    python tools/bench_rmvpe.py [--calls 100] [--warmup 5] [--batch 8] [--seconds 10] [--no-torch]
+
+The conv floor: 2 x pixels x 9 C_in C_out FLOP per conv on the f32 MFMA (157.3 TFLOP/s dense).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import prodiff_amd  # noqa: E402
+from prodiff_amd import _lib, synth  # noqa: E402
+from prodiff_amd import rmvpe as RM  # noqa: E402
+
+F32_MFMA_PEAK = 157.3e12
+FULL = dict(synth.RMVPE_DEFAULTS)
+
+
+def time_calls(fn, calls, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(calls):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms = np.sort(np.array(ms))
+    return float(np.median(ms)), float(ms[0]), float(ms[int(0.9 * (len(ms) - 1))])
+
+
+def conv_flop(shapes, model, B, T, n_mels=128):
+    """FLOP of every conv (3x3, 1x1 shortcut, transposed) for a [B, T, n_mels] input."""
+    L = model["en_de_layers"]
+    total = 0
+    for k, s in shapes.items():
+        if len(s) != 4:
+            continue
+        part = k.split(".")
+        if part[1] == "encoder":
+            lvl = int(part[3])
+        elif part[1] == "intermediate":
+            lvl = L
+        elif part[1] == "decoder":
+            lvl = L - 1 - int(part[3])
+        else:
+            lvl = 0                                   # cnn
+        pix = B * (T >> lvl) * (n_mels >> lvl)
+        if ".conv1.0." in k:                          # transposed: each output pixel sees 9/4 taps on average
+            total += 2 * pix * s[0] * s[1] * 9 // 4
+        else:
+            total += 2 * pix * s[0] * s[1] * s[2] * s[3]
+    return total
+
+
+# ---------------------------------------------------------------- the same network with torch ops
+def torch_e2e0(P, model, mel, gru):
+    def bn(p, x):
+        return F.batch_norm(x, P[p + ".running_mean"], P[p + ".running_var"], P[p + ".weight"], P[p + ".bias"], False, 0.0, 1e-5)
+
+    def block(p, x):
+        h = F.relu(bn(p + ".conv.1", F.conv2d(x, P[p + ".conv.0.weight"], padding=1)))
+        h = F.relu(bn(p + ".conv.4", F.conv2d(h, P[p + ".conv.3.weight"], padding=1)))
+        if p + ".shortcut.weight" in P:
+            return h + F.conv2d(x, P[p + ".shortcut.weight"], P[p + ".shortcut.bias"])
+        return h + x
+
+    L, nb = model["en_de_layers"], model["n_blocks"]
+    x = bn("unet.encoder.bn", mel.transpose(-1, -2).unsqueeze(1))
+    skips = []
+    for i in range(L):
+        for j in range(nb):
+            x = block(f"unet.encoder.layers.{i}.conv.{j}", x)
+        skips.append(x)
+        x = F.avg_pool2d(x, 2)
+    for i in range(model["inter_layers"]):
+        for j in range(nb):
+            x = block(f"unet.intermediate.layers.{i}.conv.{j}", x)
+    for i in range(L):
+        p = f"unet.decoder.layers.{i}"
+        x = F.relu(bn(p + ".conv1.1", F.conv_transpose2d(x, P[p + ".conv1.0.weight"], stride=2, padding=1, output_padding=1)))
+        x = torch.cat((x, skips[-1 - i]), dim=1)
+        for j in range(nb):
+            x = block(f"{p}.conv2.{j}", x)
+    x = F.conv2d(x, P["cnn.weight"], P["cnn.bias"], padding=1).transpose(1, 2).flatten(-2)
+    return torch.sigmoid(F.linear(gru(x)[0], P["fc.1.weight"], P["fc.1.bias"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--seed", type=int, default=44)
+    ap.add_argument("--no-torch", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B, Lw = a.batch, int(round(a.seconds * 16000))
+    shapes = synth.rmvpe_param_shapes(**FULL)
+    host = synth.synth_rmvpe_params(shapes, a.seed)
+    net = prodiff_amd.E2E0(FULL["n_blocks"], FULL["n_gru"], (2, 2))
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in host.items()})
+    net.to(dev)
+    g = torch.Generator().manual_seed(0)
+    wav = ((torch.rand(B, Lw, generator=g) * 2 - 1) * 0.3).to(dev)
+    ms_ = RM.MelSpectrogram(128, 16000, 1024, 160, None, 30, 8000)
+    mel = ms_.forward_time_major(wav)
+    frames = mel.shape[1]
+    mel = F.pad(mel, (0, 0, 0, -frames % 32)).contiguous()
+    T = mel.shape[1]
+    hidden = net.forward_time_major(mel)
+    line = {"bench": "rmvpe", "B": B, "samples": Lw, "frames": frames, "T": T, "calls": a.calls,
+            "device": torch.cuda.get_device_name(0), "lib": _lib.lib().pd_build_config().decode()}
+    med, best, p90 = time_calls(lambda: net.forward_time_major(mel), a.calls, a.warmup)
+    line.update(native_ms_median=round(med, 3), native_ms_min=round(best, 3), native_ms_p90=round(p90, 3))
+    line["mel_ms_median"] = round(time_calls(lambda: ms_.forward_time_major(wav), a.calls, a.warmup)[0], 4)
+    line["decode_ms_median"] = round(time_calls(lambda: RM.to_local_average_f0(hidden), a.calls, a.warmup)[0], 4)
+    # the same call from one captured graph
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = net.forward_time_major(mel)
+    gm, gb, _ = time_calls(graph.replay, a.calls, a.warmup)
+    line.update(graph_ms_median=round(gm, 3), graph_ms_min=round(gb, 3), graph_equals_eager=bool(torch.equal(out, hidden)))
+    # per kernel
+    n_prof = 5
+    _lib.profile_enable(True)
+    for _ in range(n_prof):
+        net.forward_time_major(mel)
+    torch.cuda.synchronize()
+    prof = _lib.profile_summary()
+    _lib.profile_enable(False)
+    line["kernels_ms_per_call"] = {k: [c // n_prof, round(t / n_prof, 4)] for k, (c, t) in sorted(prof.items())}
+    conv_ms = sum(t for k, (c, t) in prof.items() if k.startswith("rmvpe_conv")) / n_prof
+    flop = conv_flop(shapes, FULL, B, T)
+    line.update(conv_gflop=round(flop / 1e9, 1), conv_ms=round(conv_ms, 3),
+                conv_f32_mfma_peak_fraction=round(flop / (conv_ms * 1e-3) / F32_MFMA_PEAK, 4),
+                conv_floor_ms_at_peak=round(flop / F32_MFMA_PEAK * 1e3, 3))
+    if "rmvpe_gru" in prof:
+        line["gru_us_per_step"] = round(prof["rmvpe_gru"][1] / n_prof / T * 1e3, 3)
+    if not a.no_torch:
+        try:
+            P = {k: torch.from_numpy(v).to(dev) for k, v in host.items()}
+            gru = torch.nn.GRU(384, 256, num_layers=1, batch_first=True, bidirectional=True).to(dev).eval()
+            gru.load_state_dict({k[len("fc.0.gru."):]: v for k, v in P.items() if k.startswith("fc.0.gru.")})
+            mel_ct = mel.transpose(1, 2).contiguous()
+            with torch.no_grad():
+                ref = torch_e2e0(P, FULL, mel_ct, gru)
+                line["torch_max_abs_diff"] = float((ref - hidden).abs().max())
+                tm, tb, _ = time_calls(lambda: torch_e2e0(P, FULL, mel_ct, gru), max(a.calls // 5, 10), 3)
+            line["torch_ms_median"], line["torch_ms_min"] = round(tm, 3), round(tb, 3)
+        except Exception as e:
+            line["torch_error"] = f"{type(e).__name__}: {e}"[:300]
+    print(json.dumps(line), flush=True)
+    net.close()
+    ms_.close()
+
+
+if __name__ == "__main__":
+    main()
