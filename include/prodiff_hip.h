@@ -19,6 +19,9 @@
  *    layout ProDiff's condition/mel already have at the sampler boundary
  *    (prodiff.py:136-138 receives cond [B,T,H]; :151 returns mel [B,T,M]).
  *    "channel-major" = PyTorch Conv1d layout [batch][channel][time].
+ *    The 2-D networks (pitch extraction, harmonic-noise separation) keep channels-last
+ *    images [batch][frame][bin][channel] inside; spectra cross the boundary as planar
+ *    re / im arrays [row][frame][bin].
  */
 #ifndef PRODIFF_HIP_H
 #define PRODIFF_HIP_H
@@ -744,6 +747,85 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
  * it is not rounded to f32 on the way. */
 int pd_rmvpe_decode(const float* hidden, float* f0, int B, int T, int n_class, float thred, const long long* center,
                     double cents_const, void* stream);
+
+/* ================================================================ harmonic-noise separation
+ * pd_vr -- CascadedNet of modules/vr (nets.py, layers.py) with is_complex = True, its zero-padded STFT and its
+ * iSTFT: what extract_harmonic_aperiodic runs on a vocoder output (handler/infer/handler.py:349-358) and on every
+ * training utterance (component/binarizer/svs.py:113).  Inference only, fp32 only.
+ *   frames:  n_frames = L / hop + 1, T = 32 (n_frames / 32 + 1), T_pad = (T - 1) hop - L, Tl_pad = (T_pad / 2 / hop) hop
+ *            zeros on the left and the rest on the right; torch.stft(n_fft, hop, periodic Hann(n_fft), center = True,
+ *            pad_mode = 'constant') of that has exactly T frames.  Frame t covers samples [t hop - lead, t hop - lead +
+ *            n_fft) of the row with lead = n_fft / 2 + Tl_pad, zero outside [0, L).
+ *   network: the input is cat([real, imag]) of the bins [0, n_fft / 2) (2 channels mono, re_L re_R im_L im_R stereo).
+ *            BaseNet(nin, n): enc1 = conv3x3 + BN + ReLU; enc2..5 = two conv3x3 + BN + LeakyReLU(0.01), the first
+ *            with stride 2, widths n (2, 4, 6, 8); ASPP (mean over the bins -> 1x1 conv repeated over the bins, a 1x1
+ *            conv, three 3x3 convs dilated (4,2), (8,4), (12,6) as (bins, frames), concat, 1x1 bottleneck); dec4..2 =
+ *            bilinear x2 (align_corners) cat skip -> conv3x3 + BN + ReLU; lstm_dec2 = 1x1 conv to one channel + BN +
+ *            ReLU, a bidirectional LSTM over the frames (input = the bins, gate order i f g o, h_0 = c_0 = 0),
+ *            Linear + BatchNorm1d + ReLU, appended as one channel; dec1.  The cascade: stage 1 on the low and the high
+ *            half of the bins (BaseNet(nin, nout/2) + 1x1 conv to nout/4; BaseNet(nin, nout/4)), stage 2 on
+ *            cat([band input, stage-1 output]) (widths nout and nout/2), stage 3 on cat([x, aux1, aux2]) over all
+ *            bins, `out` (1x1, no bias), mask = tanh(|m|) m / (|m| + 1e-8) on the complex pairs, the last bin
+ *            repeated once to n_fft / 2 + 1 bins.  T must be a multiple of 32, so that crop_center is the identity.
+ *   inverse: torch.istft(spec * mask, n_fft, hop, Hann) and the samples [Tl_pad, Tl_pad + L) of it; the imaginary
+ *            parts of the DC and Nyquist bins do not enter.
+ * Every BatchNorm is the eval form (eps 1e-5), folded into its conv or Linear at create in double precision and
+ * rounded once.  Spectra and masks cross the C-ABI as two planar f32 arrays [rows][T][n_fft / 2 + 1] (rows =
+ * B * channels, row b * channels + c). */
+typedef struct pd_vr pd_vr;
+
+typedef struct {
+  int n_fft;        /* 2048; a multiple of 64 in [64, 16384]                                               */
+  int hop_length;   /* 512; >= 16, a divisor of n_fft other than n_fft itself (the squared-window overlap  */
+                    /* sum reaches zero at hop = n_fft; torch.istft raises there too)                      */
+  int nout;         /* 32; a multiple of 4 in [4, 256]                                                     */
+  int nout_lstm;    /* 128; a multiple of 4 (the high-band nets halve it, the two directions halve it      */
+                    /* again), at most 128: the recurrence kernel keeps a W_hh row of <= 64 hidden units   */
+                    /* per direction in registers                                                          */
+  int is_mono;      /* 0 (stereo model, 2 channels) or 1                                                   */
+} pd_vr_dims;
+
+/* Parameter order = the reference state-dict order without any num_batches_tracked: with cba(p) =
+ * p.conv.0.weight, p.conv.1.{weight,bias,running_mean,running_var} and base(p) = cba(p.enc1), cba(p.encK.conv1),
+ * cba(p.encK.conv2) for K = 2..5, cba(p.aspp.conv1.1), cba(p.aspp.conv2..5), cba(p.aspp.bottleneck),
+ * cba(p.dec4.conv1), cba(p.dec3.conv1), cba(p.dec2.conv1), cba(p.lstm_dec2.conv),
+ * p.lstm_dec2.lstm.{weight_ih_l0,weight_hh_l0,bias_ih_l0,bias_hh_l0} and the same four with the suffix _reverse,
+ * p.lstm_dec2.dense.0.{weight,bias}, p.lstm_dec2.dense.1.{weight,bias,running_mean,running_var}, cba(p.dec1.conv1)
+ * (114 tensors):
+ *   base(stg1_low_band_net.0), cba(stg1_low_band_net.1), base(stg1_high_band_net), base(stg2_low_band_net.0),
+ *   cba(stg2_low_band_net.1), base(stg2_high_band_net), base(stg3_full_band_net), out.weight, aux_out.weight
+ * (582 tensors; aux_out is a training-time head and is not read), then the analysis and synthesis window [n_fft]
+ * (the model's non-persistent `window` buffer, torch.hann_window(n_fft) in float32: the DFT tables are built from
+ * these values, so that the frames at the edge of the zero padding, which see only the window's small ends, hold
+ * what the reference's hold).  583 entries; 0 for dimensions outside the supported set. */
+int pd_vr_num_params(const pd_vr_dims* dims);
+/* Folds and packs every parameter and builds the DFT tables in the handle's weight pool on `stream`.  A dtype
+ * other than PD_DTYPE_F32, or dimensions outside the ranges above, return PD_ERR_UNSUPPORTED before anything is
+ * allocated. */
+int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, void* stream, pd_vr** out);
+/* The caller must ensure that no call on the handle is still in flight. */
+void pd_vr_destroy(pd_vr* h);
+/* T and lead (above) for a row of n_samples. */
+int pd_vr_frames(const pd_vr* h, int n_samples);
+int pd_vr_lead(const pd_vr* h, int n_samples);
+/* Bytes pd_vr_separate needs for [B][channels][L]; pd_vr_mask on T frames needs those of L = (T - 32) hop. */
+size_t pd_vr_workspace_size(const pd_vr* h, int B, int L);
+/* The three stages.  All calls are stream-ordered, allocation-free and capturable; an output row depends neither
+ * on the batch size nor on its position in the batch.
+ * pd_vr_stft: wav [rows][L] -> re, im [rows][T][n_fft/2 + 1]. */
+int pd_vr_stft(const pd_vr* h, const float* wav, float* re, float* im, int rows, int L, int lead, int T, void* stream);
+/* pd_vr_mask: CascadedNet.forward.  spectrum -> mask, both [B channels][T][n_fft/2 + 1]; T a multiple of 32. */
+int pd_vr_mask(const pd_vr* h, const float* spec_re, const float* spec_im, float* mask_re, float* mask_im, int B, int T,
+               void* workspace, size_t ws_bytes, void* stream);
+/* pd_vr_istft: y [rows][L_out] = the samples [lead - n_fft/2, lead - n_fft/2 + L_out) of torch.istft(spec * mask)
+ * (mask_re = mask_im = NULL: of spec), which must lie inside its (T - 1) hop samples.  With resid non-NULL the same
+ * epilogue writes resid = wav - y (wav [rows][L_out]). */
+int pd_vr_istft(const pd_vr* h, const float* spec_re, const float* spec_im, const float* mask_re, const float* mask_im,
+                const float* wav, float* y, float* resid, int rows, int T, int lead, int L_out, void* stream);
+/* predict_from_audio: wav [B][channels][L] -> harmonic [B][channels][L], and aperiodic = wav - harmonic when
+ * non-NULL.  The spectrum and the mask live in the workspace; nothing spectrum-sized is copied between the stages. */
+int pd_vr_separate(const pd_vr* h, const float* wav, float* harmonic, float* aperiodic, int B, int L, void* workspace,
+                   size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

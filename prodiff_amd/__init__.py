@@ -19,6 +19,8 @@ Drop-in replacements for the reference hot path (see DESIGN.md / INTEGRATION.md)
         <- torchaudio.transforms.Resample (component/pe/rmvpe.py:49), librosa.resample (utils/data_gen_utils.py:51)
   * prodiff_amd.rmvpe.RMVPE / E2E0 / MelSpectrogram / to_local_average_f0 (pitch extraction on the GPU)
         <- component/pe/rmvpe.py, modules/rmvpe/{model,deepunet,seq,spec,utils}.py
+  * prodiff_amd.vr.CascadedNet / load_sep_model / extract_harmonic_aperiodic (harmonic-noise separation on the GPU)
+        <- modules/vr/{nets,layers,__init__}.py, component/binarizer/binarizer_utils.py
 All compute runs in libprodiff_hip.so (hand-written gfx950 HIP kernels).
 """
 from .prodiff import GaussianDiffusion, WaveNet  # noqa: F401
@@ -31,8 +33,9 @@ from .mel import STFT, mel_filterbank  # noqa: F401
 # the functional form stays prodiff_amd.resample.resample: binding it here would hide the module of that name
 from .resample import KAISER_BEST, Resample, sinc_resample_kernel64  # noqa: F401
 from .rmvpe import E2E0, RMVPE, MelSpectrogram, to_local_average_f0  # noqa: F401
+from .vr import CascadedNet, extract_harmonic_aperiodic, load_sep_model  # noqa: F401
 
 __all__ = ["WaveNet", "GaussianDiffusion", "FastDiff", "sampling_given_noise_schedule", "RectifiedFlow",
            "PitchRectifiedFlow", "NsfGenerator", "NsfHifiGAN", "ProDiffTeacher", "PitchPredictor", "DurPredictor",
            "STFT", "mel_filterbank", "Resample", "KAISER_BEST", "sinc_resample_kernel64", "E2E0", "RMVPE",
-           "MelSpectrogram", "to_local_average_f0"]
+           "MelSpectrogram", "to_local_average_f0", "CascadedNet", "load_sep_model", "extract_harmonic_aperiodic"]

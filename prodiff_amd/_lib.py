@@ -102,6 +102,11 @@ class pd_rmvpe_dims(C.Structure):
                 ("en_out_channels", C.c_int), ("n_mels", C.c_int), ("n_class", C.c_int), ("gru_hidden", C.c_int)]
 
 
+class pd_vr_dims(C.Structure):
+    _fields_ = [("n_fft", C.c_int), ("hop_length", C.c_int), ("nout", C.c_int), ("nout_lstm", C.c_int),
+                ("is_mono", C.c_int)]
+
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -184,6 +189,16 @@ _SIGS = {
     "pd_rmvpe_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "pd_rmvpe_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "pd_rmvpe_decode": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_double, _VP]),
+    "pd_vr_num_params": (C.c_int, [C.POINTER(pd_vr_dims)]),
+    "pd_vr_create": (C.c_int, [C.POINTER(pd_vr_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
+    "pd_vr_destroy": (None, [_VP]),
+    "pd_vr_frames": (C.c_int, [_VP, C.c_int]),
+    "pd_vr_lead": (C.c_int, [_VP, C.c_int]),
+    "pd_vr_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "pd_vr_stft": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
+    "pd_vr_mask": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_vr_istft": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
+    "pd_vr_separate": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 

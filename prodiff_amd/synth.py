@@ -575,3 +575,82 @@ def _rmvpe_is_bn(name):
 
 def synth_rmvpe_params(shapes, seed, fc_gain=RMVPE_FC_GAIN):
     return OrderedDict((k, synth_rmvpe_tensor(k, v, seed, fc_gain)) for k, v in shapes.items())
+
+
+# --------------------------------------------------------------------------
+# Harmonic-noise separation (modules/vr/nets.py CascadedNet, is_complex = True): state-dict order without the
+# num_batches_tracked counters
+# --------------------------------------------------------------------------
+def _vr_cba(s, p, cin, cout, k):
+    s[p + ".conv.0.weight"] = (cout, cin, k, k)
+    for leaf in ("weight", "bias", "running_mean", "running_var"):
+        s[f"{p}.conv.1.{leaf}"] = (cout,)
+
+
+def _vr_base(s, p, nin, n, nin_lstm, nout_lstm):
+    _vr_cba(s, p + ".enc1", nin, n, 3)
+    for i, (cin, cout) in enumerate(((n, 2 * n), (2 * n, 4 * n), (4 * n, 6 * n), (6 * n, 8 * n)), start=2):
+        _vr_cba(s, f"{p}.enc{i}.conv1", cin, cout, 3)
+        _vr_cba(s, f"{p}.enc{i}.conv2", cout, cout, 3)
+    _vr_cba(s, p + ".aspp.conv1.1", 8 * n, 8 * n, 1)
+    _vr_cba(s, p + ".aspp.conv2", 8 * n, 8 * n, 1)
+    for i in (3, 4, 5):
+        _vr_cba(s, f"{p}.aspp.conv{i}", 8 * n, 8 * n, 3)
+    _vr_cba(s, p + ".aspp.bottleneck", 40 * n, 8 * n, 1)
+    _vr_cba(s, p + ".dec4.conv1", 14 * n, 6 * n, 3)
+    _vr_cba(s, p + ".dec3.conv1", 10 * n, 4 * n, 3)
+    _vr_cba(s, p + ".dec2.conv1", 6 * n, 2 * n, 3)
+    _vr_cba(s, p + ".lstm_dec2.conv", 2 * n, 1, 1)
+    hid = nout_lstm // 2
+    for suffix in ("", "_reverse"):
+        s[f"{p}.lstm_dec2.lstm.weight_ih_l0{suffix}"] = (4 * hid, nin_lstm)
+        s[f"{p}.lstm_dec2.lstm.weight_hh_l0{suffix}"] = (4 * hid, hid)
+        s[f"{p}.lstm_dec2.lstm.bias_ih_l0{suffix}"] = (4 * hid,)
+        s[f"{p}.lstm_dec2.lstm.bias_hh_l0{suffix}"] = (4 * hid,)
+    s[p + ".lstm_dec2.dense.0.weight"] = (nin_lstm, nout_lstm)
+    s[p + ".lstm_dec2.dense.0.bias"] = (nin_lstm,)
+    for leaf in ("weight", "bias", "running_mean", "running_var"):
+        s[f"{p}.lstm_dec2.dense.1.{leaf}"] = (nin_lstm,)
+    _vr_cba(s, p + ".dec1.conv1", 3 * n + 1, n, 3)
+
+
+def vr_param_shapes(n_fft=2048, nout=32, nout_lstm=128, is_mono=False):
+    """Ordered ``{key: shape}`` of the parameters pd_vr_create takes (include/prodiff_hip.h)."""
+    s = OrderedDict()
+    nin = 2 if is_mono else 4
+    nin_lstm = n_fft // 2 // 2
+    _vr_base(s, "stg1_low_band_net.0", nin, nout // 2, nin_lstm // 2, nout_lstm)
+    _vr_cba(s, "stg1_low_band_net.1", nout // 2, nout // 4, 1)
+    _vr_base(s, "stg1_high_band_net", nin, nout // 4, nin_lstm // 2, nout_lstm // 2)
+    _vr_base(s, "stg2_low_band_net.0", nout // 4 + nin, nout, nin_lstm // 2, nout_lstm)
+    _vr_cba(s, "stg2_low_band_net.1", nout, nout // 2, 1)
+    _vr_base(s, "stg2_high_band_net", nout // 4 + nin, nout // 2, nin_lstm // 2, nout_lstm // 2)
+    _vr_base(s, "stg3_full_band_net", 3 * nout // 4 + nin, nout, nin_lstm, nout_lstm)
+    s["out.weight"] = (nin, nout, 1, 1)
+    s["aux_out.weight"] = (nin, 3 * nout // 4, 1, 1)
+    return s
+
+
+def vr_is_bn(name):
+    """The BatchNorm2d after every conv (child 1 of a Conv2DBNActiv's stack) and the LSTM module's BatchNorm1d."""
+    return name.rsplit(".", 1)[0].endswith((".conv.1", ".dense.1"))
+
+
+def synth_vr_tensor(name, shape, seed):
+    """The separation model's draw rules: every weight with two or more dimensions (conv, Linear, LSTM) N(0, 1/fan_in),
+    BatchNorm gamma and running_var uniform in [0.75, 1.25], BatchNorm beta and running_mean 0.1 N(0, 1), the other
+    biases 0.02 N(0, 1)."""
+    rng = _rng(seed, name)
+    leaf = name.rsplit(".", 1)[-1]
+    if vr_is_bn(name) and leaf in ("weight", "running_var"):
+        return (0.75 + 0.5 * rng.random(size=shape, dtype=np.float32)).astype(np.float32)
+    z = rng.standard_normal(size=shape, dtype=np.float32)
+    if vr_is_bn(name):
+        return (0.1 * z).astype(np.float32)
+    if len(shape) == 1:
+        return (0.02 * z).astype(np.float32)
+    return (z / np.sqrt(int(np.prod(shape[1:])))).astype(np.float32)
+
+
+def synth_vr_params(shapes, seed):
+    return OrderedDict((k, synth_vr_tensor(k, v, seed)) for k, v in shapes.items())
