@@ -827,6 +827,75 @@ int pd_vr_istft(const pd_vr* h, const float* spec_re, const float* spec_im, cons
 int pd_vr_separate(const pd_vr* h, const float* wav, float* harmonic, float* aperiodic, int B, int L, void* workspace,
                    size_t ws_bytes, void* stream);
 
+/* ======================================================================== variance curves
+ * pd_curves -- get_kth_harmonic, get_energy, get_voicing, get_breath and get_tension of
+ * component/binarizer/binarizer_utils.py:115-213 (binarization: component/binarizer/svs.py:140-177; inference:
+ * handler/infer/handler.py:352-358), with librosa 0.8.0's feature.rms and amplitude_to_db restated.  fp32 only.
+ *   frames:   T = L / hop + 1 for a row of L samples, for the STFT (center = True) and the RMS alike.
+ *   harmonic: f = f0 (k + 1), padded on the right with its last value to max(T_f0, T) frames; interp_f0 over all of
+ *             it (log2 of the voiced frames, np.interp in double across the frames with f == 0, flat beyond the first
+ *             and last voiced frame, rounded to f32, then exp2 of every frame; an all-unvoiced row keeps -inf, so
+ *             f = 0); center = (f * win_size) / samplerate, start = max(center - hw, 0), end = min(center + hw,
+ *             win_size / 2 + 1), bin i kept iff center >= 1 and start <= i < end, all in f32: at most 8 bins.  Only
+ *             those bins of the STFT (reflect padding of win_size / 2, periodic Nuttall window) are computed, and the
+ *             inverse is torch.istft's: the kept bins' sinusoids times the window, overlap-added and divided by the
+ *             squared-window envelope of the frames that exist; DC and Nyquist enter with their real parts only.
+ *             A frame without bins, and so an all-unvoiced row, gives exact zeros.
+ *   rms:      the row padded by win_size / 2 on both sides (reflect, librosa 0.8.0, or zeros, librosa >= 0.10),
+ *             frame t = padded [t hop, t hop + win_size), sqrt(mean(x^2)).
+ *   finish:   the curve cut or zero-padded to mel_len; dB = max(d, max over the row of d - 80) with
+ *             d = 10 log10(max(1e-10, S^2)); tension t = sqrt(max(E_full^2 - E_base^2, 0)) / (E_full + 1e-5),
+ *             ratio: clip to [0, 1]; db: clip to [1e-5, 1], then dB; logit: clip to [1e-4, 1 - 1e-4], log(t / (1 - t));
+ *             then the smoothing taps (cross-correlation, (k - 1) / 2 replicated frames on the left, the rest on the
+ *             right: Conv1d padding = 'same', padding_mode = 'replicate'), then with `norm` clamp to [db_min, db_max]
+ *             and (x - db_min) / (db_max - db_min).
+ * Sums run in double and round once; the mask decision is f32 as above.  Rows of a batch have equal length. */
+typedef struct pd_curves pd_curves;
+
+typedef struct {
+  int samplerate;     /* 44100; positive                                                                   */
+  int win_size;       /* 2048; a multiple of 64 in [64, 4096]                                              */
+  int hop_size;       /* 512; divides win_size, win_size / hop_size in [2, 16]                             */
+  float half_width;   /* 3.5; in (0, 3.5], so that at most 8 bins survive                                  */
+} pd_curves_dims;
+
+#define PD_CURVES_PAD_REFLECT 0
+#define PD_CURVES_PAD_CONSTANT 1
+#define PD_CURVES_AMPLITUDE 0
+#define PD_CURVES_DB 1
+#define PD_CURVES_TENSION_RATIO 0
+#define PD_CURVES_TENSION_DB 1
+#define PD_CURVES_TENSION_LOGIT 2
+
+/* Builds the window and the win_size-entry cos / sin table in double precision, rounded once to f32.  Dimensions
+ * outside the ranges above return PD_ERR_ARG, the message naming the value, before anything is allocated. */
+int pd_curves_create(const pd_curves_dims* dims, void* stream, pd_curves** out);
+/* The caller must ensure that no call on the handle is still in flight. */
+void pd_curves_destroy(pd_curves* h);
+/* T for a row of n_samples; 0 for a null handle or n_samples <= win_size / 2 (reflect padding needs more). */
+int pd_curves_frames(const pd_curves* h, int n_samples);
+/* Bytes any call below needs for B rows of L samples and T_f0 f0 frames (0 where the call takes no f0). */
+size_t pd_curves_workspace_size(const pd_curves* h, int B, int L, int T_f0);
+/* All calls are stream-ordered, allocation-free and capturable; an output row depends neither on the batch size nor
+ * on its position in the batch.  `taps` is a device array of kernel_size in [3, 257] floats, or NULL: no smoothing.
+ * pd_curves_kth_harmonic: wav [B][L], f0 [B][T_f0] in Hz (0 = unvoiced), k >= 0 -> y [B][L], and with resid
+ * non-NULL resid = wav - y from the same epilogue. */
+int pd_curves_kth_harmonic(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid, int B,
+                           int L, int T_f0, void* workspace, size_t ws_bytes, void* stream);
+/* get_energy / get_voicing / get_breath: wav [B][L] -> out [B][mel_len]; domain PD_CURVES_AMPLITUDE or PD_CURVES_DB. */
+int pd_curves_energy(const pd_curves* h, const float* wav, int pad_mode, int domain, int mel_len, const float* taps,
+                     int kernel_size, int norm, float db_min, float db_max, float* out, int B, int L, void* workspace,
+                     size_t ws_bytes, void* stream);
+/* SinusoidalSmoothingConv1d.forward on any taps: x [rows][T] -> out [rows][T]. */
+int pd_curves_smooth(const float* x, const float* taps, int kernel_size, float* out, int rows, int T, void* stream);
+/* The fused call: sp, ap [B][L], f0 [B][T_f0] -> voicing, breath, tension [B][mel_len]; rms(sp) is computed once for
+ * voicing and tension.  voicing and breath (with ap) may be NULL: get_tension alone.  base non-NULL: the base
+ * harmonic [B][L] (k = 0) is returned too.  norm, db_min, db_max apply to voicing and breath. */
+int pd_curves_forward(const pd_curves* h, const float* sp, const float* ap, const float* f0, int pad_mode,
+                      int tension_domain, int mel_len, const float* taps, int kernel_size, int norm, float db_min,
+                      float db_max, float* voicing, float* breath, float* tension, float* base, int B, int L, int T_f0,
+                      void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,10 @@ Drop-in replacements for the reference hot path (see DESIGN.md / INTEGRATION.md)
         <- component/pe/rmvpe.py, modules/rmvpe/{model,deepunet,seq,spec,utils}.py
   * prodiff_amd.vr.CascadedNet / load_sep_model / extract_harmonic_aperiodic (harmonic-noise separation on the GPU)
         <- modules/vr/{nets,layers,__init__}.py, component/binarizer/binarizer_utils.py
+  * prodiff_amd.curves.get_energy / get_voicing / get_breath / get_kth_harmonic / get_tension /
+    SinusoidalSmoothingConv1d / VarianceCurves / isolate_parts (variance curves and k-th harmonic isolation on the GPU)
+        <- component/binarizer/binarizer_utils.py, modules/commons/common_layers.py, librosa.feature.rms,
+           librosa.amplitude_to_db
 All compute runs in libprodiff_hip.so (hand-written gfx950 HIP kernels).
 """
 from .prodiff import GaussianDiffusion, WaveNet  # noqa: F401
@@ -34,8 +38,12 @@ from .mel import STFT, mel_filterbank  # noqa: F401
 from .resample import KAISER_BEST, Resample, sinc_resample_kernel64  # noqa: F401
 from .rmvpe import E2E0, RMVPE, MelSpectrogram, to_local_average_f0  # noqa: F401
 from .vr import CascadedNet, extract_harmonic_aperiodic, load_sep_model  # noqa: F401
+from .curves import (SinusoidalSmoothingConv1d, VarianceCurves, get_breath, get_energy, get_kth_harmonic,  # noqa: F401
+                     get_tension, get_voicing, isolate_parts)
 
 __all__ = ["WaveNet", "GaussianDiffusion", "FastDiff", "sampling_given_noise_schedule", "RectifiedFlow",
            "PitchRectifiedFlow", "NsfGenerator", "NsfHifiGAN", "ProDiffTeacher", "PitchPredictor", "DurPredictor",
            "STFT", "mel_filterbank", "Resample", "KAISER_BEST", "sinc_resample_kernel64", "E2E0", "RMVPE",
-           "MelSpectrogram", "to_local_average_f0", "CascadedNet", "load_sep_model", "extract_harmonic_aperiodic"]
+           "MelSpectrogram", "to_local_average_f0", "CascadedNet", "load_sep_model", "extract_harmonic_aperiodic",
+           "SinusoidalSmoothingConv1d", "VarianceCurves", "get_energy", "get_voicing", "get_breath", "get_kth_harmonic",
+           "get_tension", "isolate_parts"]

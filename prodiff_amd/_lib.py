@@ -107,6 +107,10 @@ class pd_vr_dims(C.Structure):
                 ("is_mono", C.c_int)]
 
 
+class pd_curves_dims(C.Structure):
+    _fields_ = [("samplerate", C.c_int), ("win_size", C.c_int), ("hop_size", C.c_int), ("half_width", C.c_float)]
+
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -199,6 +203,17 @@ _SIGS = {
     "pd_vr_mask": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "pd_vr_istft": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "pd_vr_separate": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_curves_create": (C.c_int, [C.POINTER(pd_curves_dims), _VP, C.POINTER(_VP)]),
+    "pd_curves_destroy": (None, [_VP]),
+    "pd_curves_frames": (C.c_int, [_VP, C.c_int]),
+    "pd_curves_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
+    "pd_curves_kth_harmonic": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t,
+                                         _VP]),
+    "pd_curves_energy": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, C.c_float, C.c_float,
+                                   _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_curves_smooth": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP]),
+    "pd_curves_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, C.c_float,
+                                    C.c_float, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 
