@@ -259,8 +259,9 @@ class NativeHandle:
     again.  ``create`` / ``destroy`` / ``set_option`` / ``num_params`` name library functions (looked
     up on first use, so building a module does not load the library)."""
 
-    def __init__(self, name, create, destroy, set_option=None, option_ids=None, num_params=None):
+    def __init__(self, name, create, destroy, set_option=None, option_ids=None, num_params=None, plain_create=False):
         self.name = name
+        self._plain_create = plain_create   # create(dims, tensor..., stream, out): no parameter list, no dtype
         self._create, self._destroy, self._set_option, self._num_params = create, destroy, set_option, num_params
         self.option_ids = option_ids or {}
         self.dtype = "fp32"
@@ -317,7 +318,8 @@ class NativeHandle:
         return h
 
     def _call_create(self, create, dims, tensors, stream, h):
-        """The library's create call (a handle whose create takes other arguments overrides this)."""
+        if self._plain_create:
+            return create(C.byref(dims), *[fptr(t) for t in tensors], stream, C.byref(h))
         arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
         dt = PD_DTYPE_BF16 if self.dtype == "bf16" else PD_DTYPE_F32
         return create(C.byref(dims), arr, dt, stream, C.byref(h))
@@ -338,6 +340,42 @@ class NativeHandle:
             self.close()
         except Exception:
             pass
+
+
+class HandleCache:
+    """The handles of a front end whose create takes no parameter list (mel analysis, resampler, variance
+    curves), one per (key, device): ``handles`` maps key + (device,) to its NativeHandle, oldest first; at
+    ``limit`` entries the oldest is closed and dropped."""
+
+    def __init__(self, name, create, destroy, limit=None):
+        self.name, self._create, self._destroy, self.limit = name, create, destroy, limit
+        self.handles = {}
+
+    def _new(self):
+        return NativeHandle(self.name, self._create, self._destroy, plain_create=True)
+
+    def get(self, device, key, build):
+        """The C handle for ``key`` (a tuple) on ``device``; ``build(device) -> (dims struct, tensors)`` is
+        called with the normalised device when the handle has to be created."""
+        import torch
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise HipError(f"{self.name}: runs on the GPU only (got a CPU tensor; there is no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = tuple(key) + (str(device),)
+        nh = self.handles.get(key)
+        if nh is None:
+            if self.limit is not None and len(self.handles) >= self.limit:
+                self.handles.pop(next(iter(self.handles))).close()
+            nh = self.handles[key] = self._new()
+        with torch.cuda.device(device):     # WeightPool::commit allocates on the current device
+            return nh.get(key, lambda: build(device), device=device)
+
+    def close(self):
+        for nh in self.handles.values():
+            nh.close()
+        self.handles.clear()
 
 
 def fptr(t):

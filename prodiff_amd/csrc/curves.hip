@@ -20,6 +20,7 @@
 #include "../../include/prodiff_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "mfma_f32.h"
 
 using namespace pd;
 
@@ -128,13 +129,6 @@ __device__ __forceinline__ void cv_block_sum(double (&v)[N], double* red, int ti
   __syncthreads();
 }
 
-// reflect (numpy 'reflect', torch 'reflect': the edge sample is not repeated) of s into [0, L), L > win / 2
-__device__ __forceinline__ long long cv_reflect(long long s, int L) {
-  s = s < 0 ? -s : s;
-  s = s >= L ? 2ll * (L - 1) - s : s;
-  return min(max(s, 0ll), (long long)L - 1);
-}
-
 // The twiddle table into LDS: the kernels below gather from it at (bin * n) mod win, one 8-byte read per twiddle.
 __device__ __forceinline__ void cv_stage_table(float2* stw, const float2* __restrict__ tw, int win, int tid, int nt) {
   for (int i = tid; i < win; i += nt) stw[i] = tw[i];
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(CV_NT) void cv_analysis_kernel(const AnArgs a) {
 #pragma unroll
   for (int q = 0; q < 2 * CV_MAXB; ++q) acc[q] = 0.0;
   for (int m = tid; m < win; m += CV_NT) {
-    const long long s = cv_reflect((long long)t * a.p.hop + m - half, a.L);
+    const long long s = reflect_index((long long)t * a.p.hop + m - half, a.L);
     const double xw = (double)__fmul_rn(wrow[s], a.w[m]);
     int idx = (int)(((long long)fb.x * m) % win);
 #pragma unroll
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(CV_NT) void cv_rms_kernel(const RmsArgs a) {
     const long long s = (long long)t * a.p.hop + m - half;
     double x;
     if (a.constant_pad) x = (s >= 0 && s < a.L) ? (double)wrow[s] : 0.0;
-    else x = (double)wrow[cv_reflect(s, a.L)];
+    else x = (double)wrow[reflect_index(s, a.L)];
     acc[0] += x * x;
   }
   cv_block_sum<1>(acc, red, tid);

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_f32.h"
 
 namespace pd {
 
@@ -83,7 +84,6 @@ struct GemmArgs {
   int lens_mul;             //   on (null: from row T), the rows being in units of 1 / lens_mul frame
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));

@@ -51,6 +51,29 @@ int add_vectors(float* dst, const float* a, const float* b, int n, hipStream_t s
 // weight-norm fold on device: w[co,:] = g[co] * v[co,:] / ||v[co,:]||
 int weight_norm_fold(float* w, const float* g, const float* v, int Cout, int per_row, hipStream_t st);
 
+// Create-time packing of the 2-D convs that run on v_mfma_f32_32x32x2_f32 (rmvpe.hip, vr.hip):
+//   dst[((ct * nchunk + chunk) * taps + tap) * 32 + n][16] = w(co = ct * 32 + n, ci, source tap) * scale(co)
+// The chunks of 16 input channels run over source 0's c0 channels, then source 1's c1, each source padded to whole
+// chunks with zero weights; rows co >= cout are zero.  scale = bn_scale of a BatchNorm behind the conv, folded in
+// double and rounded once (bn_g null: 1).  src is Conv2d's [cout][c0 + c1][taps], read as stored (TAPS_STORED) or
+// with the two axes of a 3x3 kernel swapped (TAPS_SWAPPED: tap = 3 * (second axis) + (first axis)), or
+// ConvTranspose2d's [c0 + c1][cout][taps] read with the taps flipped (TAPS_FLIPPED_T).
+enum ConvTaps { TAPS_STORED = 0, TAPS_FLIPPED_T = 1, TAPS_SWAPPED = 2 };
+__host__ __device__ inline int ctiles(int cout) { return (cout + 31) / 32; }
+__host__ __device__ inline int conv_chunks(int c) { return (c + 15) / 16; }
+inline size_t packed_conv(int c0, int c1, int cout, int taps) {
+  return (size_t)ctiles(cout) * (conv_chunks(c0) + conv_chunks(c1)) * taps * 512;
+}
+int pack_conv_tiles(float* dst, const float* src, const float* bn_g, const float* bn_var, int cout, int c0, int c1,
+                    int taps, ConvTaps order, hipStream_t st);
+// BN fold factor of channel co in double: gamma / sqrt(var + eps)
+__device__ __forceinline__ double bn_scale(const float* g, const float* var, int co) {
+  return (double)g[co] / sqrt((double)var[co] + 1e-5);
+}
+// dst[co] = beta - mean * bn_scale(co), co < cout: the bias a conv without one gets from its folded BatchNorm
+int fold_bn_bias(float* dst, const float* g, const float* beta, const float* mean, const float* var, int cout,
+                 hipStream_t st);
+
 // fp32 -> bf16 (round to nearest even)
 int convert_f32_bf16(const float* src, __bf16* dst, long long n, hipStream_t st);
 // bf16 mirrors of packed fp32 weight pools (WeightPool::mirror_bf16): launch_gemm uses the bf16

@@ -354,6 +354,57 @@ int weight_norm_fold(float* w, const float* g, const float* v, int Cout, int per
   return PD_OK;
 }
 
+__global__ __launch_bounds__(256) void pack_conv_tiles_kernel(float* __restrict__ dst, const float* __restrict__ src,
+                                                              const float* g, const float* var, int cout, int c0, int c1,
+                                                              int taps, int order, long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int q = (int)(idx & 15), n = (int)((idx >> 4) & 31);
+  long long rest = idx >> 9;
+  const int tap = (int)(rest % taps);
+  rest /= taps;
+  const int nch0 = conv_chunks(c0), nchunk = nch0 + conv_chunks(c1);
+  const int chunk = (int)(rest % nchunk), ct = (int)(rest / nchunk);
+  const int co = ct * 32 + n;
+  int ci = -1;
+  if (chunk < nch0) {
+    if (chunk * 16 + q < c0) ci = chunk * 16 + q;
+  } else if ((chunk - nch0) * 16 + q < c1) {
+    ci = c0 + (chunk - nch0) * 16 + q;
+  }
+  float v = 0.f;
+  if (co < cout && ci >= 0) {
+    const int stap = order == TAPS_SWAPPED && taps == 9 ? (tap % 3) * 3 + tap / 3 : tap;
+    const float w = order == TAPS_FLIPPED_T ? src[((long long)ci * cout + co) * taps + (taps - 1 - tap)]
+                                            : src[((long long)co * (c0 + c1) + ci) * taps + stap];
+    v = g ? (float)((double)w * bn_scale(g, var, co)) : w;
+  }
+  dst[idx] = v;
+}
+
+int pack_conv_tiles(float* dst, const float* src, const float* bn_g, const float* bn_var, int cout, int c0, int c1,
+                    int taps, ConvTaps order, hipStream_t st) {
+  const long long total = (long long)packed_conv(c0, c1, cout, taps);
+  hipLaunchKernelGGL(pack_conv_tiles_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, dst, src, bn_g, bn_var, cout, c0,
+                     c1, taps, (int)order, total);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+__global__ __launch_bounds__(256) void fold_bn_bias_kernel(float* __restrict__ dst, const float* g, const float* beta,
+                                                           const float* mean, const float* var, int cout) {
+  const int co = blockIdx.x * 256 + threadIdx.x;
+  if (co >= cout) return;
+  dst[co] = (float)((double)beta[co] - (double)mean[co] * bn_scale(g, var, co));
+}
+
+int fold_bn_bias(float* dst, const float* g, const float* beta, const float* mean, const float* var, int cout,
+                 hipStream_t st) {
+  hipLaunchKernelGGL(fold_bn_bias_kernel, dim3(cdiv(cout, 256)), dim3(256), 0, st, dst, g, beta, mean, var, cout);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
 // ---------------------------------------------------------------- bf16 pools
 __global__ void f2bf_kernel(const float* s, __bf16* d, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

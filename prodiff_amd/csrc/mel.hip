@@ -13,7 +13,7 @@
 // of one utterance stages the signal segment those frames cover in LDS once (reflect padding applied on the
 // way, loads from clamped indices); each of its 8 waves takes 32-bin column tiles, accumulates re^T and im^T
 // [bin][frame] with v_mfma_f32_32x32x2_f32 over n ascending (exact f32: each 16-sample chunk bitwise an fmaf
-// chain from 0, the chunks' sums added in order into compensated totals, mel_fold below), takes the
+// chain from 0, the chunks' sums added in order into compensated totals, mfma_fold of mfma_f32.h), takes the
 // magnitude in registers and feeds it as the B operand of a second MFMA chain into its mel^T [mel][frame]
 // accumulators -- the D layout of the first GEMM (lane = frame, registers = bins) already is a B operand of
 // the second when its K index runs over the bins in register order, so no transpose is needed.  The tiles'
@@ -28,12 +28,11 @@
 #include "../../include/prodiff_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "mfma_f32.h"
 
 using namespace pd;
 
 namespace {
-
-typedef float melx16 __attribute__((ext_vector_type(16)));
 
 constexpr int MEL_TF = 32;          // frames per block = the MFMA column tile
 constexpr int MEL_NW = 8;           // waves per block
@@ -68,8 +67,7 @@ __global__ __launch_bounds__(256) void mel_table_kernel(float* __restrict__ tc, 
   if (n < nf && k < nb && n >= woff && n < woff + wn) {
     const double two_pi = 6.283185307179586476925286766559;
     const double w = 0.5 - 0.5 * cos(two_pi * (double)(n - woff) / (double)wn);   // torch.hann_window, periodic
-    const long long m = ((long long)n * k) % nf;
-    const double ph = two_pi * (double)m / (double)nf;
+    const double ph = dft_phase(n, k, nf);
     c = (float)(w * cos(ph));
     s = (float)(w * sin(ph));
   }
@@ -100,25 +98,6 @@ struct MelArgs {
   MelPlan p;
 };
 
-// One chunk's sums into the running totals, compensated: hi += acc by Knuth's TwoSum, the rounding error of that
-// addition collected in lo, acc back to zero.  A plain chain over the whole frame rounds relative to its
-// partial sums, which stay at the level of the frame's loudest component however quiet the bin (a truncated
-// window leaks); that put quiet mel bands of harmonic signals 5 to 8 times further from float64 than the
-// reference's FFT.  With 16-sample chains from zero and compensated totals the spectrum is within 2e-7 of
-// the frame peak of float64 (mel analysis).
-__device__ __forceinline__ void mel_fold(melx16& acc, melx16& hi, melx16& lo) {
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    const float a = acc[g], h = hi[g];
-    const float s = h + a;
-    const float bb = s - h;
-    const float err = (h - (s - bb)) + (a - bb);
-    hi[g] = s;
-    lo[g] += err;
-    acc[g] = 0.f;
-  }
-}
-
 template <int MT>
 __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];   // the segment, then red[MT * 32][33]
@@ -136,11 +115,7 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
     const int nlog = (MEL_TF - 1) * hn + nf, total = p.nq * hn;
     for (int idx = tid; idx < total; idx += MEL_NT) {
       const int q = idx / hn, r = idx - q * hn;
-      long long src = p0 + idx;
-      src = src < 0 ? -src : src;
-      src = src >= Lb ? 2ll * (Lb - 1) - src : src;
-      src = min(max(src, 0ll), (long long)Lb - 1);
-      const float v = wrow[src];
+      const float v = wrow[reflect_index(p0 + idx, Lb)];
       smem[q * stride + r] = idx < nlog ? v : 0.f;
     }
   }
@@ -155,13 +130,13 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
   // whatever the timing (no atomics), and the mel accumulators live only between the DFT loop and that add.
   for (int tile = wave; tile - wave < p.ntile; tile += MEL_NW) {
     const int col0 = tile * 32;
-    melx16 macc[MT];
+    f32x16 macc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) macc[mt][r] = 0.f;
     if (tile < p.ntile) {
-    melx16 re, im, re_hi, im_hi, re_lo, im_lo;
+    f32x16 re, im, re_hi, im_hi, re_lo, im_lo;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { re[r] = im[r] = re_hi[r] = im_hi[r] = re_lo[r] = im_lo[r] = 0.f; }
     // A = table rows (lane: bin col0 + j, k half kh), B = frame j's samples (lane: frame j, k half kh).
@@ -194,8 +169,8 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
       const bool wrap = r >= hn;
       r = wrap ? r - hn : r;
       sp = wrap ? sp + p.padw : sp;
-      mel_fold(re, re_hi, re_lo);
-      mel_fold(im, im_hi, im_lo);
+      mfma_fold(re, re_hi, re_lo);
+      mfma_fold(im, im_hi, im_lo);
     };
     load_tab(c0, s0, 0);
     for (int ch = 0; ch < nch; ch += 2) {
@@ -210,7 +185,9 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
     }
 #pragma unroll
     for (int g = 0; g < 16; ++g) { re[g] = re_hi[g] + re_lo[g]; im[g] = im_hi[g] + im_lo[g]; }
-    // register g of lane (kh, j): bin col0 + 8 (g / 4) + 4 kh + g % 4 of frame j
+    // register g of lane (kh, j): bin col0 + 8 (g / 4) + 4 kh + g % 4 of frame j.  That is mfma_row (mfma_f32.h),
+    // spelled out in this kernel alone: with the helper the compiler orders the three index sums differently,
+    // allocates the whole kernel's registers anew, and the C5 shape measured 0.1 % slower (1.0792 against 1.0779 ms).
     float mag[16];
 #pragma unroll
     for (int g = 0; g < 16; ++g) mag[g] = sqrtf(__builtin_fmaf(im[g], im[g], re[g] * re[g])) * p.mag_scale;

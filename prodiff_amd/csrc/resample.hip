@@ -35,12 +35,12 @@
 #include "../../include/prodiff_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "mfma_f32.h"
 
 using namespace pd;
 
 namespace {
 
-typedef float rsx16 __attribute__((ext_vector_type(16)));
 typedef float rsx4 __attribute__((ext_vector_type(4)));
 
 constexpr int RS_TF = 32;           // regrouped frames per block = the MFMA column tile
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(RS_NT) void resample_forward_kernel(const RsArgs a)
   // wave w takes the tiles t with (t + block) % RS_NW == w: when the tile count is no multiple of RS_NW, the wave
   // (hence the SIMD) with one tile more differs from block to block of a CU.  A tile's chain is the same whoever runs it.
   for (int tile = (wave + RS_NW - (int)(blockIdx.x % RS_NW)) % RS_NW; tile < p.ntile; tile += RS_NW) {
-    rsx16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int g = 0; g < 16; ++g) acc[g] = 0.f;
     // A = table rows (lane: phase tile * 32 + j, k half kh), B = frame j's samples (lane: frame j, k half kh).
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(RS_NT) void resample_forward_kernel(const RsArgs a)
     // register g of lane (kh, j): phase tile * 32 + 8 (g / 4) + 4 kh + g % 4 of frame j
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const int P = tile * 32 + 8 * (g >> 2) + 4 * kh + (g & 3);
+      const int P = tile * 32 + mfma_row(g, kh);
       if (P < N) ot[j * ns + P] = acc[g];
     }
   }

@@ -49,48 +49,13 @@ constexpr int GRU_ROWS = 16;        // batch rows per recurrence block: the M si
 constexpr int U_RMVPE_XPROJ = 30, U_RMVPE_HEAD = 31;
 
 // ------------------------------------------------------------------ create-time kernels
-// BN fold factor of channel co in double: gamma / sqrt(var + eps)
-__device__ __forceinline__ double bn_scale(const float* g, const float* var, int co) {
-  return (double)g[co] / sqrt((double)var[co] + 1e-5);
-}
-
-// dst[((ct * nchunk + chunk) * taps + tap) * 32 + n][16] = w(co = ct * 32 + n, ci = chunk * 16 + q, tap) * scale(co)
-// src is Conv2d's [Cout][Cin][taps], or (transposed) ConvTranspose2d's [Cin][Cout][taps] read with the taps flipped.
-__global__ __launch_bounds__(256) void pack_conv2d_kernel(float* __restrict__ dst, const float* __restrict__ src,
-                                                          const float* g, const float* var, int cout, int cin,
-                                                          int taps, int transposed, long long total) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int q = (int)(idx & 15), n = (int)((idx >> 4) & 31);
-  long long rest = idx >> 9;
-  const int tap = (int)(rest % taps);
-  rest /= taps;
-  const int nchunk = cin / CV_CK;
-  const int chunk = (int)(rest % nchunk), ct = (int)(rest / nchunk);
-  const int co = ct * 32 + n, ci = chunk * CV_CK + q;
-  float v = 0.f;
-  if (co < cout) {
-    const float w = transposed ? src[((long long)ci * cout + co) * taps + (taps - 1 - tap)]
-                               : src[((long long)co * cin + ci) * taps + tap];
-    v = g ? (float)((double)w * bn_scale(g, var, co)) : w;
-  }
-  dst[idx] = v;
-}
-
+// The 3x3 and 1x1 convs are packed by pack_conv_tiles and their BatchNorm's bias by fold_bn_bias (kernels.h).
 // dst[co][k] = src[co][k] * scale(co), k < per
 __global__ __launch_bounds__(256) void fold_rows_kernel(float* __restrict__ dst, const float* __restrict__ src,
                                                         const float* g, const float* var, int cout, int per) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= cout * per) return;
   dst[idx] = (float)((double)src[idx] * bn_scale(g, var, idx / per));
-}
-
-// dst[co] = beta - mean * scale(co)
-__global__ __launch_bounds__(256) void fold_bias_kernel(float* __restrict__ dst, const float* g, const float* beta,
-                                                        const float* mean, const float* var, int cout) {
-  const int co = blockIdx.x * 256 + threadIdx.x;
-  if (co >= cout) return;
-  dst[co] = (float)((double)beta[co] - (double)mean[co] * bn_scale(g, var, co));
 }
 
 // encoder.bn on the single input channel: dst = {scale, shift}
@@ -128,13 +93,6 @@ struct ConvArgs {
   int cout;
   int tc, tr, tiles_x; // tile columns and rows (tc * tr = 128), tiles per image row
 };
-
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 template <bool SC>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
@@ -203,7 +161,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
   const float bs = SC ? a.bsc[n] : 0.f;
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int mm = wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    const int mm = wave * 32 + mfma_row(reg, h);
     const int qr = mm / a.tc, qc = mm - qr * a.tc;
     const int gy = y0 + qr, gx = x0 + qc;
     if (gy >= a.H || gx >= a.W) continue;
@@ -467,9 +425,6 @@ struct Block {
   int cin = 0, cout = 0;
 };
 
-int ctiles(int cout) { return (cout + 31) / 32; }
-size_t packed_conv(int cin, int cout, int taps) { return (size_t)ctiles(cout) * (cin / CV_CK) * taps * 32 * 16; }
-
 bool dims_ok(const pd_rmvpe_dims& d) {
   if (d.n_gru != 0 && d.n_gru != 1) return false;
   if (d.n_blocks < 1 || d.n_blocks > 16 || d.inter_layers < 1 || d.inter_layers > 16) return false;
@@ -626,7 +581,7 @@ int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int d
   int p_first = -1;
   auto plan_convw = [&](ConvW& cw, int cin, int cout, bool transposed) {
     cw.cin = cin; cw.cout = cout;
-    wp.add(&cw.w, packed_conv(cin, cout, 9));
+    wp.add(&cw.w, packed_conv(cin, 0, cout, 9));
     wp.add(&cw.b, (size_t)ctiles(cout) * 32);
     convs.push_back({&cw, p, p + 1, transposed});
     p += 5;
@@ -648,7 +603,7 @@ int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int d
         wp.add(&h->ws_in, cout);
         wp.add(&h->bs_in, cout);
       } else {
-        wp.add(&bk.ws, packed_conv(cin, cout, 1));
+        wp.add(&bk.ws, packed_conv(cin, 0, cout, 1));
         wp.add(&bk.bs, (size_t)ctiles(cout) * 32);
         scs.push_back({&bk, p});
       }
@@ -697,29 +652,20 @@ int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int d
       hipLaunchKernelGGL(fold_rows_kernel, dim3(cdiv(c0 * 9, 256)), dim3(256), 0, st, h->w_in, params[q],
                          params[q + 1], params[q + 4], c0, 9);
       PD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(fold_bias_kernel, dim3(cdiv(c0, 256)), dim3(256), 0, st, h->b_in, params[q + 1],
-                         params[q + 2], params[q + 3], params[q + 4], c0);
-      PD_LAUNCH_CHECK();
+      PD_TRY(fold_bn_bias(h->b_in, params[q + 1], params[q + 2], params[q + 3], params[q + 4], c0, st));
       PD_TRY(copy_f32(h->ws_in, params[q + 10], c0, st));
       PD_TRY(copy_f32(h->bs_in, params[q + 11], c0, st));
     }
     for (const ConvJob& j : convs) {
       const ConvW& cw = *j.cw;
-      const long long total = (long long)packed_conv(cw.cin, cw.cout, 9);
       const float* const* bn = params + j.bn;   // weight, bias, running_mean, running_var
-      hipLaunchKernelGGL(pack_conv2d_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, cw.w, params[j.w], bn[0],
-                         bn[3], cw.cout, cw.cin, 9, j.transposed ? 1 : 0, total);
-      PD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(fold_bias_kernel, dim3(cdiv(cw.cout, 256)), dim3(256), 0, st, cw.b, bn[0], bn[1], bn[2],
-                         bn[3], cw.cout);
-      PD_LAUNCH_CHECK();
+      PD_TRY(pack_conv_tiles(cw.w, params[j.w], bn[0], bn[3], cw.cout, cw.cin, 0, 9,
+                             j.transposed ? TAPS_FLIPPED_T : TAPS_STORED, st));
+      PD_TRY(fold_bn_bias(cw.b, bn[0], bn[1], bn[2], bn[3], cw.cout, st));
     }
     for (const ScJob& j : scs) {
       const Block& bk = *j.bk;
-      const long long total = (long long)packed_conv(bk.cin, bk.cout, 1);
-      hipLaunchKernelGGL(pack_conv2d_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, bk.ws, params[j.w],
-                         (const float*)nullptr, (const float*)nullptr, bk.cout, bk.cin, 1, 0, total);
-      PD_LAUNCH_CHECK();
+      PD_TRY(pack_conv_tiles(bk.ws, params[j.w], nullptr, nullptr, bk.cout, bk.cin, 0, 1, TAPS_STORED, st));
       PD_TRY(copy_f32(bk.bs, params[j.w + 1], bk.cout, st));
     }
     PD_TRY(copy_f32(h->w_cnn, params[p_cnn], (size_t)3 * c0 * 9, st));

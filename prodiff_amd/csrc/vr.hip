@@ -37,60 +37,19 @@
 #include "../../include/prodiff_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "mfma_f32.h"
 
 using namespace pd;
 
 namespace {
-
-typedef float vrx16 __attribute__((ext_vector_type(16)));
 
 constexpr int VR_CK = 16;           // channels per K chunk
 constexpr int VR_MAX_HID = 64;      // LSTM hidden units per direction the recurrence kernel holds in registers
 constexpr int VR_MAX_NFFT = 16384;
 
 // ------------------------------------------------------------------ create-time kernels
-__device__ __forceinline__ double vr_bn_scale(const float* g, const float* var, int co) {
-  return (double)g[co] / sqrt((double)var[co] + 1e-5);
-}
-
-// dst[((ct * nchunk + chunk) * taps + tap) * 32 + n][16] = w(co = ct * 32 + n, ci, tap') * scale(co); the chunks run
-// over source 0's c0 channels, then source 1's c1, each padded to whole chunks with zeros.  src is Conv2d's
-// [Cout][c0 + c1][freq][time]; tap = 3 * (time tap) + (freq tap).
-__global__ __launch_bounds__(256) void vr_pack_conv_kernel(float* __restrict__ dst, const float* __restrict__ src,
-                                                           const float* g, const float* var, int cout, int c0, int c1,
-                                                           int taps, long long total) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int q = (int)(idx & 15), n = (int)((idx >> 4) & 31);
-  long long rest = idx >> 9;
-  const int tap = (int)(rest % taps);
-  rest /= taps;
-  const int nch0 = (c0 + VR_CK - 1) / VR_CK, nchunk = nch0 + (c1 + VR_CK - 1) / VR_CK;
-  const int chunk = (int)(rest % nchunk), ct = (int)(rest / nchunk);
-  const int co = ct * 32 + n;
-  int ci = -1;
-  if (chunk < nch0) {
-    if (chunk * VR_CK + q < c0) ci = chunk * VR_CK + q;
-  } else if ((chunk - nch0) * VR_CK + q < c1) {
-    ci = c0 + (chunk - nch0) * VR_CK + q;
-  }
-  float v = 0.f;
-  if (co < cout && ci >= 0) {
-    const int stap = taps == 9 ? (tap % 3) * 3 + tap / 3 : 0;
-    const float w = src[((long long)co * (c0 + c1) + ci) * taps + stap];
-    v = g ? (float)((double)w * vr_bn_scale(g, var, co)) : w;
-  }
-  dst[idx] = v;
-}
-
-// dst[co] = beta - mean * scale(co)
-__global__ __launch_bounds__(256) void vr_fold_bias_kernel(float* __restrict__ dst, const float* g, const float* beta,
-                                                           const float* mean, const float* var, int cout) {
-  const int co = blockIdx.x * 256 + threadIdx.x;
-  if (co >= cout) return;
-  dst[co] = (float)((double)beta[co] - (double)mean[co] * vr_bn_scale(g, var, co));
-}
-
+// The convs are packed by pack_conv_tiles (kernels.h) with TAPS_SWAPPED: src is Conv2d's [Cout][c0 + c1][freq][time],
+// the kernel's tap = 3 * (time tap) + (freq tap); their BatchNorm's bias comes from fold_bn_bias.
 // dst[k * ldn + col + n] = src[n][k] (* scale(n)): a Linear's weight, input-major
 __global__ __launch_bounds__(256) void vr_pack_linear_kernel(float* __restrict__ dst, const float* __restrict__ src,
                                                              const float* g, const float* var, int N, int K, int ldn,
@@ -99,7 +58,7 @@ __global__ __launch_bounds__(256) void vr_pack_linear_kernel(float* __restrict__
   if (idx >= N * K) return;
   const int n = idx / K, k = idx - n * K;
   const float w = src[idx];
-  dst[(long long)k * ldn + col + n] = g ? (float)((double)w * vr_bn_scale(g, var, n)) : w;
+  dst[(long long)k * ldn + col + n] = g ? (float)((double)w * bn_scale(g, var, n)) : w;
 }
 
 // Linear bias through BatchNorm1d: dst[n] = (b[n] - mean[n]) * scale(n) + beta[n]
@@ -108,7 +67,7 @@ __global__ __launch_bounds__(256) void vr_dense_bias_kernel(float* __restrict__ 
                                                             int N) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  dst[n] = (float)(((double)b[n] - (double)mean[n]) * vr_bn_scale(g, var, n) + (double)beta[n]);
+  dst[n] = (float)(((double)b[n] - (double)mean[n]) * bn_scale(g, var, n) + (double)beta[n]);
 }
 
 // Tables from the exactly reduced phase (n k) mod n_fft, in double, rounded once.  w = the caller's window (the
@@ -123,13 +82,12 @@ __global__ __launch_bounds__(256) void vr_table_kernel(float* __restrict__ fc, f
                                                        float* __restrict__ win, const float* __restrict__ window,
                                                        int nf, int nb, int nbp, int nbk) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  const double two_pi = 6.283185307179586476925286766559;
   if (idx < (long long)nf * nbp) {
     const int n = (int)(idx / nbp), k = (int)(idx - (long long)n * nbp);
     float c = 0.f, s = 0.f;
     if (k < nb) {
       const double w = (double)window[n];
-      const double ph = two_pi * (double)(((long long)n * k) % nf) / (double)nf;
+      const double ph = dft_phase(n, k, nf);
       c = (float)(w * cos(ph));
       s = (float)(-w * sin(ph));
     }
@@ -141,7 +99,7 @@ __global__ __launch_bounds__(256) void vr_table_kernel(float* __restrict__ fc, f
     float c = 0.f, s = 0.f;
     if (k < nb) {
       const double w = (double)window[n];
-      const double ph = two_pi * (double)(((long long)n * k) % nf) / (double)nf;
+      const double ph = dft_phase(n, k, nf);
       const bool edge = k == 0 || 2 * k == nf;
       const double ck = edge ? 1.0 : 2.0;
       c = (float)(w * ck * cos(ph) / (double)nf);
@@ -178,17 +136,10 @@ struct VrConvArgs {
   int oys, oxs, cout;
 };
 
-__device__ __forceinline__ void vr_load8(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
 // channels cb .. cb + 7 of one stored pixel, zero from channel s.c on
 __device__ __forceinline__ void vr_pixel8(const VrSrc& s, const float* px, int cb, float (&v)[8]) {
   if (s.vec && cb + 8 <= s.c) {
-    vr_load8(px + cb, v);
+    load8(px + cb, v);
   } else {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = cb + i < s.c ? px[cb + i] : 0.f;
@@ -223,7 +174,7 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
   for (int i = 0; i < NT; ++i)
     wrow[i] = a.wp + ((long long)min(ct0 + i, ctl) * nchunk * TAPS * 32 + r) * 16 + h * 8;
 
-  vrx16 acc[NT];
+  f32x16 acc[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -246,7 +197,7 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
           const int tap = tr * TR + tc;
           float wf[NT][8], af[8];
 #pragma unroll
-          for (int i = 0; i < NT; ++i) vr_load8(wrow[i] + wo + tap * 512, wf[i]);
+          for (int i = 0; i < NT; ++i) load8(wrow[i] + wo + tap * 512, wf[i]);
           const int iy = y * a.stride + (TAPS == 9 ? tr - 1 : 0) * a.dy, ix = x * a.stride + (TAPS == 9 ? tc - 1 : 0) * a.dx;
           const bool ok = iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi;
           const int cy = min(max(iy, 0), a.Hi - 1), cx = min(max(ix, 0), a.Wi - 1);
@@ -292,7 +243,7 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
     float* ob = a.out + (long long)b * a.obs + n;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int pp = p0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+      const int pp = p0 + mfma_row(reg, h);
       if (pp >= npix) continue;
       const int qy = pp / a.W, qx = pp - qy * a.W;
       float v = acc[i][reg] + bv;
@@ -412,20 +363,6 @@ __global__ __launch_bounds__(256) void vr_lstm_kernel(const float* __restrict__ 
   }
 }
 
-// One chunk's sums into the running totals, compensated (Knuth's TwoSum; mel.hip's mel_fold, DESIGN.md mel analysis)
-__device__ __forceinline__ void vr_fold(vrx16& acc, vrx16& hi, vrx16& lo) {
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    const float a = acc[g], h = hi[g];
-    const float s = h + a;
-    const float bb = s - h;
-    const float err = (h - (s - bb)) + (a - bb);
-    hi[g] = s;
-    lo[g] += err;
-    acc[g] = 0.f;
-  }
-}
-
 struct VrStftArgs {
   const float* wav;   // [rows][L]
   const float* fc;    // [n_fft][nbp]
@@ -447,7 +384,7 @@ __global__ __launch_bounds__(256) void vr_stft_kernel(const VrStftArgs a) {
   const long long s0 = (long long)t * a.hop - a.lead + kh;
   const float* pc = a.fc + (long long)kh * a.nbp + col0 + j;
   const float* ps = a.fs + (long long)kh * a.nbp + col0 + j;
-  vrx16 re, im, re_hi, im_hi, re_lo, im_lo;
+  f32x16 re, im, re_hi, im_hi, re_lo, im_lo;
 #pragma unroll
   for (int g = 0; g < 16; ++g) { re[g] = im[g] = re_hi[g] = im_hi[g] = re_lo[g] = im_lo[g] = 0.f; }
   for (int n0 = 0; n0 < a.nf; n0 += 16) {
@@ -466,8 +403,8 @@ __global__ __launch_bounds__(256) void vr_stft_kernel(const VrStftArgs a) {
       re = __builtin_amdgcn_mfma_f32_32x32x2f32(c[u], y[u], re, 0, 0, 0);
       im = __builtin_amdgcn_mfma_f32_32x32x2f32(sn[u], y[u], im, 0, 0, 0);
     }
-    vr_fold(re, re_hi, re_lo);
-    vr_fold(im, im_hi, im_lo);
+    mfma_fold(re, re_hi, re_lo);
+    mfma_fold(im, im_hi, im_lo);
   }
   if (t >= a.T) return;
   // register g of lane (kh, j): bin col0 + 8 (g / 4) + 4 kh + g % 4 of frame j
@@ -475,7 +412,7 @@ __global__ __launch_bounds__(256) void vr_stft_kernel(const VrStftArgs a) {
   float* oim = a.im + (row * a.T + t) * a.nb;
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
-    const int col = col0 + 8 * (g >> 2) + 4 * kh + (g & 3);
+    const int col = col0 + mfma_row(g, kh);
     if (col < a.nb) {
       ore[col] = re_hi[g] + re_lo[g];
       oim[col] = im_hi[g] + im_lo[g];
@@ -510,7 +447,7 @@ __global__ __launch_bounds__(256) void vr_istft_kernel(const VrIstftArgs a) {
   const int rb = min(r0 + j, a.hop - 1);   // B column of this lane (columns past the hop are never written)
   const long long row = blockIdx.z;
   const long long sbase = row * a.T * a.nb;
-  vrx16 acc, hi, lo;
+  f32x16 acc, hi, lo;
 #pragma unroll
   for (int g = 0; g < 16; ++g) { acc[g] = hi[g] = lo[g] = 0.f; }
   for (int q = 0; q < a.R; ++q) {
@@ -543,7 +480,7 @@ __global__ __launch_bounds__(256) void vr_istft_kernel(const VrIstftArgs a) {
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[u], tc[u], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ai[u], ts[u], acc, 0, 0, 0);
       }
-      vr_fold(acc, hi, lo);
+      mfma_fold(acc, hi, lo);
     }
   }
   // D: column (sample r0 + j) = lane & 31, row (segment) = (g & 3) + 8 (g >> 2) + 4 kh
@@ -551,7 +488,7 @@ __global__ __launch_bounds__(256) void vr_istft_kernel(const VrIstftArgs a) {
   if (rr >= a.hop) return;
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
-    const int sl = st0 + (g & 3) + 8 * (g >> 2) + 4 * kh;
+    const int sl = st0 + mfma_row(g, kh);
     if (sl >= a.nseg) continue;
     const int sg = a.seg0 + sl;
     const long long i = (long long)sg * a.hop + rr - a.lead;
@@ -582,10 +519,6 @@ struct Net {
   bool has_tail = false;
   float *wih = nullptr, *bl = nullptr, *whh = nullptr, *wd = nullptr, *bd = nullptr;
 };
-
-int ctiles(int cout) { return (cout + 31) / 32; }
-int nchunks(int c) { return (c + VR_CK - 1) / VR_CK; }
-size_t packed_conv(const Conv& c) { return (size_t)ctiles(c.cout) * (nchunks(c.c0) + nchunks(c.c1)) * c.taps * 512; }
 
 bool dims_ok(const pd_vr_dims& d) {
   if (d.is_mono != 0 && d.is_mono != 1) return false;
@@ -920,7 +853,7 @@ int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, 
   int p = 0;
   auto plan_conv = [&](Conv& cw, int c0, int c1, int cout, int taps, bool bn) {
     cw.c0 = c0; cw.c1 = c1; cw.cout = cout; cw.taps = taps;
-    wp.add(&cw.w, packed_conv(cw));
+    wp.add(&cw.w, packed_conv(c0, c1, cout, taps));
     wp.add(&cw.b, (size_t)ctiles(cout) * 32);
     convs.push_back({&cw, p, bn});
     p += bn ? 5 : 1;
@@ -974,17 +907,10 @@ int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, 
     PD_TRY(wp.commit(st, "vr"));
     for (const ConvJob& j : convs) {
       const Conv& cw = *j.cw;
-      const long long total = (long long)packed_conv(cw);
       const float* const* bn = params + j.w + 1;   // weight, bias, running_mean, running_var
-      hipLaunchKernelGGL(vr_pack_conv_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, cw.w, params[j.w],
-                         j.bn ? bn[0] : (const float*)nullptr, j.bn ? bn[3] : (const float*)nullptr, cw.cout, cw.c0,
-                         cw.c1, cw.taps, total);
-      PD_LAUNCH_CHECK();
-      if (j.bn) {
-        hipLaunchKernelGGL(vr_fold_bias_kernel, dim3(cdiv(cw.cout, 256)), dim3(256), 0, st, cw.b, bn[0], bn[1], bn[2],
-                           bn[3], cw.cout);
-        PD_LAUNCH_CHECK();
-      }
+      PD_TRY(pack_conv_tiles(cw.w, params[j.w], j.bn ? bn[0] : nullptr, j.bn ? bn[3] : nullptr, cw.cout, cw.c0, cw.c1,
+                             cw.taps, TAPS_SWAPPED, st));
+      if (j.bn) PD_TRY(fold_bn_bias(cw.b, bn[0], bn[1], bn[2], bn[3], cw.cout, st));
     }
     for (const LstmJob& j : lstms) {
       const Net& nt = *j.nt;

@@ -9,8 +9,6 @@ Every function takes the reference's numpy arrays and returns numpy, or takes CU
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -101,13 +99,6 @@ class SinusoidalSmoothingConv1d:
     forward = __call__
 
 
-class _CurvesHandle(_lib.NativeHandle):
-    """pd_curves_create takes the dimensions alone (no parameter list, no dtype)."""
-
-    def _call_create(self, create, dims, tensors, stream, h):
-        return create(C.byref(dims), stream, C.byref(h))
-
-
 class _Core:
     """One (samplerate, win_size, hop_size, half_width): its native handles (one per device) and workspace."""
 
@@ -117,25 +108,16 @@ class _Core:
         if self.samplerate < 1:
             raise _lib.HipError(f"samplerate must be positive, got {samplerate}")
         check_dims(self.win_size, self.hop_size, self.half_width)
-        self.handles = {}
+        self._cache = _lib.HandleCache("variance curves", "pd_curves_create", "pd_curves_destroy")
+        self.handles = self._cache.handles
         self._ws = _lib.Workspace()
 
     def handle(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.HipError("the variance curves run on the GPU (got a CPU tensor; there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        nh = self.handles.get(str(device))
-        if nh is None:
-            nh = self.handles[str(device)] = _CurvesHandle("curves", "pd_curves_create", "pd_curves_destroy")
         dims = _lib.pd_curves_dims(self.samplerate, self.win_size, self.hop_size, self.half_width)
-        return nh.get(str(device), lambda: (dims, []), device)
+        return self._cache.get(device, (), lambda device: (dims, []))
 
     def close(self):
-        for nh in self.handles.values():
-            nh.close()
-        self.handles.clear()
+        self._cache.close()
 
     def _rows(self, wav, name="waveform"):
         if wav.dim() not in (1, 2):

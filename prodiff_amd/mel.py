@@ -4,8 +4,6 @@ its defaults (nvSTFT.py:70), restated here so that no librosa is needed.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -63,14 +61,7 @@ def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None, htk=False):
     return mel_filterbank64(sr, n_fft, n_mels, fmin, fmax, htk).astype(np.float32)
 
 
-# ---------------------------------------------------------------- native handle
-class _MelHandle(_lib.NativeHandle):
-    """pd_mel_create takes the basis alone (no parameter list, no dtype)."""
-
-    def _call_create(self, create, dims, tensors, stream, h):
-        return create(C.byref(dims), _lib.fptr(tensors[0]), stream, C.byref(h))
-
-
+# ---------------------------------------------------------------- native front end
 def derived_sizes(n_fft, win_size, hop_length, keyshift=0, speed=1):
     """(nf, wn, hn): frame, window and hop in samples (nvSTFT.py:58-61)."""
     factor = 2 ** (keyshift / 12)
@@ -83,7 +74,60 @@ def num_frames(n_samples, n_fft, win_size, hop_length, keyshift=0, speed=1):
     return 1 + (n_samples + wn - hn - nf) // hn
 
 
-class STFT:
+class MelFrontEnd:
+    """What ``STFT`` and ``rmvpe.MelSpectrogram`` share: the filterbank on each device, up to eight pd_mel handles
+    in total (one per key shift, speed and device, oldest out first) and the pd_mel_forward call.  A subclass names
+    its create function and states its minimum-length rule (``_min_samples``)."""
+
+    def _setup(self, name, create, basis, n_fft, win_size, hop_length, clip_val):
+        self._sizes = (n_fft, win_size, hop_length, basis.shape[0])
+        self._clip = float(clip_val)
+        self.mel_basis_host = torch.from_numpy(np.ascontiguousarray(basis))
+        self.mel_basis = {}      # device -> tensor
+        self._cache = _lib.HandleCache(name, create, "pd_mel_destroy", limit=8)   # like the reference's window / basis dicts
+        self.handles = self._cache.handles      # (keyshift, speed, device) -> NativeHandle
+
+    def handle(self, keyshift, speed, device):
+        def build(device):
+            basis = self.mel_basis.get(str(device))
+            if basis is None:
+                basis = self.mel_basis[str(device)] = self.mel_basis_host.to(device)
+            return _lib.pd_mel_dims(*self._sizes, float(keyshift), float(speed), self._clip), [basis]
+        return self._cache.get(device, (float(keyshift), float(speed)), build)
+
+    def close(self):
+        self._cache.close()
+
+    def _min_samples(self, keyshift, speed):
+        """(shortest legal signal, what needs it: the tail of the error text)."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def _mel_time_major(self, y, keyshift, speed, lens=None, out_scale=1.0, return_spec=False):
+        if y.dim() == 1:
+            y = y[None]
+        y = y.float().contiguous()
+        B, L = y.shape
+        need, why = self._min_samples(keyshift, speed)
+        if L < need:
+            raise ValueError(f"signal of {L} samples is too short: {why} at least {need}")
+        dev = y.device
+        h = self.handle(keyshift, speed, dev)
+        lib = _lib.lib()
+        T = lib.pd_mel_frames(h, L)
+        ln = None
+        if lens is not None:
+            ln = _lib._device_rows(lens, B, dev, "lens", need, L)
+        n_mels, n_bins = self.mel_basis_host.shape
+        out = torch.empty(B, T, n_mels, device=dev, dtype=torch.float32)
+        spec = torch.empty(B, T, n_bins, device=dev, dtype=torch.float32) if return_spec else None
+        # pd_mel_workspace_size is 0: the kernel keeps everything in LDS and registers
+        _lib.check(lib.pd_mel_forward(h, _lib.fptr(y), _lib.iptr(ln), float(out_scale), _lib.fptr(out), _lib.fptr(spec),
+                                      B, L, None, 0, _lib.stream_ptr(dev)))
+        return (out, spec) if return_spec else out
+
+
+class STFT(MelFrontEnd):
     """nvSTFT.py:33-98.  ``get_mel`` returns the reference's [B, n_mels, T]: a transposed view of the
     native time-major output, which ``get_mel_time_major`` returns as it is.  ``mel_basis`` (float
     [n_mels, n_fft // 2 + 1]) replaces the built-in Slaney filterbank, e.g. by librosa's own."""
@@ -96,67 +140,22 @@ class STFT:
         basis = mel_filterbank(sr, n_fft, n_mels, fmin, fmax) if mel_basis is None else np.asarray(mel_basis, np.float32)
         if basis.shape != (n_mels, n_fft // 2 + 1):
             raise ValueError(f"mel_basis must be [{n_mels}, {n_fft // 2 + 1}], got {basis.shape}")
-        self.mel_basis_host = torch.from_numpy(np.ascontiguousarray(basis))
-        self.mel_basis = {}      # device -> tensor
-        self.handles = {}        # (keyshift, speed, device) -> _MelHandle
-
-    def _dims(self, keyshift, speed):
-        return _lib.pd_mel_dims(self.n_fft, self.win_size, self.hop_length, self.n_mels, float(keyshift), float(speed),
-                                float(self.clip_val))
-
-    def handle(self, keyshift, speed, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.HipError("STFT.get_mel runs on the GPU (got a CPU tensor; there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        key = (float(keyshift), float(speed), str(device))
-        nh = self.handles.get(key)
-        if nh is None:
-            if len(self.handles) >= 8:     # a small cache, like the reference's window / basis dicts
-                self.handles.pop(next(iter(self.handles))).close()
-            nh = self.handles[key] = _MelHandle("STFT", "pd_mel_create", "pd_mel_destroy")
-        basis = self.mel_basis.get(str(device))
-        if basis is None:
-            basis = self.mel_basis[str(device)] = self.mel_basis_host.to(device)
-        return nh.get(key, lambda: (self._dims(keyshift, speed), [basis]))
-
-    def close(self):
-        for nh in self.handles.values():
-            nh.close()
-        self.handles.clear()
+        self._setup("STFT.get_mel", "pd_mel_create", basis, n_fft, win_size, hop_length, clip_val)
 
     def min_samples(self, keyshift=0, speed=1):
         nf, wn, hn = derived_sizes(self.n_fft, self.win_size, self.hop_length, keyshift, speed)
         return max((wn - hn + 1) // 2 + 1, nf - wn + hn)
 
-    @torch.no_grad()
+    def _min_samples(self, keyshift, speed):
+        return self.min_samples(keyshift, speed), f"keyshift {keyshift}, speed {speed} need"
+
     def get_mel_time_major(self, y, keyshift=0, speed=1, center=False, lens=None, out_scale=1.0, return_spec=False):
         """y [B, L] (or [L]) on the GPU -> natural-log mel [B, T, n_mels] times ``out_scale``; with
         ``return_spec`` also the magnitude spectrum [B, T, n_fft // 2 + 1].  ``lens``: samples per row of a
         ragged batch (frames past a row's own count are unspecified)."""
         if center:
             raise NotImplementedError("center=True is not offered (the reference's callers use center=False)")
-        if y.dim() == 1:
-            y = y[None]
-        y = y.float().contiguous()
-        B, L = y.shape
-        need = self.min_samples(keyshift, speed)
-        if L < need:
-            raise ValueError(f"signal of {L} samples is too short: keyshift {keyshift}, speed {speed} need at least {need}")
-        dev = y.device
-        h = self.handle(keyshift, speed, dev)
-        lib = _lib.lib()
-        T = lib.pd_mel_frames(h, L)
-        ln = None
-        if lens is not None:
-            ln = _lib._device_rows(lens, B, dev, "lens", need, L)
-        out = torch.empty(B, T, self.n_mels, device=dev, dtype=torch.float32)
-        spec = torch.empty(B, T, self.n_fft // 2 + 1, device=dev, dtype=torch.float32) if return_spec else None
-        # pd_mel_workspace_size is 0: the kernel keeps everything in LDS and registers
-        _lib.check(lib.pd_mel_forward(h, _lib.fptr(y), _lib.iptr(ln), float(out_scale), _lib.fptr(out), _lib.fptr(spec),
-                                      B, L, None, 0, _lib.stream_ptr(dev)))
-        return (out, spec) if return_spec else out
+        return self._mel_time_major(y, keyshift, speed, lens, out_scale, return_spec)
 
     def get_mel(self, y, keyshift=0, speed=1, center=False, lens=None):
         """nvSTFT.py:48-98: y [B, L] -> [B, n_mels, T] natural-log mel."""

@@ -49,13 +49,6 @@ def sinc_resample_kernel64(orig, new, lowpass_filter_width=6, rolloff=0.99, resa
     return h, W, o, n
 
 
-class _ResampleHandle(_lib.NativeHandle):
-    """pd_resample_create takes the dims alone (no parameter list, no dtype)."""
-
-    def _call_create(self, create, dims, tensors, stream, h):
-        return create(C.byref(dims), stream, C.byref(h))
-
-
 class Resample:
     """``torchaudio.transforms.Resample``: ``Resample(orig, new)(waveform[..., L]) -> [..., ceil(new L / orig)]``
     on the GPU (a CPU tensor raises: there is no CPU fallback).  Equal rates return the input unchanged.
@@ -75,28 +68,18 @@ class Resample:
         g = math.gcd(self.orig_freq, self.new_freq)
         self.o, self.n = self.orig_freq // g, self.new_freq // g
         self.width = int(math.ceil(self.lowpass_filter_width * self.o / (min(self.o, self.n) * self.rolloff)))
-        self.handles = {}        # device -> _ResampleHandle
+        self._cache = _lib.HandleCache("Resample", "pd_resample_create", "pd_resample_destroy")
+        self.handles = self._cache.handles        # (device,) -> NativeHandle
 
     def _dims(self):
         return _lib.pd_resample_dims(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff,
                                      METHODS[self.resampling_method], DEFAULT_BETA if self.beta is None else float(self.beta))
 
     def handle(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.HipError("Resample runs on the GPU (got a CPU tensor; there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        nh = self.handles.get(str(device))
-        if nh is None:
-            nh = self.handles[str(device)] = _ResampleHandle("Resample", "pd_resample_create", "pd_resample_destroy")
-        with torch.cuda.device(device):
-            return nh.get(str(device), lambda: (self._dims(), []), device=device)
+        return self._cache.get(device, (), lambda device: (self._dims(), []))
 
     def close(self):
-        for nh in self.handles.values():
-            nh.close()
-        self.handles.clear()
+        self._cache.close()
 
     def out_samples(self, n_samples):
         return -(-self.n * int(n_samples) // self.o)

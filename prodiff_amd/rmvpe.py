@@ -4,14 +4,12 @@
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib, synth
-from .mel import _MelHandle, derived_sizes, mel_filterbank
+from .mel import MelFrontEnd, derived_sizes, mel_filterbank
 from .resample import Resample
 
 SAMPLE_RATE, N_CLASS, N_MELS = 16000, synth.RMVPE_N_CLASS, synth.RMVPE_N_MELS      # modules/rmvpe/constants.py
@@ -135,7 +133,7 @@ def to_local_average_f0(hidden, center=None, thred=0.03):
 
 
 # ---------------------------------------------------------------- front end
-class MelSpectrogram:
+class MelSpectrogram(MelFrontEnd):
     """modules/rmvpe/spec.py: the HTK-scale log-mel of ``torch.stft(center=True)`` on the centred pd_mel.
     ``forward`` returns the reference's [B, n_mels, T] (a transposed view of the time-major native output,
     which ``forward_time_major`` returns as it is); T = 1 + L // hop."""
@@ -145,57 +143,20 @@ class MelSpectrogram:
         self.n_fft = win_length if n_fft is None else n_fft
         self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
         self.win_length, self.hop_length, self.clamp = win_length, hop_length, clamp
-        self.mel_basis_host = torch.from_numpy(mel_filterbank(sampling_rate, self.n_fft, n_mel_channels, mel_fmin, mel_fmax,
-                                                              htk=True))
-        self.mel_basis = {}
-        self.handles = {}
+        basis = mel_filterbank(sampling_rate, self.n_fft, n_mel_channels, mel_fmin, mel_fmax, htk=True)
+        self._setup("MelSpectrogram", "pd_mel_create_centered", basis, self.n_fft, win_length, hop_length, clamp)
 
     def to(self, device):
         return self
 
-    def handle(self, keyshift, speed, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.HipError("MelSpectrogram runs on the GPU (got a CPU tensor; there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        key = (float(keyshift), float(speed), str(device))
-        nh = self.handles.get(key)
-        if nh is None:
-            if len(self.handles) >= 8:
-                self.handles.pop(next(iter(self.handles))).close()
-            nh = self.handles[key] = _MelHandle("MelSpectrogram", "pd_mel_create_centered", "pd_mel_destroy")
-        basis = self.mel_basis.get(str(device))
-        if basis is None:
-            basis = self.mel_basis[str(device)] = self.mel_basis_host.to(device)
-        dims = _lib.pd_mel_dims(self.n_fft, self.win_length, self.hop_length, self.n_mel_channels, float(keyshift),
-                                float(speed), float(self.clamp))
-        return nh.get(key, lambda: (dims, [basis]))
+    def _min_samples(self, keyshift, speed):
+        nf = derived_sizes(self.n_fft, self.win_length, self.hop_length, keyshift, speed)[0]
+        return nf // 2 + 1, "reflect padding needs"
 
-    def close(self):
-        for nh in self.handles.values():
-            nh.close()
-        self.handles.clear()
-
-    @torch.no_grad()
     def forward_time_major(self, audio, keyshift=0, speed=1, center=True, return_spec=False):
         if not center:
             raise NotImplementedError("center=False is prodiff_amd.mel.STFT's framing")
-        if audio.dim() == 1:
-            audio = audio[None]
-        y = audio.float().contiguous()
-        B, L = y.shape
-        nf = derived_sizes(self.n_fft, self.win_length, self.hop_length, keyshift, speed)[0]
-        if L < nf // 2 + 1:
-            raise ValueError(f"signal of {L} samples is too short: reflect padding needs at least {nf // 2 + 1}")
-        h = self.handle(keyshift, speed, y.device)
-        lib = _lib.lib()
-        T = lib.pd_mel_frames(h, L)
-        out = torch.empty(B, T, self.n_mel_channels, device=y.device, dtype=torch.float32)
-        spec = torch.empty(B, T, self.n_fft // 2 + 1, device=y.device, dtype=torch.float32) if return_spec else None
-        _lib.check(lib.pd_mel_forward(h, _lib.fptr(y), None, 1.0, _lib.fptr(out), _lib.fptr(spec), B, L, None, 0,
-                                      _lib.stream_ptr(y.device)))
-        return (out, spec) if return_spec else out
+        return self._mel_time_major(audio, keyshift, speed, return_spec=return_spec)
 
     def forward(self, audio, keyshift=0, speed=1, center=True):
         return self.forward_time_major(audio, keyshift, speed, center).transpose(1, 2)

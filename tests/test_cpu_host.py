@@ -447,3 +447,58 @@ def test_cpu_parameters_fail_loudly_in_handle():
     for name, m, handle in _four_modules():
         with pytest.raises(_lib.HipError, match=f"{name} parameters must live on the GPU"):
             handle()
+
+
+class _StubHandle:
+    """What HandleCache asks of a NativeHandle: get(signature, build, device) and close()."""
+
+    def __init__(self):
+        self.closed = 0
+
+    def get(self, signature, build, device=None):
+        self.signature, self.built, self.device = signature, build(), device
+        return ("handle", signature)
+
+    def close(self):
+        self.closed += 1
+
+
+def test_handle_cache_normalises_evicts_and_closes(monkeypatch):
+    """_lib.HandleCache without a device: a CPU device is refused, two spellings of one device share an
+    entry, the ninth key of a cache of eight closes exactly the oldest entry, close() closes the rest."""
+    import contextlib
+    monkeypatch.setattr(torch.cuda, "device", lambda device: contextlib.nullcontext())   # nothing to switch to here
+    made = []
+
+    def new():
+        made.append(_StubHandle())
+        return made[-1]
+
+    cache = _lib.HandleCache("stub front end", "no_create", "no_destroy", limit=8)
+    cache._new = new
+    build = lambda device: (device, [])   # noqa: E731
+    for cpu in ("cpu", torch.device("cpu")):
+        with pytest.raises(_lib.HipError, match="stub front end.*no CPU fallback"):
+            cache.get(cpu, (0.0, 1.0), build)
+    assert not made and not cache.handles
+    a = cache.get("cuda:0", (0.0, 1.0), build)
+    assert cache.get(torch.device("cuda", 0), (0.0, 1.0), build) == a
+    assert len(made) == 1 and list(cache.handles) == [(0.0, 1.0, "cuda:0")]
+    assert made[0].built == (torch.device("cuda", 0), []) and made[0].device == torch.device("cuda", 0)
+    assert made[0].signature == (0.0, 1.0, "cuda:0")
+    cache.get("cuda:1", (0.0, 1.0), build)               # another device is another entry
+    for k in range(2, 8):
+        cache.get("cuda:0", (float(k), 1.0), build)
+    assert len(cache.handles) == 8 and len(made) == 8 and not any(s.closed for s in made)
+    cache.get("cuda:0", (8.0, 1.0), build)               # the ninth key
+    assert len(cache.handles) == 8 and len(made) == 9
+    assert [s.closed for s in made] == [1] + [0] * 8
+    assert (0.0, 1.0, "cuda:0") not in cache.handles and (0.0, 1.0, "cuda:1") in cache.handles
+    cache.close()
+    assert [s.closed for s in made] == [1] * 9 and not cache.handles
+
+    unlimited = _lib.HandleCache("stub front end", "no_create", "no_destroy")
+    unlimited._new = new
+    for k in range(12):
+        unlimited.get("cuda:0", (k,), build)
+    assert len(unlimited.handles) == 12 and not any(s.closed for s in made[9:])

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from prodiff_amd import STFT, _lib
+from prodiff_amd.mel import num_frames as mel_frames
 from prodiff_amd.nsf_hifigan import NsfHifiGAN
 from tests import mel_ref as R
 
@@ -168,6 +169,27 @@ def test_handles_are_per_key_shift_and_speed_and_freed():
     assert len({nh.h.value for nh in s.handles.values()}) == 2
     assert torch.equal(s.get_mel(wav), a) and lib.pd_live_device_bytes() == two      # the first handle is reused
     assert a.shape[2] != b.shape[2]
+    s.close()
+    assert lib.pd_live_device_bytes() == start and not s.handles
+
+
+def test_eviction_frees_the_evicted_handle():
+    """Nine speeds on an STFT that keeps eight handles: the ninth create closes the oldest handle, so the live
+    device bytes stay where they were after the eighth (every pool is the same size: the tables depend on n_fft
+    and n_mels only)."""
+    lib = _lib.lib()
+    torch.cuda.synchronize()
+    start = lib.pd_live_device_bytes()
+    s = STFT(sr=22050, n_mels=8, n_fft=64, win_size=64, hop_length=16, fmin=0, fmax=11025)
+    wav = cuda(R.make_signal("noise", 400, 22050, 7)[None])
+    live = []
+    for k in range(16, 25):                     # hops 16 .. 24
+        assert s.get_mel(wav, speed=k / 16).shape[2] == mel_frames(400, 64, 64, 16, 0, k / 16)
+        live.append(lib.pd_live_device_bytes())
+    per = live[0] - start
+    assert per > 0 and live[:8] == [start + (i + 1) * per for i in range(8)]
+    assert live[8] == live[7] and len(s.handles) == 8
+    assert (0.0, 1.0, str(wav.device)) not in s.handles and (0.0, 17 / 16, str(wav.device)) in s.handles
     s.close()
     assert lib.pd_live_device_bytes() == start and not s.handles
 
