@@ -748,6 +748,49 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
 int pd_rmvpe_decode(const float* hidden, float* f0, int B, int T, int n_class, float thred, const long long* center,
                     double cents_const, void* stream);
 
+/* to_viterbi_f0's path (modules/rmvpe/utils.py:26-43: librosa.sequence.viterbi over the salience with a banded
+ * transition) for each row of hidden [B][T][n_class] (float32 >= 0).  In double throughout:
+ *   p[t][j] = h[t][j] / sum_j h[t][j]  (a frame whose sum is not positive counts as uniform, p = 1 / n_class; the
+ *   reference yields NaN there),  lp = log(p + tiny), tiny = FLT_MIN;
+ *   val[0][j] = lp[0][j] + log_init;  val[t][j] = lp[t][j] + max_i (val[t-1][i] + lt[i][j]),  ptr[t][j] = the lowest
+ *   i attaining the max;  path[T-1] = the lowest argmax_j val[T-1][j],  path[t] = ptr[t+1][path[t+1]];
+ *   logp[b] = val[T-1][path[T-1]] (librosa's return_logp), or logp = NULL.
+ * lt[i][j] = log_band[i][j - i + width - 1] for |i - j| < width and log_off outside the band; log_off must lie
+ * below every in-band entry by more than the spread of val that one frame's lp can make up (the caller's tables,
+ * log(A + tiny) of A[i][j] = max(width - |i - j|, 0) row-normalised, do: the band holds values >= -6.9, log_off is
+ * -87.3): the kernel evaluates the band and one out-of-band candidate, the lowest global argmax of val[t-1], which
+ * under that condition equals the dense maximum and its lowest argmax exactly.  The reference normalises p in
+ * float32; this entry point does it in double.
+ * n_class <= 512 and width <= 64 (PD_ERR_UNSUPPORTED beyond; widths above 30 read the band from memory instead of
+ * registers).  Back pointers are resolved in chunks of PD_RMVPE_VITERBI_CHUNK frames (pd_rmvpe_viterbi_chunk
+ * returns the library's value).  Two launches, stream-ordered, no allocation, no synchronisation, capturable; a row
+ * depends neither on B nor on its batch position.  The workspace holds lp [B][T][n_class] double, the chunk walks'
+ * states [B][T][n_class] uint16 and chunk maps; its last 16 bytes receive two shader-cycle counts of row 0 (the
+ * recurrence kernel, its backtrace parts) that tools/bench_pitch_tail.py reads and nothing else does. */
+#define PD_RMVPE_VITERBI_CHUNK 32
+int pd_rmvpe_viterbi_chunk(void);
+size_t pd_rmvpe_viterbi_workspace_size(int B, int T, int n_class, int width);
+int pd_rmvpe_viterbi(const float* hidden,      /* [B][T][n_class], device                            */
+                     const double* log_band,   /* [n_class][2*width-1]: lt[i][j], column j-i+width-1 */
+                     double log_off,           /* lt outside the band                                */
+                     double log_init,          /* log of the initial state probability               */
+                     long long* path,          /* [B][T], device                                     */
+                     double* logp,             /* [B] or NULL                                        */
+                     int B, int T, int n_class, int width, void* workspace, size_t ws_bytes, void* stream);
+
+/* The f0 curve on another frame grid (component/pe/rmvpe.py:57-72: interp_f0, then resample_align_curve of the
+ * curve and of its unvoiced flags, utils/pitch_utils.py:45-51, 86-98) for each row of f0 [B][n]:
+ *   uv = f0 == 0; unvoiced frames take the linear interpolation of float32 log2 f0 between the neighbouring voiced
+ *   frames (the first / last voiced value outside them, 0 for a row without a voiced frame), the curve is
+ *   2^(float32 of that);  both the curve and uv (0.0 / 1.0) are interpolated from the grid j t_src onto i t_dst,
+ *   i < m (m = the length of numpy.arange(0, (n - 1) t_src, t_dst), computed by the caller), then cut or padded with
+ *   the last value to `length`;  uv_out = float32(uv curve) > 0.5;  f0_out = 0 where uv_out unless interp_uv.
+ * Every interpolation is slope (x - xp[j]) + fp[j] in double without contraction, on numpy.interp's bracket, and is
+ * rounded to float32 once.  n >= 2, m >= 1, length >= 1 (PD_ERR_ARG otherwise); n <= 262144 (PD_ERR_UNSUPPORTED).
+ * f0_out [B][length] float32, uv_out [B][length] bytes (0 / 1).  One launch, one block per row, stream-ordered. */
+int pd_f0_align(const float* f0, float* f0_out, unsigned char* uv_out, int B, int n, int m, int length, double t_src,
+                double t_dst, int interp_uv, void* stream);
+
 /* ================================================================ harmonic-noise separation
  * pd_vr -- CascadedNet of modules/vr (nets.py, layers.py) with is_complex = True, its zero-padded STFT and its
  * iSTFT: what extract_harmonic_aperiodic runs on a vocoder output (handler/infer/handler.py:349-358) and on every

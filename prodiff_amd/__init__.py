@@ -17,8 +17,10 @@ Drop-in replacements for the reference hot path (see DESIGN.md / INTEGRATION.md)
         <- modules/nsf_hifigan/nvSTFT.py:STFT, librosa.filters.mel
   * prodiff_amd.resample.Resample / resample / KAISER_BEST (polyphase sinc resampler on the GPU)
         <- torchaudio.transforms.Resample (component/pe/rmvpe.py:49), librosa.resample (utils/data_gen_utils.py:51)
-  * prodiff_amd.rmvpe.RMVPE / E2E0 / MelSpectrogram / to_local_average_f0 (pitch extraction on the GPU)
-        <- component/pe/rmvpe.py, modules/rmvpe/{model,deepunet,seq,spec,utils}.py
+  * prodiff_amd.rmvpe.RMVPE / E2E0 / MelSpectrogram / to_local_average_f0 / viterbi_path / to_viterbi_f0 / align_f0
+    (pitch extraction on the GPU, up to the f0 curve on the mel frame grid)
+        <- component/pe/rmvpe.py, modules/rmvpe/{model,deepunet,seq,spec,utils}.py, librosa.sequence.viterbi,
+           utils/pitch_utils.py (interp_f0, resample_align_curve)
   * prodiff_amd.vr.CascadedNet / load_sep_model / extract_harmonic_aperiodic (harmonic-noise separation on the GPU)
         <- modules/vr/{nets,layers,__init__}.py, component/binarizer/binarizer_utils.py
   * prodiff_amd.curves.get_energy / get_voicing / get_breath / get_kth_harmonic / get_tension /
@@ -36,7 +38,8 @@ from .variance import DurPredictor, PitchPredictor  # noqa: F401
 from .mel import STFT, mel_filterbank  # noqa: F401
 # the functional form stays prodiff_amd.resample.resample: binding it here would hide the module of that name
 from .resample import KAISER_BEST, Resample, sinc_resample_kernel64  # noqa: F401
-from .rmvpe import E2E0, RMVPE, MelSpectrogram, to_local_average_f0  # noqa: F401
+from .rmvpe import (E2E0, RMVPE, MelSpectrogram, align_f0, to_local_average_f0, to_viterbi_f0,  # noqa: F401
+                    viterbi_path)
 from .vr import CascadedNet, extract_harmonic_aperiodic, load_sep_model  # noqa: F401
 from .curves import (SinusoidalSmoothingConv1d, VarianceCurves, get_breath, get_energy, get_kth_harmonic,  # noqa: F401
                      get_tension, get_voicing, isolate_parts)
@@ -44,6 +47,6 @@ from .curves import (SinusoidalSmoothingConv1d, VarianceCurves, get_breath, get_
 __all__ = ["WaveNet", "GaussianDiffusion", "FastDiff", "sampling_given_noise_schedule", "RectifiedFlow",
            "PitchRectifiedFlow", "NsfGenerator", "NsfHifiGAN", "ProDiffTeacher", "PitchPredictor", "DurPredictor",
            "STFT", "mel_filterbank", "Resample", "KAISER_BEST", "sinc_resample_kernel64", "E2E0", "RMVPE",
-           "MelSpectrogram", "to_local_average_f0", "CascadedNet", "load_sep_model", "extract_harmonic_aperiodic",
-           "SinusoidalSmoothingConv1d", "VarianceCurves", "get_energy", "get_voicing", "get_breath", "get_kth_harmonic",
+           "MelSpectrogram", "to_local_average_f0", "viterbi_path", "to_viterbi_f0", "align_f0", "CascadedNet",
+           "load_sep_model", "extract_harmonic_aperiodic", "SinusoidalSmoothingConv1d", "VarianceCurves", "get_energy", "get_voicing", "get_breath", "get_kth_harmonic",
            "get_tension", "isolate_parts"]

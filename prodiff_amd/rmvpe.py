@@ -132,6 +132,93 @@ def to_local_average_f0(hidden, center=None, thred=0.03):
     return f0
 
 
+VITERBI_CHUNK = 32        # frames per backtrace chunk of pd_rmvpe_viterbi (PD_RMVPE_VITERBI_CHUNK)
+_TINY = float(np.finfo(np.float32).tiny)      # librosa.util.tiny of a float32 probability
+_VITERBI_TABLES = {}      # (n_class, width, device) -> (device log_band, log_off, log_init)
+_VITERBI_WS = _lib.Workspace()
+
+
+def viterbi_tables(n_class, width):
+    """The transition of modules/rmvpe/utils.py:29-31 as librosa.sequence.viterbi takes its log, float64:
+    (log_band [n_class, 2 width - 1] with lt[i][j] in column j - i + width - 1, log_off, log_init)."""
+    i = np.arange(n_class)
+    A = np.maximum(width - np.abs(i[:, None] - i[None, :]), 0)
+    A = A / A.sum(axis=1, keepdims=True)
+    lt = np.log(A + _TINY)
+    log_off = float(np.log(0.0 + _TINY))
+    band = np.full((n_class, 2 * width - 1), log_off)
+    for c in range(2 * width - 1):
+        j = i + c - (width - 1)
+        ok = (j >= 0) & (j < n_class)
+        band[i[ok], c] = lt[i[ok], j[ok]]
+    return band, log_off, float(np.log(1.0 / n_class + _TINY))
+
+
+@torch.no_grad()
+def viterbi_path(hidden, width=30, return_logp=False):
+    """The path ``librosa.sequence.viterbi(prob, transition)`` finds for each row of hidden [B, T, n_class]
+    (modules/rmvpe/utils.py:26-40, with the probabilities normalised in float64) on pd_rmvpe_viterbi:
+    int64 [B, T] on hidden's device, and with ``return_logp`` the path's log-probability, float64 [B].  A frame
+    that is zero in every class counts as uniform."""
+    if not hidden.is_cuda:
+        raise _lib.HipError("viterbi_path runs on the GPU (got a CPU tensor; there is no CPU fallback)")
+    hidden = hidden.float().contiguous()
+    B, T, n = hidden.shape
+    width = int(width)
+    dev = hidden.device
+    L = _lib.lib()
+    if L.pd_rmvpe_viterbi_chunk() != VITERBI_CHUNK:
+        raise _lib.HipError("VITERBI_CHUNK differs from the library's PD_RMVPE_VITERBI_CHUNK")
+    key = (n, width, str(dev))
+    tab = _VITERBI_TABLES.get(key)
+    if tab is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.HipError("viterbi_path: call once with this n_class and width before capturing a graph")
+        band, log_off, log_init = viterbi_tables(n, width)
+        tab = _VITERBI_TABLES[key] = (torch.from_numpy(band).to(dev), log_off, log_init)
+    band, log_off, log_init = tab
+    path = torch.empty(B, T, device=dev, dtype=torch.int64)
+    logp = torch.empty(B, device=dev, dtype=torch.float64) if return_logp else None
+    ws, wsb = _VITERBI_WS.get(L.pd_rmvpe_viterbi_workspace_size(B, T, n, width), dev)
+    _lib.check(L.pd_rmvpe_viterbi(_lib.fptr(hidden), band.data_ptr(), log_off, log_init, _lib.lptr(path),
+                                  None if logp is None else logp.data_ptr(), B, T, n, width, ws, wsb, _lib.stream_ptr(dev)))
+    return (path, logp) if return_logp else path
+
+
+@torch.no_grad()
+def to_viterbi_f0(hidden, thred=0.03):
+    """modules/rmvpe/utils.py:26-43 on the GPU, for any batch size: hidden [B, T, n_class] -> f0 [B, T] (device)."""
+    return to_local_average_f0(hidden, center=viterbi_path(hidden), thred=thred)
+
+
+def resampled_length(n, original_timestep, target_timestep):
+    """len(np.arange(0, (n - 1) * original_timestep, target_timestep)) without building the array."""
+    return int(np.ceil((n - 1) * original_timestep / target_timestep))
+
+
+@torch.no_grad()
+def align_f0(f0, original_timestep, target_timestep, length, interp_uv=False):
+    """``RMVPE.get_pitch`` after ``infer_from_audio``, on the GPU (pd_f0_align): f0 [B, n] (or [n]) at
+    ``original_timestep`` -> (f0 float32 [B, length], uv bool [B, length]) at ``target_timestep``, both on the
+    device: interp_f0, resample_align_curve of the curve and of uv, uv > 0.5, and f0 = 0 where unvoiced unless
+    ``interp_uv``."""
+    if not f0.is_cuda:
+        raise _lib.HipError("align_f0 runs on the GPU (got a CPU tensor; there is no CPU fallback)")
+    single = f0.dim() == 1
+    f0 = f0.float().reshape(-1, f0.shape[-1]).contiguous()
+    B, n = f0.shape
+    length = int(length)
+    m = resampled_length(n, float(original_timestep), float(target_timestep)) if n >= 2 else 0
+    if n < 2 or m < 1 or length < 1:
+        raise ValueError(f"align_f0 needs two source frames, one resampled frame and a positive length (n = {n}, "
+                         f"resampled {m}, length {length})")
+    out = torch.empty(B, length, device=f0.device, dtype=torch.float32)
+    uv = torch.empty(B, length, device=f0.device, dtype=torch.bool)
+    _lib.check(_lib.lib().pd_f0_align(_lib.fptr(f0), _lib.fptr(out), uv.data_ptr(), B, n, m, length, float(original_timestep),
+                                      float(target_timestep), int(bool(interp_uv)), _lib.stream_ptr(f0.device)))
+    return (out[0], uv[0]) if single else (out, uv)
+
+
 # ---------------------------------------------------------------- front end
 class MelSpectrogram(MelFrontEnd):
     """modules/rmvpe/spec.py: the HTK-scale log-mel of ``torch.stft(center=True)`` on the centred pd_mel.
@@ -224,21 +311,42 @@ class RMVPE:
 
     def decode(self, hidden, thred=0.03, use_viterbi=False):
         if use_viterbi:
-            raise NotImplementedError("Viterbi decoding is librosa on the CPU in the reference and is not offered")
+            if not hidden.is_cuda:
+                raise NotImplementedError("Viterbi decoding runs on the GPU: pass a device tensor (librosa on the CPU, "
+                                          "as in the reference, is not offered)")
+            return to_viterbi_f0(hidden, thred=thred).squeeze(0).cpu().numpy()
         return to_local_average_f0(hidden, thred=thred).squeeze(0).cpu().numpy()
 
-    def infer_from_audio(self, audio, sample_rate=16000, thred=0.03, use_viterbi=False):
-        audio = torch.from_numpy(np.asarray(audio)).float().unsqueeze(0).to(self.device)
+    def _hidden_from_audio(self, audio, sample_rate):
+        """audio [B, L] on the device at ``sample_rate`` -> hidden [B, T, 360]: resampler, centred mel, network."""
         if sample_rate != SAMPLE_RATE:
             key = str(sample_rate)
             if key not in self.resample_kernel:
                 self.resample_kernel[key] = Resample(sample_rate, SAMPLE_RATE, lowpass_filter_width=128)
             audio = self.resample_kernel[key](audio)
         mel_tm = self.mel_extractor.forward_time_major(audio, center=True)
-        return self.decode(self._hidden_time_major(mel_tm), thred=thred, use_viterbi=use_viterbi)
+        return self._hidden_time_major(mel_tm)
 
-    def get_pitch(self, waveform, samplerate, length, *, hop_size, f0_min=65, f0_max=1100, speed=1, interp_uv=False):
-        f0 = self.infer_from_audio(waveform, sample_rate=samplerate)
+    def infer_from_audio(self, audio, sample_rate=16000, thred=0.03, use_viterbi=False):
+        audio = torch.from_numpy(np.asarray(audio)).float().unsqueeze(0).to(self.device)
+        return self.decode(self._hidden_from_audio(audio, sample_rate), thred=thred, use_viterbi=use_viterbi)
+
+    @torch.no_grad()
+    def get_pitch_batch(self, waveforms, samplerate, length, *, hop_size, speed=1, interp_uv=False, use_viterbi=False,
+                        thred=0.03):
+        """``get_pitch`` for a batch of equally long waveforms [B, L] (device or host), entirely on the device:
+        -> (f0 float32 [B, length], uv bool [B, length]) as device tensors.  Everything after the waveforms'
+        copy to the device is stream-ordered; nothing waits on the host."""
+        audio = waveforms if torch.is_tensor(waveforms) else torch.from_numpy(np.asarray(waveforms))
+        audio = audio.float().reshape(-1, audio.shape[-1]).to(self.device)
+        hidden = self._hidden_from_audio(audio, samplerate)
+        f0 = to_viterbi_f0(hidden, thred=thred) if use_viterbi else to_local_average_f0(hidden, thred=thred)
+        time_step = int(np.round(hop_size * speed)) / samplerate
+        return align_f0(f0, 0.01, time_step, length, interp_uv=interp_uv)
+
+    def get_pitch(self, waveform, samplerate, length, *, hop_size, f0_min=65, f0_max=1100, speed=1, interp_uv=False,
+                  use_viterbi=False, thred=0.03):
+        f0 = self.infer_from_audio(waveform, sample_rate=samplerate, thred=thred, use_viterbi=use_viterbi)
         uv = f0 == 0
         f0, uv = interp_f0(f0, uv)
         hop_size = int(np.round(hop_size * speed))
