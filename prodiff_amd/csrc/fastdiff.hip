@@ -2583,49 +2583,28 @@ int dblock(const fd_model::Down& D, const float* in, float* out, float* t0, floa
   const long long bsi = (long long)Tout * f * CI, bso = (long long)Tout * CI;
   if (const __bf16* w0 = lookup_bf16(D.c0_w)) {   // bf16: one fused launch, intermediates in LDS
     ProfScope ps("fd_dblock_fused", st);
-    if (audio && f <= 4)
-      hipLaunchKernelGGL(dblock_bf16_kernel<4>, dim3(cdiv(Tout, DB_TS), B), dim3(DB_NT), 0, st, in, out, w0, D.c0_b,
-                         lookup_bf16(D.c1_w), D.c1_b, lookup_bf16(D.c2_w), D.c2_b, Tout, f, audio, m->first_w,
-                         m->first_b, lens, rate);
-    else if (audio)
-      hipLaunchKernelGGL(dblock_bf16_kernel<16>, dim3(cdiv(Tout, DB_TS), B), dim3(DB_NT), 0, st, in, out, w0, D.c0_b,
-                         lookup_bf16(D.c1_w), D.c1_b, lookup_bf16(D.c2_w), D.c2_b, Tout, f, audio, m->first_w,
-                         m->first_b, lens, rate);
-    else
-      hipLaunchKernelGGL(dblock_bf16_kernel<0>, dim3(cdiv(Tout, DB_TS), B), dim3(DB_NT), 0, st, in, out, w0, D.c0_b,
-                         lookup_bf16(D.c1_w), D.c1_b, lookup_bf16(D.c2_w), D.c2_b, Tout, f, nullptr, nullptr, nullptr,
-                         lens, rate);
+    // AF: the first conv of the audio computed here (a0 never stored), 4 or 16 samples per output row
+    dispatch([&](auto AF) {
+      hipLaunchKernelGGL(dblock_bf16_kernel<AF()>, dim3(cdiv(Tout, DB_TS), B), dim3(DB_NT), 0, st, in, out, w0, D.c0_b,
+                         lookup_bf16(D.c1_w), D.c1_b, lookup_bf16(D.c2_w), D.c2_b, Tout, f, audio,
+                         audio ? m->first_w : nullptr, audio ? m->first_b : nullptr, lens, rate);
+    }, one_of<0, 4, 16>(!audio ? 0 : f <= 4 ? 4 : 16));
     PD_LAUNCH_CHECK();
     return PD_OK;
   }
-  {
-    GemmArgs a = make_gemm(B, Tout, CI, D.c0_w, 96, D.c0_b, t0, bso, CI);
+  // fp32: one GEMM per conv; the first reads x[f i], the last adds residual_dense on x[f i]
+  const struct { const float* w; int ldw; const float* b; int dil; const float* src; float* dst; } conv[3] = {
+      {D.c0_w, 96, D.c0_b, 1, in, t0}, {D.c1_w, 96, D.c1_b, 2, t0, t1}, {D.c2_w, 128, D.c2_b, 4, t1, out}};
+  for (const auto& c : conv) {
+    const long long bs = c.src == in ? bsi : bso;
+    const int stride = c.src == in ? f : 1;
+    GemmArgs a = make_gemm(B, Tout, CI, c.w, c.ldw, c.b, c.dst, bso, CI);
     for (int tap = 0; tap < 3; ++tap) {
-      Seg s = make_seg(in, bsi, CI, CI, tap - 1, f);
+      Seg s = make_seg(c.src, bs, CI, CI, (tap - 1) * c.dil, stride);
       s.act = ACT_LRELU; s.alpha = 0.2f;
       add_seg(a, s);
     }
-    a.lens = lens; a.lens_mul = rate;
-    PD_TRY((launch_gemm<1, 1, 4, 1, EPI_STORE, U_FD_DBLOCK>(a, st, "fd_dblock")));
-  }
-  {
-    GemmArgs a = make_gemm(B, Tout, CI, D.c1_w, 96, D.c1_b, t1, bso, CI);
-    for (int tap = 0; tap < 3; ++tap) {
-      Seg s = make_seg(t0, bso, CI, CI, (tap - 1) * 2);
-      s.act = ACT_LRELU; s.alpha = 0.2f;
-      add_seg(a, s);
-    }
-    a.lens = lens; a.lens_mul = rate;
-    PD_TRY((launch_gemm<1, 1, 4, 1, EPI_STORE, U_FD_DBLOCK>(a, st, "fd_dblock")));
-  }
-  {
-    GemmArgs a = make_gemm(B, Tout, CI, D.c2_w, 128, D.c2_b, out, bso, CI);
-    for (int tap = 0; tap < 3; ++tap) {
-      Seg s = make_seg(t1, bso, CI, CI, (tap - 1) * 4);
-      s.act = ACT_LRELU; s.alpha = 0.2f;
-      add_seg(a, s);
-    }
-    add_seg(a, make_seg(in, bsi, CI, CI, 0, f));   // residual_dense on x[f i]
+    if (c.dst == out) add_seg(a, make_seg(in, bsi, CI, CI, 0, f));
     a.lens = lens; a.lens_mul = rate;
     PD_TRY((launch_gemm<1, 1, 4, 1, EPI_STORE, U_FD_DBLOCK>(a, st, "fd_dblock")));
   }
@@ -2668,45 +2647,292 @@ struct FdFinal {
   const int* uid;
 };
 
-template <int TS, bool UPS, bool AUD, bool FIN, bool PF, bool SUB = false, int TPW = 2>
-void launch_lvc_block_t(const LvcBlockArgs& la, long long Tout, int B, hipStream_t st) {
-  hipLaunchKernelGGL((lvc_block_bf16_kernel<TS, UPS, AUD, FIN, PF, SUB, TPW>), dim3(cdiv(Tout, TS), B),
-                     dim3(LbGeo<TS, TPW>::NT), 0, st, la);
+// What the stages of one eps-network evaluation share.  lens (device, B ints, or null): ragged batch --
+// utterance b is lens[b] mel frames of the padded Tc; every conv of the network reads zero past it
+// ("Ragged batches").
+struct FdCall {
+  const fd_model* m;
+  float* ws;
+  const FdWs& W;
+  int B, Tc;
+  const int* lens;
+  hipStream_t st;
+  const float* xa;       // audio [B][L]
+  bool aud;              // a0 = first_conv(audio) is recomputed by its consumers (fd_final_fused), never stored
+  const FdFinal* fin;    // the sampler update for the last block to apply, or null
+  bool side;             // the kernel predictor runs on the side stream (fd_sample)
+};
+
+// One LVC block's place in the network: x [B][Tin][32] -> [B][Tout = Tin r][32], written to xn; ad: audio_down
+// at Tout rows; Bfp: the block's LVC biases [B][Tc][256]
+struct FdBlockIo {
+  int n, r, hop;
+  long long Tin, Tout;
+  const float* x;
+  float* xn;
+  const float* ad;
+  const float* Bfp;
+};
+
+// The persistent whole-block kernel (r06) -- the final block (upsample r = 4, hop 256) and the hop-64 block
+// (upsample r = 8, audio_down from HBM): the phase GEMMs one phase per wave (NW % r == 0), the frames' biases
+// staged for hop >= 256 / 64.
+int launch_lvc_ps(const fd_model* m, const LvcBlockArgs& la, bool fin, long long Tout, int B, hipStream_t st) {
+  // one block per CU (a multiple of 8 blocks keeps the XCD-aware tile order; any grid size walks
+  // every tile once)
+  int dev = 0, ncu = 0;
+  PD_HIP(hipGetDevice(&dev));
+  PD_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  // FD_OPT_LVC_CARRY: with more tiles than blocks, a block walks runs of consecutive tiles and carries
+  // the left halo from tile to tile (lvc_ps_run); otherwise one tile per block, as before
+  const int ntx = (int)cdiv(Tout, 384), ntiles = ntx * B;
+  int nruns = 0;
+  const int grid = lvc_ps_grid((int)Tout, B, ncu, m->lvc_ps_grid, &nruns);
+  const int nb = m->lvc_carry && nruns ? B : 0;
+  if (!nb) nruns = ntiles;
+  dispatch([&](auto FINAL) {
+    hipLaunchKernelGGL(lvc_ps_kernel<FINAL()>, dim3(grid), dim3(512), 0, st, la, ntx, nruns, nb);
+  }, bool_of(fin));
+  PD_LAUNCH_CHECK();
+  return PD_OK;
 }
-template <int TS, int TPW = 2>
-int launch_lvc_block_ts(const LvcBlockArgs& la, bool ups, bool aud, bool fin, bool pf, long long Tout, int B,
-                        hipStream_t st) {
-  if constexpr (TPW == 1) {   // one tile per wave (hop >= 32 only)
-    if (la.hop < 32 || !ups || (aud != fin)) { set_error("lvc_block: one tile per wave needs hop >= 32 and the fused upsample"); return PD_ERR_ARG; }
-    if (fin) {
-      if (pf) launch_lvc_block_t<TS, true, true, true, true, false, 1>(la, Tout, B, st);
-      else launch_lvc_block_t<TS, true, true, true, false, false, 1>(la, Tout, B, st);
-    } else {
-      if (pf) launch_lvc_block_t<TS, true, false, false, true, false, 1>(la, Tout, B, st);
-      else launch_lvc_block_t<TS, true, false, false, false, false, 1>(la, Tout, B, st);
-    }
+
+// One whole-block LVC launch over B utterances of Tout rows: the persistent kernel, one tile per wave
+// (FD_OPT_LVC_TPW 1) or the TS-row tiles, with the block's fusions -- ups: the upsample, aud: a = first_conv
+// (audio) recomputed (the last block), fin: the final conv and the sampler update.
+int launch_lvc_block(const fd_model* m, const LvcBlockArgs& la, bool ups, bool aud, bool fin, long long Tout, int B,
+                     hipStream_t st) {
+  const int hop = la.hop, ts = hop < 32 ? m->lvc_ts_sub : m->lvc_ts;
+  const bool pf = m->lvc_pf && hop % 64 == 0;   // a 64-row tile pair shares one frame
+  const bool ps_fin = fin && la.r == 4 && hop % 256 == 0;
+  const bool ps_ups = ups && !fin && !aud && la.a && la.r == 8 && hop % 64 == 0;
+  if (pf && ts == 384 && m->lvc_tpw == 2 && m->lvc_ps && (ps_fin || ps_ups)) return launch_lvc_ps(m, la, ps_fin, Tout, B, st);
+  auto go = [&](auto TS, auto UPS, auto AUD, auto FIN, auto PF, auto SUB, auto TPW) {
+    hipLaunchKernelGGL((lvc_block_bf16_kernel<TS(), UPS(), AUD(), FIN(), PF(), SUB(), TPW()>), dim3(cdiv(Tout, TS()), B),
+                       dim3(LbGeo<TS(), TPW()>::NT), 0, st, la);
+  };
+  const bool sub = hop < 32;   // several frames per 32-row tile (the hop-8 block)
+  if (ts == 384 && m->lvc_tpw == 1 && !sub && ups && aud == fin) {   // one tile per wave (hop >= 32 only)
+    dispatch([&](auto FIN, auto PF) { go(Const<384>{}, Const<true>{}, FIN, FIN, PF, Const<false>{}, Const<1>{}); },
+             bool_of(fin), bool_of(pf));
     PD_LAUNCH_CHECK();
     return PD_OK;
   }
-  if (la.hop < 32) {   // several frames per 32-row tile (the hop-8 block)
-    if (aud || fin) { set_error("lvc_block: audio/final fusion needs hop >= 32"); return PD_ERR_ARG; }
-    if (ups) launch_lvc_block_t<TS, true, false, false, false, true>(la, Tout, B, st);
-    else launch_lvc_block_t<TS, false, false, false, false, true>(la, Tout, B, st);
-  } else if (!ups) {
-    if (aud || fin) { set_error("lvc_block: audio/final fusion needs the fused upsample"); return PD_ERR_ARG; }
-    launch_lvc_block_t<TS, false, false, false, false>(la, Tout, B, st);
-  } else if (!aud && !fin) {
-    if (pf) launch_lvc_block_t<TS, true, false, false, true>(la, Tout, B, st);
-    else launch_lvc_block_t<TS, true, false, false, false>(la, Tout, B, st);
-  } else if (aud && !fin) {
-    launch_lvc_block_t<TS, true, true, false, false>(la, Tout, B, st);
-  } else if (aud && fin) {
-    if (pf) launch_lvc_block_t<TS, true, true, true, true>(la, Tout, B, st);
-    else launch_lvc_block_t<TS, true, true, true, false>(la, Tout, B, st);
-  } else {
-    set_error("lvc_block: final fusion needs the audio fusion"); return PD_ERR_ARG;
-  }
+  if (sub && (aud || fin)) { set_error("lvc_block: audio/final fusion needs hop >= 32"); return PD_ERR_ARG; }
+  if (!ups && (aud || fin)) { set_error("lvc_block: audio/final fusion needs the fused upsample"); return PD_ERR_ARG; }
+  if (fin && !aud) { set_error("lvc_block: final fusion needs the audio fusion"); return PD_ERR_ARG; }
+  // two tiles per wave: the (UPS, AUD, FIN, PF, SUB) instantiated for every tile size (a tile size that is
+  // neither 256 nor 384 runs as 128).  The register prefetch (PF) exists beside the fused upsample without the
+  // audio fusion or with both fusions; the checks above leave no other combination.
+  const bool pfk = pf && !sub && ups && aud == fin;
+  dispatch([&](auto TS) {
+    dispatch_rows<DispatchRow<false, false, false, false, true>, DispatchRow<true, false, false, false, true>,
+                  DispatchRow<false, false, false, false, false>, DispatchRow<true, false, false, false, false>,
+                  DispatchRow<true, false, false, true, false>, DispatchRow<true, true, false, false, false>,
+                  DispatchRow<true, true, true, false, false>, DispatchRow<true, true, true, true, false>>(
+        [&](auto... cs) { go(TS, cs..., Const<2>{}); }, ups, aud, fin, pfk, sub);
+  }, one_of<128, 256, 384>(ts == 256 || ts == 384 ? ts : 128));
   PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// first conv (unless its consumers recompute it: aud) and the downsample chain a0 -> d[0] -> ... -> d[nb-1]
+// (FastDiff_model.py:89-93).  downs[n]: the input of DBlock n; *bottom: the last output [B][Tc][32].
+int fd_downsample(const FdCall& c, const float* downs[4], const float** bottom) {
+  const fd_model* m = c.m;
+  const int nb = m->nblocks;
+  const long long L = (long long)c.Tc * m->hops[nb - 1];
+  float* a0 = c.ws + c.W.a0;
+  if (!c.aud) {
+    ProfScope ps("fd_first_conv", c.st);
+    hipLaunchKernelGGL(first_conv_kernel, dim3(cdiv(L, 32), c.B), dim3(256), 0, c.st, c.xa, m->first_w,
+                       m->first_b, a0, (int)L, c.lens, m->hops[nb - 1]);
+    PD_LAUNCH_CHECK();
+  }
+  const float* cur = a0;
+  long long Lc = L;
+  for (int n = 0; n < nb; ++n) {
+    downs[n] = cur;
+    const int f = m->ratios[nb - 1 - n];
+    Lc /= f;
+    PD_TRY(dblock(m->dn[n], cur, c.ws + c.W.d[n], c.ws + c.W.dtmp0, c.ws + c.W.dtmp1, c.B, (int)Lc, f, c.st, m,
+                  n == 0 && c.aud ? c.xa : nullptr, c.lens, (int)(Lc / c.Tc)));
+    cur = c.ws + c.W.d[n];
+  }
+  *bottom = cur;
+  return PD_OK;
+}
+
+// fp32 kernel predictor of block n on c + fc_t(emb) (modules.py:202-204, 320-343): *hk = the final hidden
+// h [B][Tc][64], and the block's LVC biases in ws.Bf
+int fd_kp_f32(const FdCall& c, int n, const float* condT, const float* nz, const float** hk) {
+  const fd_model::Block& K = c.m->blk[n];
+  float* ws = c.ws;
+  const FdWs& W = c.W;
+  const int B = c.B, Tc = c.Tc, nb = c.m->nblocks;
+  const long long bsC = (long long)Tc * CC, bsH = (long long)Tc * HK;
+  {
+    GemmArgs a = make_gemm(B, Tc, HK, K.kin_w, 5 * 96, K.kin_b, ws + W.h0, bsH, HK);
+    for (int tap = 0; tap < 5; ++tap) {
+      Seg s = make_seg(condT, bsC, CC, CC, tap - 2);
+      s.add_vec = nz + n * CC;
+      s.add_ld = nb * CC;
+      add_seg(a, s);
+    }
+    a.act = ACT_LRELU; a.alpha = 0.1f;
+    a.lens = c.lens; a.lens_mul = 1;
+    PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_IN>(a, c.st, "fd_kp_in")));
+  }
+  const float* src = ws + W.h0;
+  float* rbuf[2] = {ws + W.ra, ws + W.rb};
+  for (int j = 0; j < 6; ++j) {
+    float* dst = rbuf[j & 1];
+    GemmArgs a = make_gemm(B, Tc, HK, K.kres_w[j], 3 * HK, K.kres_b[j], dst, bsH, HK);
+    for (int tap = 0; tap < 3; ++tap) add_seg(a, make_seg(src, bsH, HK, HK, tap - 1));
+    a.act = ACT_LRELU; a.alpha = 0.1f;
+    if (j == 5) { a.res = ws + W.h0; a.res_bs = bsH; a.res_ld = HK; }   // h + R(h)
+    a.lens = c.lens; a.lens_mul = 1;
+    PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_RES>(a, c.st, "fd_kp_res")));
+    src = dst;
+  }
+  *hk = src;
+  GemmArgs a = make_gemm(B, Tc, 2 * CI * NLY, K.kb_w, 3 * HK, K.kb_b, ws + W.Bf, (long long)Tc * 2 * CI * NLY,
+                         2 * CI * NLY);
+  for (int tap = 0; tap < 3; ++tap) add_seg(a, make_seg(src, bsH, HK, HK, tap - 1));
+  a.lens = c.lens; a.lens_mul = 1;
+  return launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_BIAS>(a, c.st, "fd_kp_bias");
+}
+
+// xn = upsample(x) of block b (modules.py:205-206)
+int fd_upsample(const FdCall& c, const FdBlockIo& b) {
+  const fd_model::Block& K = c.m->blk[b.n];
+  ProfScope ps("fd_upsample", c.st);
+  hipLaunchKernelGGL(upsample_kernel, dim3(cdiv(b.Tin, 32), b.r, c.B), dim3(256), 0, c.st, b.x, K.up_w, K.up_b, b.xn,
+                     (int)b.Tin, b.r, b.r / 2 + b.r % 2, c.lens, (int)(b.Tin / c.Tc));
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// The whole-block kernel's arguments for utterances [b0, b0 + nbk) of block b.  Kc: their kernels, every
+// layer's [nbk * Tc][6144]; ups / aud: the block's fusions; fin: the fused sampler update, or null.
+LvcBlockArgs lvc_block_args(const FdCall& c, const FdBlockIo& b, const __bf16* Kc, int b0, int nbk, bool ups, bool aud,
+                            const FdFinal* fin) {
+  const fd_model* m = c.m;
+  const fd_model::Block& K = m->blk[b.n];
+  const size_t rows = (size_t)nbk * c.Tc, L = (size_t)c.Tc * m->hops[m->nblocks - 1];
+  LvcBlockArgs la{};
+  for (int i = 0; i < NLY; ++i) {
+    la.Kf[i] = Kc + (size_t)i * rows * KPERLAYER;
+    la.Wc[i] = lookup_bf16(K.cv_w[i]);
+    la.bc[i] = K.cv_b[i];
+  }
+  // never write the buffer this launch reads: with the upsample fused, x_prev is the
+  // previous block's output (the other ping-pong buffer, or the DBlock output)
+  la.xin = (ups ? b.x : b.xn) + (size_t)b0 * (ups ? b.Tin : b.Tout) * CI;
+  la.xout = (ups ? b.xn : c.ws + c.W.y) + (size_t)b0 * b.Tout * CI;
+  la.a = aud ? nullptr : b.ad + (size_t)b0 * b.Tout * CI;
+  la.Bf = b.Bfp + (size_t)b0 * c.Tc * 2 * CI * NLY; la.Tc = c.Tc; la.hop = b.hop; la.b_off = b0;
+  la.lens = c.lens ? c.lens + b0 : nullptr;
+  la.prio = m->lvc_prio;
+  la.Wup = lookup_bf16(K.upf_w); la.bup = K.up_b; la.r = b.r; la.p = b.r / 2 + b.r % 2;
+  la.audio = c.xa + (size_t)b0 * L; la.fw = m->first_w; la.fb = m->first_b;
+  la.wfin = m->final_w; la.bfin = m->final_b;
+  if (fin) {
+    la.audio_out = fin->audio_out + (size_t)b0 * L; la.noise = fin->noise ? fin->noise + (size_t)b0 * L : nullptr;
+    la.ce = fin->ce; la.den = fin->den;
+    la.sig = fin->sig; la.seed = fin->seed; la.stream = fin->stream; la.uid = fin->uid;
+  }
+  return la;
+}
+
+// Block b as the whole-block LVC kernel (bf16): every layer's kernels first (frame-major bf16), then the whole
+// block in one launch.  hkb: the kernel predictor's hidden output.  *xo: the block's output, or null once the
+// fused final update has written c.fin->audio_out instead.
+int fd_block_whole(const FdCall& c, const FdBlockIo& b, const __bf16* hkb, float** xo) {
+  const fd_model* m = c.m;
+  const fd_model::Block& K = m->blk[b.n];
+  const int B = c.B, Tc = c.Tc, n = b.n;
+  const bool last = n == m->nblocks - 1;
+  const bool ups = m->lvc_fuse && b.r >= 4;
+  const bool fuse_fin = ups && last && c.fin != nullptr, side = c.side, aud = last && c.aud;
+  if (!ups) PD_TRY(fd_upsample(c, b));   // separate upsample
+  __bf16* Kb = reinterpret_cast<__bf16*>(c.ws + c.W.Kf);
+  // FD_OPT_KP_CHUNK: kernel predictor + LVC block per chunk of utterances, so a chunk's
+  // kernel tensor can still be on-die (Infinity Cache) when the LVC block reads it
+  const int cb = (!side && m->kp_chunk > 0 && m->kp_chunk < B) ? m->kp_chunk : B;
+  for (int b0 = 0; b0 < B; b0 += cb) {
+    const int nbk = B - b0 < cb ? B - b0 : cb;
+    __bf16* Kc = Kb;
+    if (side) {   // written on the side stream (fd_sample)
+      Kc += (size_t)n * nbk * Tc * NLY * KPERLAYER;
+      PD_HIP(hipStreamWaitEvent(c.st, m->ev_kp[n], 0));
+    } else {
+      PD_TRY(kp_kernels_all(K, hkb + (size_t)b0 * Tc * HK, Kc, nbk, Tc, c.st, true));
+    }
+    const LvcBlockArgs la = lvc_block_args(c, b, Kc, b0, nbk, ups, aud, fuse_fin ? c.fin : nullptr);
+    ProfScope ps(fuse_fin ? "fd_lvc_block_final" : b.hop < 32 ? "fd_lvc_block_sub" : ups ? "fd_lvc_block_ups"
+                                                                                     : "fd_lvc_block", c.st);
+    PD_TRY(launch_lvc_block(m, la, ups, aud, fuse_fin, b.Tout, nbk, c.st));
+  }
+  if (side) PD_HIP(hipEventRecord(m->ev_lvc[n], c.st));   // ring slot n free again
+  *xo = fuse_fin ? nullptr : ups ? b.xn : c.ws + c.W.y;
+  return PD_OK;
+}
+
+// Block b layer by layer (modules.py:205-217): the upsample, then per layer its kernels (fp32: hk -> ws.Kf
+// here; bf16: all four from hkb up front) and pre-conv + LVC + gate, in one launch (bf16, hop % 64 == 0) or two.
+// The output is b.xn.
+int fd_block_layers(const FdCall& c, const FdBlockIo& b, const float* hk, const __bf16* hkb) {
+  const fd_model* m = c.m;
+  const fd_model::Block& K = m->blk[b.n];
+  float* ws = c.ws;
+  const FdWs& W = c.W;
+  const int B = c.B, Tc = c.Tc, hop = b.hop;
+  const bool bf = m->weights.bf16() != nullptr;
+  PD_TRY(fd_upsample(c, b));
+  if (bf) PD_TRY(kp_kernels_all(K, hkb, reinterpret_cast<__bf16*>(ws + W.Kf), B, Tc, c.st, false));   // all 4 layers
+  for (int i = 0; i < NLY; ++i) {
+    const __bf16* Kbl = reinterpret_cast<const __bf16*>(ws + W.Kf) + (size_t)i * B * Tc * KPERLAYER;
+    if (!bf) {
+      GemmArgs a = make_gemm(B, Tc, KPERLAYER, K.kk_w + (size_t)i * KPERLAYER * 3 * HK, 3 * HK,
+                             K.kk_b + (size_t)i * KPERLAYER, ws + W.Kf, (long long)Tc * KPERLAYER,
+                             KPERLAYER);
+      for (int tap = 0; tap < 3; ++tap) add_seg(a, make_seg(hk, (long long)Tc * HK, HK, HK, tap - 1));
+      a.lens = c.lens; a.lens_mul = 1;
+      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_KERNEL>(a, c.st, "fd_kp_kernel")));
+    }
+    const int dil = (int)std::pow(3, i);
+    const float* Bfl = b.Bfp + i * 2 * CI;
+    if (bf && hop % 64 == 0) {
+      // one fused launch per layer: pre-conv + LVC + gate (bf16 MFMA)
+      ProfScope ps("fd_lvc_fused", c.st);
+      dispatch([&](auto TS) {
+        hipLaunchKernelGGL(lvc_fused_bf16_kernel<TS()>, dim3(B * Tc * (hop / TS())), dim3(TS() * 2), 0, c.st, b.xn, b.ad,
+                           Kbl, KPERLAYER, Bfl, 2 * CI * NLY, lookup_bf16(K.cv_w[i]), K.cv_b[i], Tc, hop, dil);
+      }, one_of<128, 64>(hop % 128 == 0 ? 128 : 64));
+    } else {
+      {  // y = lrelu(conv_dil3^i(lrelu(x + a)) + b)
+        GemmArgs a = make_gemm(B, (int)b.Tout, CI, K.cv_w[i], 96, K.cv_b[i], ws + W.y, b.Tout * CI, CI);
+        for (int tap = 0; tap < 3; ++tap) {
+          Seg sg = make_seg(b.xn, b.Tout * CI, CI, CI, (tap - 1) * dil);
+          sg.add_ten = b.ad;
+          sg.act = ACT_LRELU; sg.alpha = 0.2f;
+          add_seg(a, sg);
+        }
+        a.act = ACT_LRELU; a.alpha = 0.2f;
+        a.lens = c.lens; a.lens_mul = hop;
+        PD_TRY((launch_gemm<1, 1, 4, 1, EPI_STORE, U_FD_LVC_PRECONV>(a, c.st, "fd_lvc_preconv")));
+      }
+      ProfScope ps("fd_lvc", c.st);
+      if (bf)
+        hipLaunchKernelGGL(lvc_kernel<__bf16>, dim3(B * Tc), dim3(256), 0, c.st, b.xn, b.ad, ws + W.y, Kbl, KPERLAYER,
+                           Bfl, 2 * CI * NLY, Tc, hop, c.lens);
+      else
+        hipLaunchKernelGGL(lvc_kernel<float>, dim3(B * Tc), dim3(256), 0, c.st, b.xn, b.ad, ws + W.y, ws + W.Kf,
+                           KPERLAYER, Bfl, 2 * CI * NLY, Tc, hop, c.lens);
+    }
+    PD_LAUNCH_CHECK();
+  }
   return PD_OK;
 }
 
@@ -2714,240 +2940,40 @@ int launch_lvc_block_ts(const LvcBlockArgs& la, bool ups, bool aud, bool fin, bo
 // nz: this step's per-block fc_t(emb) rows ([B][nblocks*80]).  Leaves the LVC output in
 // *xout, or -- when `fin` is given and the last block is the fused LVC kernel -- applies
 // the sampler update itself and sets *xout = nullptr.
-// lens (device, B ints, or null): ragged batch -- utterance b is lens[b] mel frames of the padded Tc;
-// every conv of the network reads zero past it ("Ragged batches").
 int fd_net(const fd_model* m, float* ws, const FdWs& W, const float* xa, const float* condT,
            const float* nz, int step, int B, int Tc, float** xout, hipStream_t st,
            const FdFinal* fin = nullptr, bool side = false, const int* lens = nullptr) {
   const int nb = m->nblocks;
-  if (lens && m->weights.bf16() && m->lvc_ts == 0) {
+  const bool bf = m->weights.bf16() != nullptr;
+  if (lens && bf && m->lvc_ts == 0) {
     set_error("FD_OPT_LVC_TS 0 (per-layer LVC launches) does not take ragged batches (lens)");
     return PD_ERR_UNSUPPORTED;
   }
-  const long long L = (long long)Tc * m->hops[nb - 1];
-  const bool bf = m->weights.bf16() != nullptr;
-  // whole-block LVC kernel with its prologue/epilogue fusions (bf16)
-  // (hop % 32 == 0: one frame per 32-row tile; hop | 32: several, masked per frame)
-  auto fused_block = [&](int n) { return fd_block_fused(m, n); };
-  auto fused_ups = [&](int n) { return fused_block(n) && m->lvc_fuse && m->ratios[n] >= 4; };
-  const bool aud = fd_final_fused(m);              // a0 = first_conv(audio) recomputed by its consumers
-  float* a0 = ws + W.a0;
-  if (!aud) {
-    ProfScope ps("fd_first_conv", st);
-    hipLaunchKernelGGL(first_conv_kernel, dim3(cdiv(L, 32), B), dim3(256), 0, st, xa, m->first_w,
-                       m->first_b, a0, (int)L, lens, m->hops[nb - 1]);
-    PD_LAUNCH_CHECK();
-  }
-  // downsample chain: a0 -> d[0] -> ... -> d[nb-1]   (FastDiff_model.py:89-93)
-  const float* cur = a0;
-  long long Lc = L;
+  const FdCall c{m, ws, W, B, Tc, lens, st, xa, fd_final_fused(m), fin, side};
   const float* downs[4];
-  for (int n = 0; n < nb; ++n) {
-    downs[n] = cur;
-    const int f = m->ratios[nb - 1 - n];
-    Lc /= f;
-    PD_TRY(dblock(m->dn[n], cur, ws + W.d[n], ws + W.dtmp0, ws + W.dtmp1, B, (int)Lc, f, st, m,
-                  n == 0 && aud ? xa : nullptr, lens, (int)(Lc / Tc)));
-    cur = ws + W.d[n];
-  }
+  const float* x = nullptr;   // [B][Tc][32]
+  PD_TRY(fd_downsample(c, downs, &x));
   // LVC blocks (FastDiff_model.py:95-97)
-  const float* x = cur;   // [B][Tc][32]
   float* bufs[2] = {ws + W.X0, ws + W.X1};
   long long Tin = Tc;
   for (int n = 0; n < nb; ++n) {
-    const fd_model::Block& K = m->blk[n];
-    const int r = m->ratios[n], hop = m->hops[n];
-    const float* ad = downs[nb - 1 - n];
-    float* xn = bufs[n & 1];
-    const long long Tout = Tin * r;
-    const long long bsC = (long long)Tc * CC, bsH = (long long)Tc * HK;
-    // --- kernel predictor on c + fc_t(emb)   (modules.py:202-204, 320-343)
-    const float* hk = nullptr;   // final h  [B][Tc][64] (fp32 path)
-    const __bf16* hkb = nullptr; // final h, bf16 path
-    float* Bfp = ws + W.Bf;      // LVC biases of this block [B][Tc][256]
-    if (bf) {
-      // computed for every step and block up front (fd_kp_hidden_all)
+    FdBlockIo b{n, m->ratios[n], m->hops[n], Tin, Tin * m->ratios[n], x, bufs[n & 1], downs[nb - 1 - n], ws + W.Bf};
+    const float* hk = nullptr;   // the kernel predictor's final h [B][Tc][64] (fp32 path)
+    const __bf16* hkb = nullptr; // the same on the bf16 path: computed for every step and block up front
+    if (bf) {                    // (fd_kp_hidden_all)
       const size_t z = (size_t)step * nb + n;
       hkb = reinterpret_cast<const __bf16*>(ws + W.hall) + z * B * Tc * HK;
-      Bfp = ws + W.bfall + z * B * Tc * 2 * CI * NLY;
+      b.Bfp = ws + W.bfall + z * B * Tc * 2 * CI * NLY;
     } else {
-    {
-      GemmArgs a = make_gemm(B, Tc, HK, K.kin_w, 5 * 96, K.kin_b, ws + W.h0, bsH, HK);
-      for (int tap = 0; tap < 5; ++tap) {
-        Seg s = make_seg(condT, bsC, CC, CC, tap - 2);
-        s.add_vec = nz + n * CC;
-        s.add_ld = nb * CC;
-        add_seg(a, s);
-      }
-      a.act = ACT_LRELU; a.alpha = 0.1f;
-      a.lens = lens; a.lens_mul = 1;
-      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_IN>(a, st, "fd_kp_in")));
+      PD_TRY(fd_kp_f32(c, n, condT, nz, &hk));
     }
-    const float* src = ws + W.h0;
-    float* rbuf[2] = {ws + W.ra, ws + W.rb};
-    for (int j = 0; j < 6; ++j) {
-      float* dst = rbuf[j & 1];
-      GemmArgs a = make_gemm(B, Tc, HK, K.kres_w[j], 3 * HK, K.kres_b[j], dst, bsH, HK);
-      for (int tap = 0; tap < 3; ++tap) add_seg(a, make_seg(src, bsH, HK, HK, tap - 1));
-      a.act = ACT_LRELU; a.alpha = 0.1f;
-      if (j == 5) { a.res = ws + W.h0; a.res_bs = bsH; a.res_ld = HK; }   // h + R(h)
-      a.lens = lens; a.lens_mul = 1;
-      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_RES>(a, st, "fd_kp_res")));
-      src = dst;
-    }
-    hk = src;
-    {
-      GemmArgs a = make_gemm(B, Tc, 2 * CI * NLY, K.kb_w, 3 * HK, K.kb_b, ws + W.Bf,
-                             (long long)Tc * 2 * CI * NLY, 2 * CI * NLY);
-      for (int tap = 0; tap < 3; ++tap) add_seg(a, make_seg(hk, bsH, HK, HK, tap - 1));
-      a.lens = lens; a.lens_mul = 1;
-      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_BIAS>(a, st, "fd_kp_bias")));
-    }
-    }
-    if (fused_block(n)) {
-      // every layer's kernels first (frame-major bf16), then the whole block in one launch
-      const bool ups = fused_ups(n), last = n == nb - 1;
-      const bool fuse_fin = ups && last && fin != nullptr;
-      if (!ups) {   // separate upsample (modules.py:205-206)
-        ProfScope ps("fd_upsample", st);
-        hipLaunchKernelGGL(upsample_kernel, dim3(cdiv(Tin, 32), r, B), dim3(256), 0, st, x, K.up_w, K.up_b,
-                           xn, (int)Tin, r, r / 2 + r % 2, lens, (int)(Tin / Tc));
-        PD_LAUNCH_CHECK();
-      }
-      __bf16* Kb = reinterpret_cast<__bf16*>(ws + W.Kf);
-      // FD_OPT_KP_CHUNK: kernel predictor + LVC block per chunk of utterances, so a chunk's
-      // kernel tensor can still be on-die (Infinity Cache) when the LVC block reads it
-      const int cb = (!side && m->kp_chunk > 0 && m->kp_chunk < B) ? m->kp_chunk : B;
-      for (int b0 = 0; b0 < B; b0 += cb) {
-      const int nbk = B - b0 < cb ? B - b0 : cb;
-      const int rows = nbk * Tc;
-      __bf16* Kc = Kb;
-      if (side) {   // written on the side stream (fd_sample)
-        Kc += (size_t)n * rows * NLY * KPERLAYER;
-        PD_HIP(hipStreamWaitEvent(st, m->ev_kp[n], 0));
-      } else {
-        PD_TRY(kp_kernels_all(K, hkb + (size_t)b0 * Tc * HK, Kc, nbk, Tc, st, true));
-      }
-      LvcBlockArgs la{};
-      for (int i = 0; i < NLY; ++i) {
-        la.Kf[i] = Kc + (size_t)i * rows * KPERLAYER;
-        la.Wc[i] = lookup_bf16(K.cv_w[i]);
-        la.bc[i] = K.cv_b[i];
-      }
-      // never write the buffer this launch reads: with the upsample fused, x_prev is the
-      // previous block's output (the other ping-pong buffer, or the DBlock output)
-      la.xin = (ups ? x : xn) + (size_t)b0 * (ups ? Tin : Tout) * CI;
-      la.xout = (ups ? xn : ws + W.y) + (size_t)b0 * Tout * CI;
-      la.a = (last && aud) ? nullptr : ad + (size_t)b0 * Tout * CI;
-      la.Bf = Bfp + (size_t)b0 * Tc * 2 * CI * NLY; la.Tc = Tc; la.hop = hop; la.b_off = b0;
-      la.lens = lens ? lens + b0 : nullptr;
-      la.prio = m->lvc_prio;
-      la.Wup = lookup_bf16(K.upf_w); la.bup = K.up_b; la.r = r; la.p = r / 2 + r % 2;
-      la.audio = xa + (size_t)b0 * L; la.fw = m->first_w; la.fb = m->first_b;
-      la.wfin = m->final_w; la.bfin = m->final_b;
-      if (fuse_fin) {
-        la.audio_out = fin->audio_out + (size_t)b0 * L; la.noise = fin->noise ? fin->noise + (size_t)b0 * L : nullptr;
-        la.ce = fin->ce; la.den = fin->den;
-        la.sig = fin->sig; la.seed = fin->seed; la.stream = fin->stream; la.uid = fin->uid;
-      }
-      {
-        ProfScope ps(fuse_fin ? "fd_lvc_block_final" : hop < 32 ? "fd_lvc_block_sub" : ups ? "fd_lvc_block_ups"
-                                                                                   : "fd_lvc_block", st);
-        const int ts = hop < 32 ? m->lvc_ts_sub : m->lvc_ts;
-        const bool pf = m->lvc_pf && hop % 64 == 0;   // a 64-row tile pair shares one frame
-        // r06: the persistent kernel -- the final block (upsample r = 4, hop 256) and the hop-64 block
-        // (upsample r = 8, audio_down from HBM): the phase GEMMs one phase per wave (NW % r == 0), the
-        // frames' biases staged for hop >= 256 / 64
-        const bool ps_fin = fuse_fin && r == 4 && hop % 256 == 0;
-        const bool ps_ups = ups && !fuse_fin && !(last && aud) && la.a && r == 8 && hop % 64 == 0;
-        if (pf && ts == 384 && m->lvc_tpw == 2 && m->lvc_ps && (ps_fin || ps_ups)) {
-          // one block per CU (a multiple of 8 blocks keeps the XCD-aware tile order; any grid size walks
-          // every tile once)
-          int dev = 0, ncu = 0;
-          PD_HIP(hipGetDevice(&dev));
-          PD_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-          // FD_OPT_LVC_CARRY: with more tiles than blocks, a block walks runs of consecutive tiles and carries
-          // the left halo from tile to tile (lvc_ps_run); otherwise one tile per block, as before
-          const int ntx = (int)cdiv(Tout, 384), ntiles = ntx * nbk;
-          int nruns = 0;
-          const int grid = lvc_ps_grid((int)Tout, nbk, ncu, m->lvc_ps_grid, &nruns);
-          const int nb = m->lvc_carry && nruns ? nbk : 0;
-          if (!nb) nruns = ntiles;
-          if (ps_fin) hipLaunchKernelGGL(lvc_ps_kernel<true>, dim3(grid), dim3(512), 0, st, la, ntx, nruns, nb);
-          else hipLaunchKernelGGL(lvc_ps_kernel<false>, dim3(grid), dim3(512), 0, st, la, ntx, nruns, nb);
-          PD_LAUNCH_CHECK();
-        } else if (ts == 256) PD_TRY(launch_lvc_block_ts<256>(la, ups, last && aud, fuse_fin, pf, Tout, nbk, st));
-        else if (ts == 384 && m->lvc_tpw == 1 && hop >= 32 && ups && (last && aud) == fuse_fin)
-          PD_TRY((launch_lvc_block_ts<384, 1>(la, ups, last && aud, fuse_fin, pf, Tout, nbk, st)));
-        else if (ts == 384) PD_TRY(launch_lvc_block_ts<384>(la, ups, last && aud, fuse_fin, pf, Tout, nbk, st));
-        else PD_TRY(launch_lvc_block_ts<128>(la, ups, last && aud, fuse_fin, pf, Tout, nbk, st));
-      }
-      }
-      float* xo = ups ? xn : ws + W.y;
-      if (side) PD_HIP(hipEventRecord(m->ev_lvc[n], st));   // ring slot n free again
-      if (fuse_fin) { *xout = nullptr; return PD_OK; }
-      x = xo;
-      Tin = Tout;
-      continue;
-    }
-    // --- upsample (modules.py:205-206)
-    {
-      const int p = r / 2 + r % 2;
-      ProfScope ps("fd_upsample", st);
-      hipLaunchKernelGGL(upsample_kernel, dim3(cdiv(Tin, 32), r, B), dim3(256), 0, st, x, K.up_w, K.up_b,
-                         xn, (int)Tin, r, p, lens, (int)(Tin / Tc));
-      PD_LAUNCH_CHECK();
-    }
-    // --- 4 LVC layers (modules.py:208-217)
-    if (bf) PD_TRY(kp_kernels_all(K, hkb, reinterpret_cast<__bf16*>(ws + W.Kf), B, Tc, st, false));   // all 4 layers
-    for (int i = 0; i < NLY; ++i) {
-      const __bf16* Kbl = reinterpret_cast<const __bf16*>(ws + W.Kf) + (size_t)i * B * Tc * KPERLAYER;
-      if (!bf) {
-        GemmArgs a = make_gemm(B, Tc, KPERLAYER, K.kk_w + (size_t)i * KPERLAYER * 3 * HK, 3 * HK,
-                               K.kk_b + (size_t)i * KPERLAYER, ws + W.Kf, (long long)Tc * KPERLAYER,
-                               KPERLAYER);
-        for (int tap = 0; tap < 3; ++tap) add_seg(a, make_seg(hk, bsH, HK, HK, tap - 1));
-        a.lens = lens; a.lens_mul = 1;
-        PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_FD_KP_KERNEL>(a, st, "fd_kp_kernel")));
-      }
-      const int dil = (int)std::pow(3, i);
-      if (bf && hop % 64 == 0) {
-        // one fused launch per layer: pre-conv + LVC + gate (bf16 MFMA)
-        ProfScope ps("fd_lvc_fused", st);
-        const __bf16* Kb = Kbl;
-        const __bf16* Wc = lookup_bf16(K.cv_w[i]);
-        if (hop % 128 == 0)
-          hipLaunchKernelGGL(lvc_fused_bf16_kernel<128>, dim3(B * Tc * (hop / 128)), dim3(256), 0, st, xn, ad, Kb,
-                             KPERLAYER, Bfp + i * 2 * CI, 2 * CI * NLY, Wc, K.cv_b[i], Tc, hop, dil);
-        else
-          hipLaunchKernelGGL(lvc_fused_bf16_kernel<64>, dim3(B * Tc * (hop / 64)), dim3(128), 0, st, xn, ad, Kb,
-                             KPERLAYER, Bfp + i * 2 * CI, 2 * CI * NLY, Wc, K.cv_b[i], Tc, hop, dil);
-      } else {
-        {  // y = lrelu(conv_dil3^i(lrelu(x + a)) + b)
-          GemmArgs a = make_gemm(B, (int)Tout, CI, K.cv_w[i], 96, K.cv_b[i], ws + W.y, Tout * CI, CI);
-          for (int tap = 0; tap < 3; ++tap) {
-            Seg sg = make_seg(xn, Tout * CI, CI, CI, (tap - 1) * dil);
-            sg.add_ten = ad;
-            sg.act = ACT_LRELU; sg.alpha = 0.2f;
-            add_seg(a, sg);
-          }
-          a.act = ACT_LRELU; a.alpha = 0.2f;
-          a.lens = lens; a.lens_mul = hop;
-          PD_TRY((launch_gemm<1, 1, 4, 1, EPI_STORE, U_FD_LVC_PRECONV>(a, st, "fd_lvc_preconv")));
-        }
-        ProfScope ps("fd_lvc", st);
-        if (bf)
-          hipLaunchKernelGGL(lvc_kernel<__bf16>, dim3(B * Tc), dim3(256), 0, st, xn, ad, ws + W.y,
-                             Kbl, KPERLAYER, Bfp + i * 2 * CI,
-                             2 * CI * NLY, Tc, hop, lens);
-        else
-          hipLaunchKernelGGL(lvc_kernel<float>, dim3(B * Tc), dim3(256), 0, st, xn, ad, ws + W.y, ws + W.Kf,
-                             KPERLAYER, Bfp + i * 2 * CI, 2 * CI * NLY, Tc, hop, lens);
-      }
-      PD_LAUNCH_CHECK();
-    }
-    x = xn;
-    Tin = Tout;
+    float* xo = b.xn;
+    // whole-block LVC kernel with its prologue/epilogue fusions (bf16), or layer by layer
+    if (fd_block_fused(m, n)) PD_TRY(fd_block_whole(c, b, hkb, &xo));
+    else PD_TRY(fd_block_layers(c, b, hk, hkb));
+    if (!xo) { *xout = nullptr; return PD_OK; }
+    x = xo;
+    Tin = b.Tout;
   }
   *xout = const_cast<float*>(x);
   return PD_OK;

@@ -1,11 +1,58 @@
 // Small utility kernels shared by the WaveNet and FastDiff paths.
 #pragma once
+#include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "common.h"
 
 namespace pd {
+
+// ---- runtime value -> template argument
+// A launcher writes its launch once, as a generic lambda over std::integral_constant arguments
+// (`[&](auto K, auto D) { hipLaunchKernelGGL((kernel<K(), D()>), ...); }`), and one of the two forms below
+// calls it with the constants that equal the runtime values.  Both return false, calling nothing, when no entry
+// matches: the caller then reports the shape or falls to its runtime kernel (`go(Const<0>{}, Const<0>{})`).
+// Only the listed combinations are instantiated.
+template <auto V> using Const = std::integral_constant<decltype(V), V>;
+template <class T, T... Vs> struct OneOf { T v; };
+template <int... Vs> OneOf<int, Vs...> one_of(int v) { return {v}; }
+inline OneOf<bool, false, true> bool_of(bool v) { return {v}; }
+
+// Product form: every combination of the axes' values, e.g. dispatch(go, one_of<3, 7, 11>(taps), one_of<1, 3, 5>(dil)).
+template <class F> bool dispatch(F&& f) { f(); return true; }
+template <class F, class T, T... Vs, class... Rest>
+bool dispatch(F&& f, OneOf<T, Vs...> a, Rest... rest) {
+  return ((a.v == Vs && dispatch([&](auto... cs) { f(std::integral_constant<T, Vs>{}, cs...); }, rest...)) || ...);
+}
+
+// List form, for ladders that are no product:
+//   dispatch_rows<DispatchRow<32, 3, 16, 8>, DispatchRow<64, 3, 8, 8>, ...>(go, C, taps)
+// calls go with the constants of the first row whose leading entries equal the keys (the other entries ride along).
+// A key has the type of its column (bool or int): a mismatch does not compile.
+template <auto... Vs> struct DispatchRow {
+  template <size_t... I, class... K> static bool match(std::index_sequence<I...>, K... key) {
+    using Cols = std::tuple<decltype(Vs)...>;
+    static_assert((std::is_same_v<K, std::tuple_element_t<I, Cols>> && ...), "a key's type is its column's");
+    return ((key == std::get<I>(Cols{Vs...})) && ...);
+  }
+  template <class F, class... K> static bool try_call(F& f, K... key) {
+    return match(std::index_sequence_for<K...>{}, key...) && (f(Const<Vs>{}...), true);
+  }
+};
+template <class... Rows, class F, class... K> bool dispatch_rows(F&& f, K... key) {
+  return (Rows::try_call(f, key...) || ...);
+}
+
+// Raises Kernel's dynamic LDS limit to `bytes`: one hipFuncSetAttribute call per kernel for the life of the
+// process (every caller passes the kernel's one fixed maximum).
+template <auto Kernel> int raise_dynamic_lds(int bytes, const char* who) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (attr != hipSuccess) { set_error(std::string(who) + ": cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
+  return PD_OK;
+}
 
 // out[v][n] = act(sum_k W[n][k] * in[v][k] + bias[n]) for v < nvec.
 // One wave per output row, lanes stride K (coalesced rows of W).

@@ -236,9 +236,7 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
 
 template <int MT>
 int launch_mel(const MelArgs& a, int B, hipStream_t st) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_forward_kernel<MT>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)MEL_MAX_LDS);
-  if (attr != hipSuccess) { set_error("mel: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
+  PD_TRY(raise_dynamic_lds<&mel_forward_kernel<MT>>((int)MEL_MAX_LDS, "mel"));
   ProfScope ps("mel_forward", st);
   hipLaunchKernelGGL(mel_forward_kernel<MT>, dim3(cdiv(a.T, MEL_TF), B), dim3(MEL_NT), a.p.lds_bytes, st, a);
   PD_LAUNCH_CHECK();

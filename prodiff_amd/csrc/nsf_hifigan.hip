@@ -355,9 +355,7 @@ int launch_conv_small(const NsfConv& c, const float* in, float alpha, float scal
   constexpr int OC = C < 8 ? C : 8, NG = C / OC, TR = 256 / NG * 4;
   const size_t lds = ((size_t)c.taps * C * C + (size_t)(TR + (c.taps - 1) * c.dil) * (C + 1)) * sizeof(float);
   if (lds > 160 * 1024) { set_error("nsf conv: LDS window too large"); return PD_ERR_UNSUPPORTED; }
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&nsf_conv_small_kernel<C>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr != hipSuccess) { set_error("nsf conv: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
+  PD_TRY(raise_dynamic_lds<&nsf_conv_small_kernel<C>>(160 * 1024, "nsf conv"));
   ProfScope ps("nsf_res_small", st);
   hipLaunchKernelGGL(nsf_conv_small_kernel<C>, dim3(cdiv(Tl, TR), B), dim3(256), lds, st, in, c.w, c.taps * c.kpad,
                      c.kpad, c.b, c.taps, c.dil, alpha, scale, Tl, res, out, rag_);
@@ -739,44 +737,37 @@ __global__ __launch_bounds__(256, 2) void nsf_pair_kernel(const float* __restric
 #ifndef NSF_PAIR_FMO128
 #define NSF_PAIR_FMO128 4  // C = 128 output row tiles per block
 #endif
-template <int C, int TAPS, int DIL>
-int launch_pair_ct(const NsfConv& c1, const NsfConv& c2, const float* x, int B, int Tl, float* out, int accum,
-                   hipStream_t st, NsfRag rag_) {
-  constexpr int FMO = C == 32 ? NSF_PAIR_FMO32 : C == 64 ? NSF_PAIR_FMO64 : NSF_PAIR_FMO128, TM = 32 * FMO;
-  // x / xt window + stage_window's spare row
-  const size_t lds = (size_t)(32 * (FMO + 1) + (c1.taps - 1) * c1.dil + 1) * (C + 8) * sizeof(__bf16);
-  static const hipError_t attr = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&nsf_pair_kernel<C, FMO, TAPS, DIL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-      160 * 1024);
-  if (attr != hipSuccess) { set_error("nsf pair: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
-  ProfScope ps("nsf_pair", st);
-  hipLaunchKernelGGL((nsf_pair_kernel<C, FMO, TAPS, DIL>), dim3(cdiv(Tl, TM), 1, B), dim3(256), lds, st, x,
-                     lookup_bf16(c1.w), lookup_bf16(c2.w), c1.taps * c1.kpad, c1.kpad, c1.b, c2.b, c1.taps, c1.dil, Tl,
-                     out, accum, rag_);
-  PD_LAUNCH_CHECK();
-  return PD_OK;
-}
-
 // compile-time (taps, dilation) for the shipped ResBlock1 shapes (kernel sizes 3, 7, 11 x dilations
 // 1, 3, 5; handler/base_config.yaml), the runtime kernel otherwise
 template <int C>
 int launch_pair_c(const NsfConv& c1, const NsfConv& c2, const float* x, int B, int Tl, float* out, int accum,
                   hipStream_t st, NsfRag rag_) {
-#define PD_PAIR_CASE(K, D) \
-  if (c1.taps == K && c1.dil == D && c1.kpad == C) return launch_pair_ct<C, K, D>(c1, c2, x, B, Tl, out, accum, st, rag_)
-  PD_PAIR_CASE(3, 1); PD_PAIR_CASE(3, 3); PD_PAIR_CASE(3, 5);
-  PD_PAIR_CASE(7, 1); PD_PAIR_CASE(7, 3); PD_PAIR_CASE(7, 5);
-  PD_PAIR_CASE(11, 1); PD_PAIR_CASE(11, 3); PD_PAIR_CASE(11, 5);
-#undef PD_PAIR_CASE
-  return launch_pair_ct<C, 0, 0>(c1, c2, x, B, Tl, out, accum, st, rag_);
+  constexpr int FMO = C == 32 ? NSF_PAIR_FMO32 : C == 64 ? NSF_PAIR_FMO64 : NSF_PAIR_FMO128, TM = 32 * FMO;
+  // x / xt window + stage_window's spare row
+  const size_t lds = (size_t)(32 * (FMO + 1) + (c1.taps - 1) * c1.dil + 1) * (C + 8) * sizeof(__bf16);
+  int rc = PD_OK;
+  auto go = [&](auto K, auto D) {
+    constexpr auto kernel = &nsf_pair_kernel<C, FMO, K(), D()>;
+    if ((rc = raise_dynamic_lds<kernel>(160 * 1024, "nsf pair")) != PD_OK) return;
+    ProfScope ps("nsf_pair", st);
+    hipLaunchKernelGGL(kernel, dim3(cdiv(Tl, TM), 1, B), dim3(256), lds, st, x, lookup_bf16(c1.w), lookup_bf16(c2.w),
+                       c1.taps * c1.kpad, c1.kpad, c1.b, c2.b, c1.taps, c1.dil, Tl, out, accum, rag_);
+  };
+  if (c1.kpad != C || !dispatch(go, one_of<3, 7, 11>(c1.taps), one_of<1, 3, 5>(c1.dil))) go(Const<0>{}, Const<0>{});
+  PD_TRY(rc);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
 }
 
-bool wconv_ok(const NsfConv& c);
-// The fused pair for these convs, if it has one: both windowed (bf16), 32, 64 or 128 channels, equal
-// taps and packing, c2 undilated.
-// C = 16 (nsf_pair16_kernel): the shipped shapes only -- taps 3 / 7 / 11, c1 dilation 1 / 3 / 5.
-// The whole 16-channel ResBlock1 in one launch (nsf_rb16_kernel): three bf16 windowed pairs of one
-// shipped kernel size with c1 dilations 1, 3, 5 and c2 undilated.
+// The windowed conv for this ResBlock conv, if it has one (bf16 weights, C in {16..256}); on the
+// bf16 path it takes precedence over NSF_OPT_SMALL_MAX, which then only routes the fp32 path.
+bool wconv_ok(const NsfConv& c) {
+  return c.wconv && c.cin == c.cout && c.taps <= 11 && lookup_bf16(c.w) != nullptr &&
+         (c.cout == 16 || c.cout == 32 || c.cout == 64 || c.cout == 128 || c.cout == 256);
+}
+
+// The whole ResBlock1 in one launch (nsf_rb16_kernel, nsf_rb_kernel), if these convs have one: three bf16
+// windowed pairs of one shipped kernel size with c1 dilations 1, 3, 5 and c2 undilated.
 bool rb_ok(const nsf_model* m, const NsfConv* c1, const NsfConv* c2, int C) {
   const int k = c1[0].taps, bit = k == 3 ? 1 : k == 7 ? 2 : k == 11 ? 4 : 0;
   if (C == 16 ? !m->rb16 : C == 32 ? !(m->rb32 & bit) : C == 64 ? !(m->rb64 & bit) : true) return false;
@@ -788,26 +779,15 @@ bool rb_ok(const nsf_model* m, const NsfConv* c1, const NsfConv* c2, int C) {
   }
   return c1[0].taps == 3 || c1[0].taps == 7 || c1[0].taps == 11;
 }
+// The fused pair for these convs, if it has one: both windowed (bf16), 32, 64 or 128 channels, equal
+// taps and packing, c2 undilated.
+// C = 16 (nsf_pair16_kernel): the shipped shapes only -- taps 3 / 7 / 11, c1 dilation 1 / 3 / 5.
 bool pair_ok(const nsf_model* m, const NsfConv& c1, const NsfConv& c2) {
   const bool c16 = c1.cout == 16 && c1.kpad == 32 && (c1.taps == 3 || c1.taps == 7 || c1.taps == 11) &&
                    (c1.dil == 1 || c1.dil == 3 || c1.dil == 5);
   return m->pair && wconv_ok(c1) && wconv_ok(c2) && c1.cout == c2.cout &&
          (c1.cout == 32 || c1.cout == 64 || c1.cout == 128 || (c16 && m->pair16)) &&
          c1.taps == c2.taps && c1.kpad == c2.kpad && c2.dil == 1 && c1.taps <= 33;
-}
-int launch_pair16(const NsfConv& c1, const NsfConv& c2, const float* x, int B, int Tl, float* out, int accum,
-                  hipStream_t st, NsfRag rag_);
-
-int launch_pair(const NsfConv& c1, const NsfConv& c2, const float* x, int B, int Tl, float* out, int accum,
-                hipStream_t st, NsfRag rag_) {
-  if ((long long)B * Tl * c1.cout >= (1ll << 31)) {
-    set_error("nsf pair: B * T * C >= 2^31 elements (32-bit epilogue offsets)");
-    return PD_ERR_UNSUPPORTED;
-  }
-  if (c1.cout == 16) return launch_pair16(c1, c2, x, B, Tl, out, accum, st, rag_);
-  if (c1.cout == 128) return launch_pair_c<128>(c1, c2, x, B, Tl, out, accum, st, rag_);
-  if (c1.cout == 32) return launch_pair_c<32>(c1, c2, x, B, Tl, out, accum, st, rag_);
-  return launch_pair_c<64>(c1, c2, x, B, Tl, out, accum, st, rag_);
 }
 
 // 16-channel variant (the last upsample stage, 512 samples per frame) on
@@ -1014,17 +994,28 @@ int launch_pair16(const NsfConv& c1, const NsfConv& c2, const float* x, int B, i
                   hipStream_t st, NsfRag rag_) {
   const dim3 grid(cdiv(Tl, 256), B);
   ProfScope ps("nsf_pair16", st);
-#define PD_PAIR16(K, D)                                                                                            \
-  if (c1.taps == K && c1.dil == D)                                                                                 \
-    hipLaunchKernelGGL((nsf_pair16_kernel<K, D>), grid, dim3(256), 0, st, x, lookup_bf16(c1.w), lookup_bf16(c2.w), \
-                       c1.b, c2.b, Tl, out, accum, rag_)
-  PD_PAIR16(3, 1); else PD_PAIR16(3, 3); else PD_PAIR16(3, 5);
-  else PD_PAIR16(7, 1); else PD_PAIR16(7, 3); else PD_PAIR16(7, 5);
-  else PD_PAIR16(11, 1); else PD_PAIR16(11, 3); else PD_PAIR16(11, 5);
-  else { set_error("nsf pair16: not a shipped (taps, dilation) shape"); return PD_ERR_UNSUPPORTED; }
-#undef PD_PAIR16
+  auto go = [&](auto K, auto D) {
+    hipLaunchKernelGGL((nsf_pair16_kernel<K(), D()>), grid, dim3(256), 0, st, x, lookup_bf16(c1.w), lookup_bf16(c2.w),
+                       c1.b, c2.b, Tl, out, accum, rag_);
+  };
+  if (!dispatch(go, one_of<3, 7, 11>(c1.taps), one_of<1, 3, 5>(c1.dil))) {
+    set_error("nsf pair16: not a shipped (taps, dilation) shape");
+    return PD_ERR_UNSUPPORTED;
+  }
   PD_LAUNCH_CHECK();
   return PD_OK;
+}
+
+int launch_pair(const NsfConv& c1, const NsfConv& c2, const float* x, int B, int Tl, float* out, int accum,
+                hipStream_t st, NsfRag rag_) {
+  if ((long long)B * Tl * c1.cout >= (1ll << 31)) {
+    set_error("nsf pair: B * T * C >= 2^31 elements (32-bit epilogue offsets)");
+    return PD_ERR_UNSUPPORTED;
+  }
+  if (c1.cout == 16) return launch_pair16(c1, c2, x, B, Tl, out, accum, st, rag_);
+  if (c1.cout == 128) return launch_pair_c<128>(c1, c2, x, B, Tl, out, accum, st, rag_);
+  if (c1.cout == 32) return launch_pair_c<32>(c1, c2, x, B, Tl, out, accum, st, rag_);
+  return launch_pair_c<64>(c1, c2, x, B, Tl, out, accum, st, rag_);
 }
 
 // ---------------------------------------------------------------- whole ResBlock1 at C = 16 (r06)
@@ -1356,64 +1347,57 @@ __global__ __launch_bounds__(NW * 64) void nsf_rb_kernel(const float* __restrict
   }
 }
 
-template <int C, int TAPS, int NTW, int NW>
-int launch_rb_ct(const NsfRb16Args& a, const float* x, int B, int Tl, float* out, int accum, hipStream_t st,
-                 NsfRag rag_) {
-  constexpr int LDS = (32 * NTW + 64) * (C + 8) * 2;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&nsf_rb_kernel<C, TAPS, NTW, NW>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (attr != hipSuccess) { set_error("nsf rb: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
-  hipLaunchKernelGGL((nsf_rb_kernel<C, TAPS, NTW, NW>), dim3(cdiv(Tl, 32 * NTW - 12 * (TAPS - 1)), B), dim3(64 * NW),
-                     LDS, st, x, a, Tl, out, accum, rag_);
-  PD_LAUNCH_CHECK();
-  return PD_OK;
-}
-
-// NSF_OPT_RB32 / RB64: the 32- / 64-channel ResBlock1s as one launch each, for the kernel sizes whose bit
-// (1: taps 3, 2: taps 7, 4: taps 11) is set
-int launch_rb(const NsfConv* c1, const NsfConv* c2, const float* x, int B, int Tl, float* out, int accum,
-              hipStream_t st, NsfRag rag_) {
+// the three (c1, c2) pairs of one ResBlock1 as the whole-ResBlock kernels take them
+NsfRb16Args rb_args(const NsfConv* c1, const NsfConv* c2) {
   NsfRb16Args a{};
   for (int q = 0; q < 3; ++q) {
     a.w1[q] = lookup_bf16(c1[q].w); a.w2[q] = lookup_bf16(c2[q].w);
     a.b1[q] = c1[q].b; a.b2[q] = c2[q].b;
   }
+  return a;
+}
+
+// NSF_OPT_RB32 / RB64: the 32- / 64-channel ResBlock1s as one launch each, for the kernel sizes whose bit
+// (1: taps 3, 2: taps 7, 4: taps 11) is set.  rb_ok admits only the (channels, taps) of the table.
+int launch_rb(const NsfConv* c1, const NsfConv* c2, const float* x, int B, int Tl, float* out, int accum,
+              hipStream_t st, NsfRag rag_) {
+  const NsfRb16Args a = rb_args(c1, c2);
   ProfScope ps(c1[0].cout == 32 ? "nsf_rb32" : "nsf_rb64", st);
-  const int k = c1[0].taps;
-  if (c1[0].cout == 32) {
-    if (k == 3) return launch_rb_ct<32, 3, 16, 8>(a, x, B, Tl, out, accum, st, rag_);
-    if (k == 7) return launch_rb_ct<32, 7, 16, 8>(a, x, B, Tl, out, accum, st, rag_);
-    return launch_rb_ct<32, 11, 16, 8>(a, x, B, Tl, out, accum, st, rag_);
+  int rc = PD_OK;
+  auto go = [&](auto C, auto TAPS, auto NTW, auto NW) {
+    constexpr int LDS = (32 * NTW() + 64) * (C() + 8) * 2;
+    constexpr auto kernel = &nsf_rb_kernel<C(), TAPS(), NTW(), NW()>;
+    if ((rc = raise_dynamic_lds<kernel>(LDS, "nsf rb")) != PD_OK) return;
+    hipLaunchKernelGGL(kernel, dim3(cdiv(Tl, 32 * NTW() - 12 * (TAPS() - 1)), B), dim3(64 * NW()), LDS, st, x, a, Tl,
+                       out, accum, rag_);
+  };
+  // (channels, taps) -> (NTW, NW)
+  if (!dispatch_rows<DispatchRow<32, 3, 16, 8>, DispatchRow<32, 7, 16, 8>, DispatchRow<32, 11, 16, 8>, DispatchRow<64, 3, 8, 8>, DispatchRow<64, 7, 16, 8>,
+                     DispatchRow<64, 11, 16, 8>>(go, c1[0].cout, c1[0].taps)) {
+    set_error("nsf rb: not a shipped (channels, taps) shape");
+    return PD_ERR_UNSUPPORTED;
   }
-  if (k == 3) return launch_rb_ct<64, 3, 8, 8>(a, x, B, Tl, out, accum, st, rag_);
-  if (k == 7) return launch_rb_ct<64, 7, 16, 8>(a, x, B, Tl, out, accum, st, rag_);
-  return launch_rb_ct<64, 11, 16, 8>(a, x, B, Tl, out, accum, st, rag_);
+  PD_TRY(rc);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
 }
 
 // NSF_OPT_RB16: the 16-channel ResBlock1s of the shipped shapes as one launch each (nsf_rb16_kernel)
 int launch_rb16(const NsfConv* c1, const NsfConv* c2, const float* x, int B, int Tl, float* out, int accum,
                 hipStream_t st, NsfRag rag_, int geo) {
-  NsfRb16Args a{};
-  for (int q = 0; q < 3; ++q) {
-    a.w1[q] = lookup_bf16(c1[q].w); a.w2[q] = lookup_bf16(c2[q].w);
-    a.b1[q] = c1[q].b; a.b2[q] = c2[q].b;
-  }
+  const NsfRb16Args a = rb_args(c1, c2);
   ProfScope ps("nsf_rb16", st);
   // geometry (NSF_OPT_RB16): 1 = 32-tile windows of 4 waves (3 blocks per CU), 2 = 64-tile windows of 8
   // waves (half the halo share, one block per CU)
-#define PD_RB16(K, NTW, NW)                                                                                 \
-  hipLaunchKernelGGL((nsf_rb16_kernel<K, NTW, NW>), dim3(cdiv(Tl, 16 * NTW - 12 * (K - 1)), B), dim3(64 * NW), 0, \
-                     st, x, a, Tl, out, accum, rag_)
-  if (geo == 2) {
-    if (c1[0].taps == 3) PD_RB16(3, 64, 8);
-    else if (c1[0].taps == 7) PD_RB16(7, 64, 8);
-    else PD_RB16(11, 64, 8);
-  } else {
-    if (c1[0].taps == 3) PD_RB16(3, 32, 4);
-    else if (c1[0].taps == 7) PD_RB16(7, 32, 4);
-    else PD_RB16(11, 32, 4);
+  auto go = [&](auto WIDE, auto K) {
+    constexpr int NTW = WIDE() ? 64 : 32, NW = WIDE() ? 8 : 4;
+    hipLaunchKernelGGL((nsf_rb16_kernel<K(), NTW, NW>), dim3(cdiv(Tl, 16 * NTW - 12 * (K() - 1)), B), dim3(64 * NW), 0,
+                       st, x, a, Tl, out, accum, rag_);
+  };
+  if (!dispatch(go, bool_of(geo == 2), one_of<3, 7, 11>(c1[0].taps))) {   // (rb_ok admits only these taps)
+    set_error("nsf rb16: not a shipped kernel size");
+    return PD_ERR_UNSUPPORTED;
   }
-#undef PD_RB16
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -1424,30 +1408,13 @@ int launch_wconv16(const NsfConv& c, const __bf16* wb, const void* in, bool in_b
   const size_t lds = (size_t)(256 + (c.taps - 1) * c.dil + 1) * 24 * sizeof(__bf16);   // + stage_window's spare row
   dim3 grid(cdiv(Tl, 256), B);
   ProfScope ps("nsf_res_small", st);
-#define PD_WCONV16T(IB, OB, K, D)                                                                                 \
-  hipLaunchKernelGGL((nsf_wconv16_kernel<IB, OB, K, D>), grid, dim3(256), lds, st, in, wb, c.kpad, c.b, c.taps,   \
-                     c.dil, alpha, scale, Tl, res, out, accum, rag_)
+  auto go = [&](auto IB, auto OB, auto K, auto D) {
+    hipLaunchKernelGGL((nsf_wconv16_kernel<IB(), OB(), K(), D()>), grid, dim3(256), lds, st, in, wb, c.kpad, c.b,
+                       c.taps, c.dil, alpha, scale, Tl, res, out, accum, rag_);
+  };
   // compile-time (taps, dilation) for the shipped ResBlock shapes, the runtime kernel otherwise
-#define PD_WCONV16(IB, OB)                                                                                        \
-  do {                                                                                                            \
-    const int K_ = c.kpad == 32 ? c.taps : 0, D_ = c.dil;                                                         \
-    if (K_ == 3 && D_ == 1) PD_WCONV16T(IB, OB, 3, 1);                                                            \
-    else if (K_ == 3 && D_ == 3) PD_WCONV16T(IB, OB, 3, 3);                                                       \
-    else if (K_ == 3 && D_ == 5) PD_WCONV16T(IB, OB, 3, 5);                                                       \
-    else if (K_ == 7 && D_ == 1) PD_WCONV16T(IB, OB, 7, 1);                                                       \
-    else if (K_ == 7 && D_ == 3) PD_WCONV16T(IB, OB, 7, 3);                                                       \
-    else if (K_ == 7 && D_ == 5) PD_WCONV16T(IB, OB, 7, 5);                                                       \
-    else if (K_ == 11 && D_ == 1) PD_WCONV16T(IB, OB, 11, 1);                                                     \
-    else if (K_ == 11 && D_ == 3) PD_WCONV16T(IB, OB, 11, 3);                                                     \
-    else if (K_ == 11 && D_ == 5) PD_WCONV16T(IB, OB, 11, 5);                                                     \
-    else PD_WCONV16T(IB, OB, 0, 0);                                                                               \
-  } while (0)
-  if (in_bf && out_bf) PD_WCONV16(true, true);
-  else if (in_bf) PD_WCONV16(true, false);
-  else if (out_bf) PD_WCONV16(false, true);
-  else PD_WCONV16(false, false);
-#undef PD_WCONV16
-#undef PD_WCONV16T
+  if (c.kpad != 32 || !dispatch(go, bool_of(in_bf), bool_of(out_bf), one_of<3, 7, 11>(c.taps), one_of<1, 3, 5>(c.dil)))
+    dispatch([&](auto IB, auto OB) { go(IB, OB, Const<0>{}, Const<0>{}); }, bool_of(in_bf), bool_of(out_bf));
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -1655,24 +1622,16 @@ int launch_ups_c(const NsfUps& U, const __bf16* wb, const float* in, float scale
   // input window + stage_window's spare row (+ NC: the source window and its spare slot)
   const size_t win = (size_t)((U.ntap + TQ + 1) * (CIN + 8) + 7) / 8 * 8 * sizeof(__bf16);
   const size_t lds = win + (nz.har ? (size_t)(TQ * U.u * nz.stride + nz.k + 1) * sizeof(float) : 0);
-  static const hipError_t attr = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  static const hipError_t attr_nc = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD, true>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr != hipSuccess || attr_nc != hipSuccess) { set_error("nsf ups: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
+  PD_TRY((raise_dynamic_lds<&nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD>>(160 * 1024, "nsf ups")));
+  PD_TRY((raise_dynamic_lds<&nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD, true>>(160 * 1024, "nsf ups")));
   if (lds > 160 * 1024) { set_error("nsf ups: LDS window too large"); return PD_ERR_UNSUPPORTED; }
   dim3 grid(cdiv(Tin, TQ), NPAD ? 1 : U.cout / TN, B);
   ProfScope ps("nsf_ups", st);
-  if (nz.har)
-    hipLaunchKernelGGL((nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD, true>), grid, dim3(256), lds, st, in, wb,
+  dispatch([&](auto NC) {
+    hipLaunchKernelGGL((nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD, NC()>), grid, dim3(256), lds, st, in, wb,
                        (long long)(U.w[1] - U.w[0]), U.kpad, U.ntap, U.u, p, 1 - U.ntap, U.cout, U.b, NSF_LRELU,
                        scale, Tin, res, out, rag_, nz);
-  else
-    hipLaunchKernelGGL((nsf_ups_kernel<CIN, FM, FN, WM, WN, NPAD>), grid, dim3(256), lds, st, in, wb,
-                       (long long)(U.w[1] - U.w[0]), U.kpad, U.ntap, U.u, p, 1 - U.ntap, U.cout, U.b, NSF_LRELU,
-                       scale, Tin, res, out, rag_, nz);
+  }, bool_of(nz.har != nullptr));
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -1714,30 +1673,17 @@ int launch_wconv_c(const NsfConv& c, const __bf16* wb, const void* in, bool in_b
   if (lds > 160 * 1024) { set_error("nsf conv: LDS window too large"); return PD_ERR_UNSUPPORTED; }
   dim3 grid(cdiv(Tl, TM), C / TN, B);
   const int ldw = c.taps * c.kpad;
-#define PD_WCONV(IB, OB)                                                                                          \
-  do {                                                                                                            \
-    static const hipError_t attr = hipFuncSetAttribute(                                                           \
-        reinterpret_cast<const void*>(&nsf_wconv_kernel<C, FM, FN, WM, WN, IB, OB>),                              \
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                                  \
-    if (attr != hipSuccess) { set_error("nsf conv: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }    \
-    hipLaunchKernelGGL((nsf_wconv_kernel<C, FM, FN, WM, WN, IB, OB>), grid, dim3(64 * WM * WN), lds, st, in, wb, ldw, \
-                       c.kpad, c.b, c.taps, c.dil, alpha, scale, Tl, res, out, accum, rag_);                        \
-  } while (0)
   ProfScope ps("nsf_res", st);
-  if (in_bf && out_bf) PD_WCONV(true, true);
-  else if (in_bf) PD_WCONV(true, false);
-  else if (out_bf) PD_WCONV(false, true);
-  else PD_WCONV(false, false);
-#undef PD_WCONV
+  int rc = PD_OK;
+  dispatch([&](auto IB, auto OB) {
+    constexpr auto kernel = &nsf_wconv_kernel<C, FM, FN, WM, WN, IB(), OB()>;
+    if ((rc = raise_dynamic_lds<kernel>(160 * 1024, "nsf conv")) != PD_OK) return;
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * WM * WN), lds, st, in, wb, ldw, c.kpad, c.b, c.taps, c.dil, alpha,
+                       scale, Tl, res, out, accum, rag_);
+  }, bool_of(in_bf), bool_of(out_bf));
+  PD_TRY(rc);
   PD_LAUNCH_CHECK();
   return PD_OK;
-}
-
-// The windowed conv for this ResBlock conv, if it has one (bf16 weights, C in {16..256}); on the
-// bf16 path it takes precedence over NSF_OPT_SMALL_MAX, which then only routes the fp32 path.
-bool wconv_ok(const NsfConv& c) {
-  return c.wconv && c.cin == c.cout && c.taps <= 11 && lookup_bf16(c.w) != nullptr &&
-         (c.cout == 16 || c.cout == 32 || c.cout == 64 || c.cout == 128 || c.cout == 256);
 }
 
 // accum = 1: out (fp32) += conv + res -- the ResBlock sum xs += resblock_j(x) (models.py:275-279)
@@ -1853,6 +1799,211 @@ int nsf_conv(const NsfConv& c, const float* in, float in_alpha, float in_scale, 
   if (use == U_NSF_CONV_PRE) return launch_gemm<1, 2, 4, 1, EPI_STORE, U_NSF_CONV_PRE>(a, st, "nsf_conv_pre");
   // (a 256 x 32 tile for the 32-channel stage measured slower: 11.9 vs 9.9 ms per step)
   return launch_gemm<1, 2, 4, 1, EPI_STORE, U_NSF_RES>(a, st, "nsf_res");
+}
+
+// ---------------------------------------------------------------- the stages of nsf_forward
+// What the stages of one call share.  Ragged batch: a stage of `rate` rows per mel frame reads zero past
+// lens[b] * rate (the phase prefix and the source are causal per utterance, so frames past an utterance's end
+// change nothing before it).
+struct NsfCall {
+  const nsf_model* m;
+  int B, T;
+  const int* lens;
+  hipStream_t st;
+  float *T1, *R, *XS;   // workspace [B][rows][C]: a ResBlock's scratch, the result of ResBlock j > 0, the stage's sum
+  NsfRag rag(int rate) const { NsfRag g; g.lens = lens; g.rate = rate; return g; }
+};
+
+// har [B][T * upp] = the harmonic source of f0 (models.py:100-219); P, Rd: the per-frame phase prefix and rad
+int nsf_source(const NsfCall& c, const float* f0, const float* rand_ini, const float* noise, unsigned long long seed,
+               const int* utt_ids, double* P, float* Rd, float* har) {
+  const nsf_model* m = c.m;
+  const float sr = (float)m->d.sampling_rate;
+  {
+    ProfScope ps("nsf_source", c.st);
+    hipLaunchKernelGGL(nsf_phase_prefix_kernel, dim3(c.B * m->dim), dim3(NSF_PP_THREADS), 0, c.st, f0, c.B, c.T, m->dim,
+                       sr, rand_ini, seed, utt_ids, P, Rd);
+    hipLaunchKernelGGL(nsf_source_kernel, dim3(cdiv((long long)c.B * c.T * m->upp, 256)), dim3(256), 0, c.st, f0, P, Rd,
+                       c.B, c.T, m->upp, m->dim, sr, rand_ini, noise, seed, utt_ids, m->lin_w, m->lin_b, har);
+  }
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// out [B][T][C0] = conv_pre(mel_scale * mel^T) (nsf_hifigan.py:53, models.py:267)
+int nsf_conv_pre(const NsfCall& c, const float* mel, float mel_scale, float* out) {
+  const NsfConv& cv = c.m->pre;
+  const int nm = c.m->d.num_mels;
+  GemmArgs a = make_gemm(c.B, c.T, cv.cout, cv.w, 7 * cv.kpad, cv.b, out, (long long)c.T * cv.cout, cv.cout);
+  for (int k = 0; k < 7; ++k) {
+    Seg s = make_seg(mel, (long long)c.T * nm, nm, nm, k - 3);
+    s.kpad = cv.kpad;
+    s.scale = mel_scale;
+    add_seg(a, s);
+  }
+  a.lens = c.lens; a.lens_mul = 1;
+  return launch_gemm<1, 2, 4, 1, EPI_STORE, U_NSF_CONV_PRE>(a, c.st, "nsf_conv_pre");
+}
+
+// The noise conv of upsample stage U over har (models.py:271-272), Lc output rows per utterance: either left
+// to the windowed upsample (*nz filled, nothing launched) or written to `out` [B][Lc][cout] for it to add.
+int nsf_noise_conv(const NsfCall& c, const NsfUps& U, bool upsw, const float* har, int Lc, float* out, NsfNoise* nz) {
+  const nsf_model* m = c.m;
+  const long long L = (long long)c.T * m->upp;
+  // NSF_OPT_UPS_NC: the windowed upsample computes the noise conv itself (short source kernels:
+  // the last three stages); otherwise nsf_noise_conv_kernel writes it for the upsample to add
+  if (upsw && m->ups_nc && U.nc_k <= NSF_NC_KMAX) {
+    nz->har = har; nz->L = L; nz->w = U.nc_w; nz->b = U.nc_b;
+    nz->k = U.nc_k; nz->stride = U.nc_stride; nz->pad = U.nc_pad; nz->rag = c.rag(m->upp);
+    return PD_OK;
+  }
+  ProfScope ps("nsf_noise_conv", c.st);
+  // (NSF_OPT_NC_MFMA 1: the K = 128 conv only; 2 (default): the K = 16 one too.  C5: 104-105 -> 91-93 us per
+  // launch, profiles/r06_ab/nsf_c256_noise_ab.txt)
+  if (m->nc_mfma && U.nc_stride * 2 == U.nc_k && (U.nc_k == 128 || (U.nc_k == 16 && m->nc_mfma == 2)) &&
+      U.cout % 32 == 0) {
+    dispatch([&](auto K) {
+      hipLaunchKernelGGL(nsf_noise_mfma_kernel<K()>, dim3(cdiv(Lc, 128), U.cout / 32, c.B), dim3(256), 0, c.st, har, L,
+                         U.nc_w, U.nc_b, U.cout, U.nc_pad, (long long)Lc, out, c.rag(m->upp));
+    }, one_of<128, 16>(U.nc_k));
+  } else {
+    const int CT = U.cout < 256 ? U.cout : 256, G = 256 / CT;
+    const size_t lds = (size_t)((G * NC_ROWS - 1) * U.nc_stride + U.nc_k) * sizeof(float);
+    hipLaunchKernelGGL(nsf_noise_conv_kernel, dim3(cdiv(Lc, G * NC_ROWS), U.cout / CT, c.B), dim3(256), lds, c.st, har,
+                       L, U.nc_w, U.nc_b, U.cout, U.nc_k, U.nc_stride, U.nc_pad, (long long)Lc, out, c.rag(m->upp));
+  }
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// out [B][Tin * u][cout] = ups(leaky_relu(in_scale * in, 0.1)) + noise_conv(har)  (models.py:270-274): the
+// windowed bf16 kernel (noise conv from nz, or read from `src`), or one GEMM per phase adding `src`
+int nsf_upsample(const NsfCall& c, const NsfUps& U, bool upsw, const float* in, float in_scale, int Tin,
+                 const float* src, const NsfNoise& nz, float* out) {
+  if (upsw) return launch_ups_window(U, in, in_scale, c.B, Tin, src, out, c.st, c.rag(Tin / c.T), nz);
+  const int Lc = Tin * U.u, p = (U.k - U.u) / 2;
+  for (int phi = 0; phi < U.u; ++phi) {
+    const int q0 = U.qmin[phi];
+    const int o = q0 * U.u + phi - p;        // first output row of this phase, in [0, u)
+    GemmArgs a = make_gemm(c.B, Tin, U.cout, U.w[phi], U.ntap * U.kpad, U.b, out + (long long)o * U.cout,
+                           (long long)Lc * U.cout, U.u * U.cout);
+    for (int mt = 0; mt < U.ntap; ++mt) {
+      Seg s = make_seg(in, (long long)Tin * U.cin, U.cin, U.cin, q0 - mt);
+      s.kpad = U.kpad;
+      s.act = ACT_LRELU;
+      s.alpha = NSF_LRELU;
+      s.scale = in_scale;
+      add_seg(a, s);
+    }
+    a.res = src + (long long)o * U.cout;
+    a.res_bs = (long long)Lc * U.cout;
+    a.res_ld = U.u * U.cout;
+    a.lens = c.lens; a.lens_mul = Tin / c.T;
+    PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_NSF_UPS>(a, c.st, "nsf_ups")));
+  }
+  return PD_OK;
+}
+
+// ResBlock1 j of a stage whose three pairs are m->res[r ..] as one launch (r06: x read once, xs written
+// (j == 0) / added (j > 0) once), if it has one (*done)
+int nsf_resblock_whole(const NsfCall& c, size_t r, int j, const float* x, int Lc, bool* done) {
+  const nsf_model* m = c.m;
+  const int D = m->d.num_dilations;
+  *done = false;
+  if (m->d.resblock != 1 || D != 3) return PD_OK;
+  NsfConv c1s[3], c2s[3];
+  for (int q = 0; q < 3; ++q) { c1s[q] = m->res[r + q]; c2s[q] = m->res[r + D + q]; }
+  const int Cr = c1s[0].cout;
+  if (!((Cr == 16 || Cr == 32 || Cr == 64) && rb_ok(m, c1s, c2s, Cr))) return PD_OK;
+  if ((long long)c.B * Lc * Cr >= (1ll << 31)) { set_error("nsf rb: B * T * C >= 2^31"); return PD_ERR_UNSUPPORTED; }
+  *done = true;
+  if (Cr == 16) return launch_rb16(c1s, c2s, x, c.B, Lc, c.XS, j > 0 ? 1 : 0, c.st, c.rag(Lc / c.T), m->rb16);
+  return launch_rb(c1s, c2s, x, c.B, Lc, c.XS, j > 0 ? 1 : 0, c.st, c.rag(Lc / c.T));
+}
+
+// One (c1, c2) pair q of ResBlock1 j: *cur -> x + c2(lrelu(c1(lrelu(x)))) (models.py:57-63), landing in the
+// block's result buffer (XS for j == 0, else R) or in T1; *summed: the last pair of a block j > 0 added into XS.
+int nsf_resblock1_pair(const NsfCall& c, const NsfConv& c1, const NsfConv& c2, int j, int q, int Lc,
+                       const float** cur, bool* summed) {
+  const int D = c.m->d.num_dilations;
+  float *T1 = c.T1, *XS = c.XS, *target = j == 0 ? c.XS : c.R;
+  const NsfRag rag_ = c.rag(Lc / c.T);
+  const bool last_acc = j > 0 && q == D - 1;
+  if (pair_ok(c.m, c1, c2)) {
+    // one launch per pair; it reads neighbouring blocks' rows of cur, so it never writes
+    // cur: the pairs alternate between T1 (fp32 here) and target (XS / R), the last one
+    // landing in target -- or accumulating into XS for resblock j >= 1
+    float* dst = q == D - 1 ? (last_acc ? XS : target) : ((D - 2 - q) % 2 == 0 ? T1 : target);
+    PD_TRY(launch_pair(c1, c2, *cur, c.B, Lc, dst, last_acc ? 1 : 0, c.st, rag_));
+    if (last_acc) *summed = true;
+    else *cur = dst;
+    return PD_OK;
+  }
+  if (wconv_ok(c1) && wconv_ok(c2)) {
+    // windowed bf16 convs; the inner activation xt = c1(lrelu(x)) travels as bf16; the
+    // last pair of resblock j >= 1 accumulates straight into XS
+    PD_TRY(launch_wconv(c1, *cur, false, NSF_LRELU, 1.f, c.B, Lc, T1, true, nullptr, c.st, 0, rag_));
+    PD_TRY(launch_wconv(c2, T1, true, NSF_LRELU, 1.f, c.B, Lc, last_acc ? XS : target, false, *cur, c.st,
+                        last_acc ? 1 : 0, rag_));
+    if (last_acc) { *summed = true; return PD_OK; }
+  } else {
+    PD_TRY(nsf_conv(c1, *cur, NSF_LRELU, 1.f, c.B, Lc, T1, nullptr, ACT_NONE, c.st, U_NSF_RES, rag_));
+    PD_TRY(nsf_conv(c2, T1, NSF_LRELU, 1.f, c.B, Lc, target, *cur, ACT_NONE, c.st, U_NSF_RES, rag_));
+  }
+  *cur = target;
+  return PD_OK;
+}
+
+// ResBlock j of a stage (convs m->res[r ..]) over x [B][Lc][C], added into the stage's sum XS
+// (xs = sum_j resblock_j(x), models.py:275-279; j == 0 stores).  *in_xs: the block's own launches already left
+// it there; otherwise *y is the buffer (T1, R or XS's alias) that holds resblock_j(x) for nsf_accum.
+int nsf_resblock(const NsfCall& c, size_t r, int j, const float* x, int Lc, bool* in_xs, const float** y) {
+  const nsf_model* m = c.m;
+  const int D = m->d.num_dilations;
+  PD_TRY(nsf_resblock_whole(c, r, j, x, Lc, in_xs));
+  if (*in_xs) return PD_OK;
+  float* target = j == 0 ? c.XS : c.R;
+  const float* cur = x;
+  for (int q = 0; q < D; ++q) {
+    if (m->d.resblock == 1) {
+      PD_TRY(nsf_resblock1_pair(c, m->res[r + q], m->res[r + D + q], j, q, Lc, &cur, in_xs));
+    } else {
+      // out must not alias the taps being read: ping-pong target <-> T1
+      float* dst = (cur == target) ? c.T1 : target;
+      const NsfConv& cv = m->res[r + q];
+      if (wconv_ok(cv))
+        PD_TRY(launch_wconv(cv, cur, false, NSF_LRELU, 1.f, c.B, Lc, dst, false, cur, c.st, 0, c.rag(Lc / c.T)));
+      else
+        PD_TRY(nsf_conv(cv, cur, NSF_LRELU, 1.f, c.B, Lc, dst, cur, ACT_NONE, c.st, U_NSF_RES, c.rag(Lc / c.T)));
+      cur = dst;
+    }
+  }
+  if (j == 0 && cur == c.XS) *in_xs = true;
+  *y = cur;
+  return PD_OK;
+}
+
+// xs = y (assign) or xs += y, n4 float4 each
+int nsf_accum(float* xs, const float* y, long long n4, bool assign, hipStream_t st) {
+  ProfScope ps("nsf_accum", st);
+  hipLaunchKernelGGL(nsf_accum_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, reinterpret_cast<float4*>(xs),
+                     reinterpret_cast<const float4*>(y), n4, assign ? 1 : 0);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// wav [B][Tin] = tanh(conv_post(leaky_relu(in_scale * in, 0.01)))  (models.py:280-282)
+int nsf_conv_post(const NsfCall& c, const float* in, float in_scale, int Tin, float* wav) {
+  const NsfConv& post = c.m->post;
+  if (!(post.taps == 7 && post.cout == 1 && (post.cin == 16 || post.cin == 32)))
+    return nsf_conv(post, in, 0.01f, in_scale, c.B, Tin, wav, nullptr, ACT_TANH, c.st, U_NSF_POST, c.rag(Tin / c.T));
+  ProfScope ps("nsf_post", c.st);
+  dispatch([&](auto C) {
+    hipLaunchKernelGGL(nsf_post_kernel<C()>, dim3(cdiv(Tin, 256), c.B), dim3(256), 0, c.st, in, post.w, post.kpad,
+                       post.b, 0.01f, in_scale, Tin, wav, c.rag(Tin / c.T));
+  }, one_of<16, 32>(post.cin));
+  PD_LAUNCH_CHECK();
+  return PD_OK;
 }
 
 }  // namespace
@@ -2065,184 +2216,35 @@ int nsf_forward(const nsf_model* m, const float* mel, float mel_scale, const flo
   const NsfWs W = nsf_layout(m, B, T);
   if (!workspace || ws_bytes < W.total) { set_error("workspace too small"); return PD_ERR_WORKSPACE; }
   PD_CHECK_ARG((reinterpret_cast<uintptr_t>(mel) & 15) == 0, "mel must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
-  const nsf_dims& d = m->d;
-  const int dim = m->dim, nk = d.num_kernels;
-  const long long L = (long long)T * m->upp;
-  double* P = reinterpret_cast<double*>(ws + W.P);
-  float* har = ws + W.har;
-  float *X = ws + W.X, *T1 = ws + W.T1, *R = ws + W.R, *XS = ws + W.XS, *XSRC = ws + W.src;
-  const float sr = (float)d.sampling_rate;
-  {
-    ProfScope ps("nsf_source", st);
-    float* Rd = ws + W.Rd;
-    hipLaunchKernelGGL(nsf_phase_prefix_kernel, dim3(B * dim), dim3(NSF_PP_THREADS), 0, st, f0, B, T, dim, sr,
-                       rand_ini, seed, utt_ids, P, Rd);
-    hipLaunchKernelGGL(nsf_source_kernel, dim3(cdiv((long long)B * L, 256)), dim3(256), 0, st, f0, P, Rd, B, T, m->upp,
-                       dim, sr, rand_ini, noise, seed, utt_ids, m->lin_w, m->lin_b, har);
-  }
-  PD_LAUNCH_CHECK();
-  // ragged batch: stage s of `rate` samples per frame reads zero past lens[b] * rate (the phase
-  // prefix and the source are causal per utterance, so frames past an utterance's end change nothing
-  // before it)
-  auto rag = [&](int rate) { NsfRag g; g.lens = lens; g.rate = rate; return g; };
-  // conv_pre(mel_scale * mel^T) (nsf_hifigan.py:53, models.py:267)
-  {
-    const NsfConv& c = m->pre;
-    GemmArgs a = make_gemm(B, T, c.cout, c.w, 7 * c.kpad, c.b, XS, (long long)T * c.cout, c.cout);
-    for (int k = 0; k < 7; ++k) {
-      Seg s = make_seg(mel, (long long)T * d.num_mels, d.num_mels, d.num_mels, k - 3);
-      s.kpad = c.kpad;
-      s.scale = mel_scale;
-      add_seg(a, s);
-    }
-    a.lens = lens; a.lens_mul = 1;
-    PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_NSF_CONV_PRE>(a, st, "nsf_conv_pre")));
-  }
+  const NsfCall c{m, B, T, lens, (hipStream_t)stream, ws + W.T1, ws + W.R, ws + W.XS};
+  const int nk = m->d.num_kernels;
+  float *har = ws + W.har, *X = ws + W.X, *XS = c.XS, *XSRC = ws + W.src;
+  PD_TRY(nsf_source(c, f0, rand_ini, noise, seed, utt_ids, reinterpret_cast<double*>(ws + W.P), ws + W.Rd, har));
+  PD_TRY(nsf_conv_pre(c, mel, mel_scale, XS));
   int Tin = T;
   float in_scale = 1.f;
   size_t r = 0;
-  for (int i = 0; i < d.num_upsamples; ++i) {
+  for (int i = 0; i < m->d.num_upsamples; ++i) {
     const NsfUps& U = m->ups[i];
     const int Lc = Tin * U.u;
     const bool upsw = ups_window_ok(U, m->ups_window);
-    // NSF_OPT_UPS_NC: the windowed upsample computes the noise conv itself (short source kernels:
-    // the last three stages); otherwise nsf_noise_conv_kernel writes it for the upsample to add
+    // x = ups(leaky_relu(x, 0.1)) + noise_conv(har)  (models.py:270-274)
     NsfNoise nz;
-    if (upsw && m->ups_nc && U.nc_k <= NSF_NC_KMAX) {
-      nz.har = har; nz.L = L; nz.w = U.nc_w; nz.b = U.nc_b;
-      nz.k = U.nc_k; nz.stride = U.nc_stride; nz.pad = U.nc_pad; nz.rag = rag(m->upp);
-    }
-    // (NSF_OPT_NC_MFMA 1: the K = 128 conv only; 2 (default): the K = 16 one too.  C5: 104-105 -> 91-93 us per
-    // launch, profiles/r06_ab/nsf_c256_noise_ab.txt)
-    if (!nz.har && m->nc_mfma && U.nc_stride * 2 == U.nc_k && (U.nc_k == 128 || (U.nc_k == 16 && m->nc_mfma == 2)) &&
-        U.cout % 32 == 0) {
-      ProfScope ps("nsf_noise_conv", st);
-      const dim3 grid(cdiv(Lc, 128), U.cout / 32, B);
-      if (U.nc_k == 128)
-        hipLaunchKernelGGL(nsf_noise_mfma_kernel<128>, grid, dim3(256), 0, st, har, L, U.nc_w, U.nc_b, U.cout,
-                           U.nc_pad, (long long)Lc, XSRC, rag(m->upp));
-      else
-        hipLaunchKernelGGL(nsf_noise_mfma_kernel<16>, grid, dim3(256), 0, st, har, L, U.nc_w, U.nc_b, U.cout,
-                           U.nc_pad, (long long)Lc, XSRC, rag(m->upp));
-      PD_LAUNCH_CHECK();
-    } else if (!nz.har) {
-      const int CT = U.cout < 256 ? U.cout : 256, G = 256 / CT;
-      const size_t lds = (size_t)((G * NC_ROWS - 1) * U.nc_stride + U.nc_k) * sizeof(float);
-      ProfScope ps("nsf_noise_conv", st);
-      hipLaunchKernelGGL(nsf_noise_conv_kernel, dim3(cdiv(Lc, G * NC_ROWS), U.cout / CT, B), dim3(256), lds, st, har,
-                         L, U.nc_w, U.nc_b, U.cout, U.nc_k, U.nc_stride, U.nc_pad, (long long)Lc, XSRC, rag(m->upp));
-      PD_LAUNCH_CHECK();
-    }
-    // x = ups(leaky_relu(x, 0.1)) + noise_conv(har)  (models.py:270-274): the windowed bf16
-    // kernel, or one GEMM per phase
-    const int p = (U.k - U.u) / 2;
-    if (upsw) PD_TRY(launch_ups_window(U, XS, in_scale, B, Tin, XSRC, X, st, rag(Tin / T), nz));
-    for (int phi = 0; phi < (upsw ? 0 : U.u); ++phi) {
-      const int q0 = U.qmin[phi];
-      const int o = q0 * U.u + phi - p;        // first output row of this phase, in [0, u)
-      GemmArgs a = make_gemm(B, Tin, U.cout, U.w[phi], U.ntap * U.kpad, U.b, X + (long long)o * U.cout,
-                             (long long)Lc * U.cout, U.u * U.cout);
-      for (int mt = 0; mt < U.ntap; ++mt) {
-        Seg s = make_seg(XS, (long long)Tin * U.cin, U.cin, U.cin, q0 - mt);
-        s.kpad = U.kpad;
-        s.act = ACT_LRELU;
-        s.alpha = NSF_LRELU;
-        s.scale = in_scale;
-        add_seg(a, s);
-      }
-      a.res = XSRC + (long long)o * U.cout;
-      a.res_bs = (long long)Lc * U.cout;
-      a.res_ld = U.u * U.cout;
-      a.lens = lens; a.lens_mul = Tin / T;
-      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_NSF_UPS>(a, st, "nsf_ups")));
-    }
+    PD_TRY(nsf_noise_conv(c, U, upsw, har, Lc, XSRC, &nz));
+    PD_TRY(nsf_upsample(c, U, upsw, XS, in_scale, Tin, XSRC, nz, X));
     // xs = sum_j resblock_j(x); x = xs / num_kernels (models.py:275-281); the division is
     // folded into the next consumer's load scale.
-    const long long n4 = (long long)B * Lc * U.cout / 4;
-    const NsfRag rag_ = rag(Lc / T);
-    for (int j = 0; j < nk; ++j) {
-      float* target = j == 0 ? XS : R;
-      const float* cur = X;
-      bool summed = false;   // resblock_j(x) already added into XS by its last conv
-      const int D = d.num_dilations;
-      if (d.resblock == 1 && D == 3) {
-        NsfConv c1s[3], c2s[3];
-        for (int q = 0; q < 3; ++q) { c1s[q] = m->res[r + q]; c2s[q] = m->res[r + D + q]; }
-        const int Cr = c1s[0].cout;
-        if ((Cr == 16 || Cr == 32 || Cr == 64) && rb_ok(m, c1s, c2s, Cr)) {
-          // r06: the whole ResBlock in one launch, x read once, xs written / added once
-          if ((long long)B * Lc * Cr >= (1ll << 31)) { set_error("nsf rb: B * T * C >= 2^31"); return PD_ERR_UNSUPPORTED; }
-          if (Cr == 16) PD_TRY(launch_rb16(c1s, c2s, X, B, Lc, XS, j > 0 ? 1 : 0, st, rag_, m->rb16));
-          else PD_TRY(launch_rb(c1s, c2s, X, B, Lc, XS, j > 0 ? 1 : 0, st, rag_));
-          r += m->convs_per_block;
-          continue;
-        }
-      }
-      for (int q = 0; q < D; ++q) {
-        if (d.resblock == 1) {
-          const NsfConv& c1 = m->res[r + q];
-          const NsfConv& c2 = m->res[r + D + q];
-          if (pair_ok(m, c1, c2)) {
-            // one launch per pair; it reads neighbouring blocks' rows of cur, so it never writes
-            // cur: the pairs alternate between T1 (fp32 here) and target (XS / R), the last one
-            // landing in target -- or accumulating into XS for resblock j >= 1
-            const bool last_acc = j > 0 && q == D - 1;
-            float* dst = q == D - 1 ? (last_acc ? XS : target) : ((D - 2 - q) % 2 == 0 ? T1 : target);
-            PD_TRY(launch_pair(c1, c2, cur, B, Lc, dst, last_acc ? 1 : 0, st, rag_));
-            if (last_acc) { summed = true; continue; }
-            cur = dst;
-            continue;
-          }
-          if (wconv_ok(c1) && wconv_ok(c2)) {
-            // windowed bf16 convs; the inner activation xt = c1(lrelu(x)) travels as bf16; the
-            // last pair of resblock j >= 1 accumulates straight into XS
-            const bool last_acc = j > 0 && q == d.num_dilations - 1;
-            PD_TRY(launch_wconv(c1, cur, false, NSF_LRELU, 1.f, B, Lc, T1, true, nullptr, st, 0, rag_));
-            PD_TRY(launch_wconv(c2, T1, true, NSF_LRELU, 1.f, B, Lc, last_acc ? XS : target, false, cur, st,
-                                last_acc ? 1 : 0, rag_));
-            if (last_acc) { summed = true; continue; }
-          } else {
-            PD_TRY(nsf_conv(c1, cur, NSF_LRELU, 1.f, B, Lc, T1, nullptr, ACT_NONE, st, U_NSF_RES, rag_));
-            PD_TRY(nsf_conv(c2, T1, NSF_LRELU, 1.f, B, Lc, target, cur, ACT_NONE, st, U_NSF_RES, rag_));
-          }
-          cur = target;
-        } else {
-          // out must not alias the taps being read: ping-pong target <-> T1
-          float* dst = (cur == target) ? T1 : target;
-          if (wconv_ok(m->res[r + q]))
-            PD_TRY(launch_wconv(m->res[r + q], cur, false, NSF_LRELU, 1.f, B, Lc, dst, false, cur, st, 0, rag_));
-          else
-            PD_TRY(nsf_conv(m->res[r + q], cur, NSF_LRELU, 1.f, B, Lc, dst, cur, ACT_NONE, st, U_NSF_RES, rag_));
-          cur = dst;
-        }
-      }
-      r += m->convs_per_block;
-      if (summed) continue;
-      if (j == 0 && cur == XS) continue;
-      ProfScope ps("nsf_accum", st);
-      hipLaunchKernelGGL(nsf_accum_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, reinterpret_cast<float4*>(XS),
-                         reinterpret_cast<const float4*>(cur), n4, j == 0 ? 1 : 0);
-      PD_LAUNCH_CHECK();
+    for (int j = 0; j < nk; ++j, r += m->convs_per_block) {
+      bool in_xs = false;
+      const float* y = nullptr;
+      PD_TRY(nsf_resblock(c, r, j, X, Lc, &in_xs, &y));
+      if (!in_xs) PD_TRY(nsf_accum(XS, y, (long long)B * Lc * U.cout / 4, j == 0, c.st));
     }
     Tin = Lc;
     in_scale = 1.f / (float)nk;
   }
-  // tanh(conv_post(leaky_relu(x, 0.01)))  (models.py:280-282)
-  if (m->post.taps == 7 && m->post.cout == 1 && (m->post.cin == 16 || m->post.cin == 32)) {
-    ProfScope ps("nsf_post", st);
-    if (m->post.cin == 16)
-      hipLaunchKernelGGL(nsf_post_kernel<16>, dim3(cdiv(Tin, 256), B), dim3(256), 0, st, XS, m->post.w, m->post.kpad,
-                         m->post.b, 0.01f, in_scale, Tin, wav, rag(Tin / T));
-    else
-      hipLaunchKernelGGL(nsf_post_kernel<32>, dim3(cdiv(Tin, 256), B), dim3(256), 0, st, XS, m->post.w, m->post.kpad,
-                         m->post.b, 0.01f, in_scale, Tin, wav, rag(Tin / T));
-    PD_LAUNCH_CHECK();
-  } else {
-    PD_TRY(nsf_conv(m->post, XS, 0.01f, in_scale, B, Tin, wav, nullptr, ACT_TANH, st, U_NSF_POST, rag(Tin / T)));
-  }
-  return PD_OK;
+  return nsf_conv_post(c, XS, in_scale, Tin, wav);
 }
 
 }  // extern "C"

@@ -368,9 +368,7 @@ int pd_resample_forward(const pd_resample* h, const float* wav, const int* lens,
   PD_CHECK_ARG(h && wav && out, "null pointer");
   PD_CHECK_ARG(B > 0 && B <= 65535, "B must lie in [1, 65535]");
   PD_CHECK_ARG(L > 0, "L must be positive");
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&resample_forward_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_MAX_LDS);
-  if (attr != hipSuccess) { set_error("resample: cannot raise the dynamic LDS limit"); return PD_ERR_HIP; }
+  PD_TRY(raise_dynamic_lds<&resample_forward_kernel>((int)RS_MAX_LDS, "resample"));
   RsArgs a{};
   a.wav = wav; a.lens = lens; a.tab = h->tab; a.out = out; a.L = L; a.Lout = (long long)pd_resample_out_samples(h, L); a.p = h->p;
   const long long nblk = (a.Lout + (long long)RS_TF * h->p.N - 1) / ((long long)RS_TF * h->p.N);

@@ -633,19 +633,11 @@ int launch_conv(const Conv& cw, const VrSrc& s0, const VrSrc* s1, int B, int Hi,
     return PD_ERR_ARG;
   }
   ProfScope ps(tag, st);
-#define VR_CONV(TAPS, UP, NT) hipLaunchKernelGGL((vr_conv_kernel<TAPS, UP, NT>), grid, dim3(256), 0, st, a)
-#define VR_CONV_NT(TAPS, UP) \
-  switch (nt) {              \
-    case 1: VR_CONV(TAPS, UP, 1); break; \
-    case 2: VR_CONV(TAPS, UP, 2); break; \
-    case 3: VR_CONV(TAPS, UP, 3); break; \
-    default: VR_CONV(TAPS, UP, 4); break; \
-  }
-  if (cw.taps != 9) { VR_CONV_NT(1, false) }
-  else if (up) { VR_CONV_NT(9, true) }
-  else { VR_CONV_NT(9, false) }
-#undef VR_CONV_NT
-#undef VR_CONV
+  dispatch([&](auto NT) {
+    dispatch_rows<DispatchRow<1, false>, DispatchRow<9, true>, DispatchRow<9, false>>([&](auto TAPS, auto UP) {
+      hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT()>), grid, dim3(256), 0, st, a);
+    }, cw.taps != 9 ? 1 : 9, cw.taps == 9 && up);
+  }, one_of<1, 2, 3, 4>(nt));
   PD_LAUNCH_CHECK();
   return PD_OK;
 }

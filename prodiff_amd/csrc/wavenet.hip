@@ -1443,25 +1443,6 @@ int launch_small_gemm(const GemmArgs& a, hipStream_t st, const char* tag) {
   return launch_gemm<1, 1, 1, 4, EPI, ID>(a, st, tag);
 }
 
-// One stack launch: the instantiation for the launch's stage (IN / TAIL / middle), ragged or dense,
-// dilation cycle 1 or longer.
-template <bool RAG, bool DIL>
-void launch_wn_stack_v(const WnStackArgs& P, dim3 grid, hipStream_t st) {
-  if (P.spec) hipLaunchKernelGGL((wn_stack_bf16_kernel<true, 0, RAG, DIL>), grid, dim3(512), 0, st, P);
-  else if (P.Wsb && P.noise) hipLaunchKernelGGL((wn_stack_bf16_kernel<false, 2, RAG, DIL>), grid, dim3(512), 0, st, P);
-  else if (P.Wsb) hipLaunchKernelGGL((wn_stack_bf16_kernel<false, 1, RAG, DIL>), grid, dim3(512), 0, st, P);
-  else hipLaunchKernelGGL((wn_stack_bf16_kernel<false, 0, RAG, DIL>), grid, dim3(512), 0, st, P);
-}
-void launch_wn_stack(const WnStackArgs& P, dim3 grid, bool dil, hipStream_t st) {
-  if (P.lens) {
-    if (dil) launch_wn_stack_v<true, true>(P, grid, st);
-    else launch_wn_stack_v<true, false>(P, grid, st);
-  } else {
-    if (dil) launch_wn_stack_v<false, true>(P, grid, st);
-    else launch_wn_stack_v<false, false>(P, grid, st);
-  }
-}
-
 // A ProDiff sampler pass's output stage (prodiff.py:106-126) for wavenet_core to fuse into the
 // last stack launch: x0 = W_out relu(W_skip skip / sqrt(L) + b) + b_out, then the posterior update.
 struct StackTail {
@@ -1474,264 +1455,341 @@ struct StackTail {
   unsigned stream_id;
   const int* uid;
 };
+// the posterior's part of a kernel argument struct (WnStackArgs, WnF32TailArgs: the same field names)
+template <class Args> void set_tail(Args& a, const StackTail& t) {
+  a.mel = t.mel; a.c1 = t.c1; a.c2 = t.c2; a.sigma = t.sigma;
+  a.noise = t.noise; a.noise_bs = t.noise_bs; a.noise_ld = t.noise_ld;
+  a.seed = t.seed; a.stream_id = t.stream_id; a.uid = t.uid;
+}
 
-// Input projection + residual stack + skip head.  xin: time-major [B][T][M];
-// cond: time-major [B][T][H]; dproj: [B][L][C].  Leaves relu(skip head) in ws.hs -- or, when
-// `tail` is given and the stack kernel fuses it (PD_WN_OPT_STACK_FUSE), applies the whole output
-// stage itself and sets *tail_done.
-// lens (device, B ints, or null): each row's utterance length in frames -- a ragged batch whose rows
-// are padded to T; every dilated conv reads zero past the row's own end, so each utterance's
-// frames equal a run of that utterance alone (B = 1, T = lens[b]).
+// What the stages of one wavenet_core call share.  cond: time-major [B][T][H]; dproj: [B][L][C]; lens (device,
+// B ints, or null): each row's utterance length in frames -- a ragged batch whose rows are padded to T; every
+// dilated conv reads zero past the row's own end, so each utterance's frames equal a run of that utterance
+// alone (B = 1, T = lens[b]).  The residual stream is ws.x, the skip sum ws.skip.
+struct WnCall {
+  const pd_wavenet* h;
+  float* ws;
+  const WsLayout& Lw;
+  const float* cond;
+  const float* dproj;
+  int B, T;
+  const int* lens;
+  hipStream_t st;
+  int rows() const { return B * T; }
+};
+
+// bf16 layer implementation (PD_WN_OPT_LAYER 1): GATE + RESSKIP launches per residual layer
+// (wn_gate_bf16_kernel, wn_resskip_bf16_kernel).  Not the default: at B*T = 1722 .. 27552 frames it measured
+// equal to or slower than the fused kernel.
+int wn_layers_two(const WnCall& c) {
+  const pd_wavenet* h = c.h;
+  const int H = h->H, C = h->C, Ly = h->L, rows = c.rows(), T = c.T;
+  float* x = c.ws + c.Lw.x;
+  __bf16* xa = reinterpret_cast<__bf16*>(c.ws + c.Lw.xa);
+  __bf16* condb = reinterpret_cast<__bf16*>(c.ws + c.Lw.condb);
+  __bf16* gb = reinterpret_cast<__bf16*>(c.ws + c.Lw.g);
+  {
+    ProfScope ps("wn_xa", c.st);
+    const long long n4 = ((long long)rows * (C > H ? C : H) + 3) / 4;
+    hipLaunchKernelGGL(wn_xa_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, c.st, x, c.dproj, Ly * C, xa, c.cond, condb,
+                       rows, T, C, H);
+    PD_LAUNCH_CHECK();
+  }
+  const int K1 = 3 * C + H;
+  for (int l = 0; l < Ly; ++l) {
+    WnGateArgs G{};
+    G.xa = xa; G.condb = condb; G.Wp = h->W1p + (size_t)l * 2 * C * K1; G.b1 = h->bl1 + (size_t)l * 2 * C;
+    G.g = gb; G.rows = rows; G.T = T; G.dil = 1 << (l % h->cyc);
+    {
+      ProfScope ps("wn_gate2", c.st);
+      dispatch([&](auto DW) {
+        hipLaunchKernelGGL(wn_gate_bf16_kernel<DW()>, dim3(cdiv(rows, WG2_ROWS), C / 64), dim3(512), 0, c.st, G);
+      }, one_of<1, 16>(h->cyc == 1 ? 1 : 16));
+      PD_LAUNCH_CHECK();
+    }
+    const bool last = l == Ly - 1;
+    WnResSkipArgs P{};
+    P.g = gb; P.W2f = h->W2f + (size_t)l * 2 * C * C; P.b2 = h->bl2 + (size_t)l * 2 * C;
+    P.x = x; P.skip = c.ws + c.Lw.skip; P.first = l == 0;
+    P.xa_next = last ? nullptr : xa; P.dp_next = last ? nullptr : c.dproj + (size_t)(l + 1) * C; P.dp_ld = Ly * C;
+    // the last layer's residual half feeds nothing (wavenet.py:115-119 keeps only skip)
+    P.nt0 = last ? C / 32 : 0;
+    P.rows = rows; P.T = T;
+    {
+      ProfScope ps("wn_resskip2", c.st);
+      hipLaunchKernelGGL(wn_resskip_bf16_kernel<WN_RS_RQ>, dim3(cdiv(rows, 32 * WN_RS_RQ), (last ? C : 2 * C) / 128),
+                         dim3(256), 0, c.st, P);
+      PD_LAUNCH_CHECK();
+    }
+  }
+  return PD_OK;
+}
+
+// The stack launches' layer groups [grp[k][0], grp[k + 1][0]): at most stack_nl layers whose dilations sum
+// (grp[k][1]) to at most the window's halo budget (cycle 1: nl layers, halo nl; cycle 5: {1,2,4,8}, {16}, ...)
+int wn_stack_groups(const pd_wavenet* h, int grp[64][2]) {
+  int ngrp = 0;
+  for (int l0 = 0; l0 < h->L && ngrp < 64;) {
+    int nl = 0, sum = 0;
+    while (l0 + nl < h->L && nl < h->stack_nl) {
+      const int d = 1 << ((l0 + nl) % h->cyc);
+      if (nl > 0 && sum + d > WST_HMAX) break;
+      sum += d;
+      ++nl;
+    }
+    grp[ngrp][0] = l0; grp[ngrp][1] = sum;
+    ++ngrp;
+    l0 += nl;
+  }
+  return ngrp;
+}
+
+// What the first and the last stack launch fuse (PD_WN_OPT_STACK_FUSE): in -- x = relu(W_in spec + b) of the
+// window rows from xin [B][T][M]; tail -- the sampler pass's output stage, or null
+struct WnStackFuse {
+  const float* xin = nullptr;
+  const __bf16* Winb = nullptr;   // bf16 mirrors of W_in, W_skip, W_out
+  const StackTail* tail = nullptr;
+  const __bf16 *Wsb = nullptr, *Wob = nullptr;
+};
+
+// One stack launch: the instantiation for the launch's stage (IN / TAIL / middle), ragged or dense,
+// dilation cycle 1 or longer.
+void launch_wn_stack(const WnStackArgs& P, dim3 grid, bool dil, hipStream_t st) {
+  const int tail = P.spec || !P.Wsb ? 0 : P.noise ? 2 : 1;
+  dispatch([&](auto RAG, auto DIL) {
+    dispatch_rows<DispatchRow<true, 0>, DispatchRow<false, 2>, DispatchRow<false, 1>, DispatchRow<false, 0>>([&](auto IN, auto TAIL) {
+      hipLaunchKernelGGL((wn_stack_bf16_kernel<IN(), TAIL(), RAG(), DIL()>), grid, dim3(512), 0, st, P);
+    }, P.spec != nullptr, tail);
+  }, bool_of(P.lens != nullptr), bool_of(dil));
+}
+
+// The fused output stage of the last stack launch: skip head, output projection and posterior
+void wn_stack_fuse_tail(WnStackArgs& P, const pd_wavenet* h, const WnStackFuse& fuse) {
+  P.Wsb = fuse.Wsb; P.bs = h->bs; P.Wob = fuse.Wob; P.bo = h->bo; P.M = h->M;
+  P.skip_scale = 1.0f / sqrtf((float)h->L);   // the skip head's segment scale (wn_skip_head)
+  set_tail(P, *fuse.tail);
+}
+
+// bf16: the layer groups, one wn_stack_bf16_kernel launch each, x ping-pongs x <-> x2
+int wn_layers_stack(const WnCall& c, const int grp[64][2], int ngrp, const WnStackFuse& fuse) {
+  const pd_wavenet* h = c.h;
+  const int H = h->H, C = h->C, Ly = h->L, rows = c.rows();
+  __bf16* condb = reinterpret_cast<__bf16*>(c.ws + c.Lw.condb);
+  {
+    ProfScope ps("wn_condb", c.st);
+    hipLaunchKernelGGL(wn_xa_kernel, dim3(cdiv(((long long)rows * H + 3) / 4, 256)), dim3(256), 0, c.st, nullptr,
+                       nullptr, 0, nullptr, c.cond, condb, rows, c.T, C, H);
+    PD_LAUNCH_CHECK();
+  }
+  float* xb[2] = {c.ws + c.Lw.x, c.ws + c.Lw.x2};
+  for (int k = 0; k < ngrp; ++k) {
+    const int l0 = grp[k][0], l1 = k + 1 < ngrp ? grp[k + 1][0] : Ly;
+    WnStackArgs P{};
+    P.xin = xb[k & 1]; P.xout = xb[(k + 1) & 1]; P.skip = c.ws + c.Lw.skip; P.condb = condb;
+    P.dp = c.dproj; P.dp_ld = Ly * C;
+    P.W1f = h->W1f; P.b1 = h->bl1; P.W2f = h->W2f; P.b2 = h->bl2;
+    P.rows = rows; P.T = c.T; P.l0 = l0; P.nl = l1 - l0; P.first = l0 == 0; P.L = Ly;
+    P.lens = c.lens; P.cyc = h->cyc;
+    // output rows per block (PD_WN_OPT_STACK_RO; r04 default 32).  r04: spreading C3's 6888 rows over
+    // all 256 CUs (27 rows per block) measured slower than 216 blocks of 32 (214 vs 202-205 us per
+    // 10 layers, profiles/r04_ab/): every block streams each layer's 1.3 MB of weights from its
+    // XCD's L2, and 32 blocks per XCD instead of 27 share that L2's bandwidth
+    // r05: the halo is the launch's layer count (>= 8, the skip image's first row), and the
+    // default writes every exact row, 64 - 2 hl (44 at 10 layers)
+    // (cycle > 1: the sum of the group's dilations)
+    P.hl = std::max(grp[k][1], 8);
+    P.ro = std::min(h->stack_ro > 0 ? h->stack_ro : 64, 64 - 2 * P.hl);
+    if (fuse.xin && l0 == 0) {
+      P.spec = fuse.xin; P.Winb = fuse.Winb; P.b_in = h->b_in; P.M = h->M; P.ldw_in = h->ldw_in;
+    }
+    // (not the first launch: it reads mel, this one writes it)
+    if (fuse.tail && k == ngrp - 1) wn_stack_fuse_tail(P, h, fuse);
+    ProfScope ps("wn_stack", c.st);
+    launch_wn_stack(P, dim3((unsigned)cdiv(rows, P.ro)), h->cyc > 1, c.st);
+    PD_LAUNCH_CHECK();
+  }
+  return PD_OK;
+}
+
+// bf16, C == 256: one fused launch per residual layer, x ping-pongs x <-> x2
+int wn_layers_fused(const WnCall& c) {
+  const pd_wavenet* h = c.h;
+  const int H = h->H, C = h->C, Ly = h->L;
+  const long long BT = (long long)c.B * c.T;
+  float* xb[2] = {c.ws + c.Lw.x, c.ws + c.Lw.x2};
+  for (int l = 0; l < Ly; ++l) {
+    WnLayerArgs P{};
+    P.xin = xb[l & 1]; P.xout = xb[(l + 1) & 1]; P.skip = c.ws + c.Lw.skip; P.cond = c.cond;
+    P.dp = c.dproj + (size_t)l * C; P.dp_ld = Ly * C;
+    P.W1f = h->W1f + (size_t)l * 2 * C * (3 * C + H); P.b1 = h->bl1 + (size_t)l * 2 * C;
+    P.W2f = h->W2f + (size_t)l * 2 * C * C; P.b2 = h->bl2 + (size_t)l * 2 * C;
+    P.B = c.B; P.T = c.T; P.H = H; P.dil = 1 << (l % h->cyc); P.first = (l == 0); P.lens = c.lens;
+    // the next layer's weights (the last layer, or prefetch off: this layer's, already on-die)
+    const int lp = l + 1 < Ly && h->l2_prefetch ? l + 1 : l;
+    P.pfw[0] = h->W1f + (size_t)lp * 2 * C * (3 * C + H);
+    P.pfw[1] = h->W2f + (size_t)lp * 2 * C * C;
+    P.pf_lines[0] = (int)((size_t)2 * C * (3 * C + H) * 2 / 128);
+    P.pf_lines[1] = (int)((size_t)2 * C * C * 2 / 128);
+    ProfScope ps("wn_layer", c.st);
+    // auto: 64-frame blocks once they still fill every CU (r02: B=32 x 861 frames 73 vs 88 us per
+    // layer), else 32-frame blocks (B=8: 108 blocks of 64 frames leave half the chip idle, 37 vs 27 us)
+    const bool wide = (h->layer_mode == 2 && cdiv(BT, 64) >= 256) || h->layer_mode == 3;
+    dispatch([&](auto RT) {
+      hipLaunchKernelGGL((wn_layer_bf16_kernel<1024, RT()>), dim3(cdiv(BT, 32 * RT())), dim3(512), 0, c.st, P);
+    }, one_of<2, 1>(wide ? 2 : 1));
+    PD_LAUNCH_CHECK();
+  }
+  return PD_OK;
+}
+
+// fp32, small batches: the dedicated two-launch layer (wn_f32_layer_kernel) where the GEMM
+// engine would split K (PD_WN_OPT_F32_LAYER 1), or always (2)
+bool wn_f32_direct(const WnCall& c) {
+  const pd_wavenet* h = c.h;
+  return h->f32_layer && h->C == 256 &&
+         (h->f32_layer == 2 || wn_ksplit((long long)c.B * c.T, h->C, h->ldw1, h->ksplit_blocks) > 1);
+}
+int wn_f32_layer_direct(const WnCall& c, int l) {
+  const pd_wavenet* h = c.h;
+  const int H = h->H, C = h->C, rows = c.rows();
+  float *x = c.ws + c.Lw.x, *g = c.ws + c.Lw.g;
+  const dim3 grid((unsigned)cdiv(rows, 32), C / 32);
+  WnF32Args F{};
+  F.rows = rows; F.T = c.T; F.C = C; F.H = H; F.dil = 1 << (l % h->cyc); F.lens = c.lens;
+  F.a = x; F.cond = c.cond; F.dp = c.dproj + (size_t)l * C; F.dp_ld = h->L * C;
+  F.W = h->Wl1 + (size_t)l * 2 * C * h->ldw1; F.ldw = h->ldw1; F.bias = h->bl1 + (size_t)l * 2 * C; F.g = g;
+  {
+    ProfScope ps("wn_gate", c.st);
+    dispatch([&](auto RAG) {
+      hipLaunchKernelGGL((wn_f32_layer_kernel<true, 32 / WF32_NW, WF32_NW, RAG()>), grid, dim3(WF32_NW * 64), 0, c.st, F);
+    }, bool_of(c.lens != nullptr));
+    PD_LAUNCH_CHECK();
+  }
+  WnF32Args Q{};
+  Q.rows = rows; Q.T = c.T; Q.C = C; Q.H = H;
+  Q.a = g; Q.W = h->Wl2 + (size_t)l * 2 * C * C; Q.ldw = C; Q.bias = h->bl2 + (size_t)l * 2 * C;
+  Q.x = x; Q.skip = c.ws + c.Lw.skip; Q.first = l == 0;
+  ProfScope ps("wn_resskip", c.st);
+  hipLaunchKernelGGL((wn_f32_layer_kernel<false, 8 / WF32_NW, WF32_NW>), grid, dim3(WF32_NW * 64), 0, c.st, Q);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// fp32: one residual layer as two GEMMs with the GATE / RESSKIP epilogues
+int wn_f32_layer_gemm(const WnCall& c, int l) {
+  const pd_wavenet* h = c.h;
+  const int H = h->H, C = h->C, B = c.B, T = c.T, Ly = h->L, dil = 1 << (l % h->cyc);
+  const long long BTs = (long long)T;
+  float *x = c.ws + c.Lw.x, *g = c.ws + c.Lw.g;
+  {  // z = dilconv(x + dproj) + condproj ; g = sigmoid(z[:C]) * tanh(z[C:])   (wavenet.py:60-67)
+    GemmArgs a = make_gemm(B, T, 2 * C, h->Wl1 + (size_t)l * 2 * C * h->ldw1, h->ldw1,
+                           h->bl1 + (size_t)l * 2 * C, g, BTs * C, C);
+    for (int tap = 0; tap < 3; ++tap) {
+      Seg s = make_seg(x, BTs * C, C, C, (tap - 1) * dil);
+      s.add_vec = c.dproj + (size_t)l * C;
+      s.add_ld = Ly * C;
+      add_seg(a, s);
+    }
+    add_seg(a, make_seg(c.cond, BTs * H, H, H, 0));
+    a.half = C;
+    a.ksplit = wn_ksplit((long long)B * T, C, h->ldw1, h->ksplit_blocks);
+    a.part = c.ws + c.Lw.part;
+    a.lens = c.lens; a.lens_mul = 1;
+    PD_TRY((launch_gemm<1, 2, 4, 1, EPI_GATE, U_WN_GATE>(a, c.st, "wn_gate")));
+  }
+  // o = W_out g + b ; x = (x + o[:C]) / sqrt2 ; skip += o[C:]   (wavenet.py:69-72)
+  GemmArgs a = make_gemm(B, T, 2 * C, h->Wl2 + (size_t)l * 2 * C * C, C, h->bl2 + (size_t)l * 2 * C, x, BTs * C, C);
+  add_seg(a, make_seg(g, BTs * C, C, C, 0));
+  a.half = C;
+  a.out2 = c.ws + c.Lw.skip; a.out2_bs = BTs * C; a.out2_ld = C;
+  a.flag = (l == 0);
+  a.ksplit = wn_ksplit((long long)B * T, C, C, h->ksplit_blocks);
+  a.part = c.ws + c.Lw.part;
+  return launch_gemm<1, 2, 4, 1, EPI_RESSKIP, U_WN_RESSKIP>(a, c.st, "wn_resskip");
+}
+
+int wn_layers_f32(const WnCall& c) {
+  const pd_wavenet* h = c.h;
+  const bool direct = wn_f32_direct(c) && h->H == 256 && h->ldw1 == 3 * h->C + h->H;
+  for (int l = 0; l < h->L; ++l) PD_TRY(direct ? wn_f32_layer_direct(c, l) : wn_f32_layer_gemm(c, l));
+  return PD_OK;
+}
+
+// fp32 at small batches: skip head + output projection + posterior in one launch per 32 frames
+int wn_f32_tail(const WnCall& c, const StackTail& tail) {
+  const pd_wavenet* h = c.h;
+  WnF32TailArgs F{};
+  F.skip = c.ws + c.Lw.skip; F.scale = 1.0f / sqrtf((float)h->L); F.Ws = h->Ws; F.bs = h->bs; F.Wo = h->Wo; F.bo = h->bo;
+  set_tail(F, tail);
+  F.rows = c.rows(); F.T = c.T; F.C = h->C; F.M = h->M;
+  ProfScope ps("wn_f32_tail", c.st);
+  hipLaunchKernelGGL(wn_f32_tail_kernel, dim3(cdiv(c.rows(), 32)), dim3(512), 0, c.st, F);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+// hs = relu(W_skip (sum skip / sqrt(L)) + b)   (wavenet.py:119-121)
+int wn_skip_head(const WnCall& c) {
+  const pd_wavenet* h = c.h;
+  const int C = h->C;
+  const long long bs = (long long)c.T * C;
+  GemmArgs a = make_gemm(c.B, c.T, C, h->Ws, C, h->bs, c.ws + c.Lw.hs, bs, C);
+  Seg s = make_seg(c.ws + c.Lw.skip, bs, C, C, 0);
+  s.scale = 1.0f / sqrtf((float)h->L);
+  add_seg(a, s);
+  a.act = ACT_RELU;
+  return launch_small_gemm<EPI_STORE, U_WN_SKIP>(a, c.st, "wn_skiphead");
+}
+
+// Input projection + residual stack + skip head.  xin: time-major [B][T][M]; cond, dproj, lens: WnCall.
+// Leaves relu(skip head) in ws.hs -- or, when `tail` is given and the stack kernel (PD_WN_OPT_STACK_FUSE) or the
+// fp32 tail kernel fuses it, applies the whole output stage itself and sets *tail_done.
 int wavenet_core(const pd_wavenet* h, float* ws, const WsLayout& Lw, const float* xin,
                  const float* cond, const float* dproj, int B, int T, hipStream_t st,
                  const StackTail* tail = nullptr, bool* tail_done = nullptr, const int* lens = nullptr) {
   const int M = h->M, H = h->H, C = h->C, Ly = h->L;
-  const long long BTs = (long long)T;
-  float* x = ws + Lw.x;
-  float* g = ws + Lw.g;
-  float* skip = ws + Lw.skip;
-  float* hs = ws + Lw.hs;
+  const WnCall c{h, ws, Lw, cond, dproj, B, T, lens, st};
   if (tail_done) *tail_done = false;
   // (stores through buffer resources: 32-bit byte offsets into [rows][C] fp32)
   const bool stack = h->W1f && h->stack_nl > 0 && h->layer_mode == 2 && H == WNF_C && T >= 64 && Ly <= 64 &&
                      (long long)B * T * C * 4 < (1ll << 31);
-  // the stack launches' layer groups [l0, l0 + nl): at most stack_nl layers whose dilations sum to
-  // at most the window's halo budget (cycle 1: nl layers, halo nl; cycle 5: {1,2,4,8}, {16}, ...)
-  int grp[64][2], ngrp = 0;
-  if (stack) {
-    for (int l0 = 0; l0 < Ly && ngrp < 64;) {
-      int nl = 0, sum = 0;
-      while (l0 + nl < Ly && nl < h->stack_nl) {
-        const int d = 1 << ((l0 + nl) % h->cyc);
-        if (nl > 0 && sum + d > WST_HMAX) break;
-        sum += d;
-        ++nl;
-      }
-      grp[ngrp][0] = l0; grp[ngrp][1] = sum;
-      ++ngrp;
-      l0 += nl;
-    }
-  }
+  int grp[64][2];
+  const int ngrp = stack ? wn_stack_groups(h, grp) : 0;
   // fused input projection / output stage: bf16 mirrors of W_in, W_skip, W_out present
-  const __bf16* Winb = lookup_bf16(h->Win);
-  const __bf16* Wsb = lookup_bf16(h->Ws);
-  const __bf16* Wob = lookup_bf16(h->Wo);
-  const bool fuse_in = stack && h->stack_fuse && Winb && h->ldw_in <= 128 && M % 4 == 0;
+  WnStackFuse fuse;
+  fuse.Winb = lookup_bf16(h->Win); fuse.Wsb = lookup_bf16(h->Ws); fuse.Wob = lookup_bf16(h->Wo);
+  const bool fuse_in = stack && h->stack_fuse && fuse.Winb && h->ldw_in <= 128 && M % 4 == 0;
   // (the fused tail stores mel through a buffer resource: 32-bit byte offsets)
-  const bool fuse_tail = fuse_in && tail && Wsb && Wob && M <= 8 * 32 && C == WNF_C && ngrp > 1 &&
-                         (long long)B * T * M * 4 < (1ll << 31) && (long long)B * T * C * 4 < (1ll << 31);
+  const bool fuse_tail = fuse_in && tail && fuse.Wsb && fuse.Wob && M <= 8 * 32 && C == WNF_C &&
+                         ngrp > 1 && (long long)B * T * M * 4 < (1ll << 31) && (long long)B * T * C * 4 < (1ll << 31);
+  fuse.xin = fuse_in ? xin : nullptr;
+  fuse.tail = fuse_tail ? tail : nullptr;
   if (!fuse_in) {  // x = relu(W_in spec + b)   (wavenet.py:108-111)
-    GemmArgs a = make_gemm(B, T, C, h->Win, h->ldw_in, h->b_in, x, BTs * C, C);
-    add_seg(a, make_seg(xin, BTs * M, M, M, 0));
+    GemmArgs a = make_gemm(B, T, C, h->Win, h->ldw_in, h->b_in, ws + Lw.x, (long long)T * C, C);
+    add_seg(a, make_seg(xin, (long long)T * M, M, M, 0));
     a.act = ACT_RELU;
     PD_TRY((launch_small_gemm<EPI_STORE, U_WN_INPROJ>(a, st, "wn_inproj")));
   }
-  const int rows = B * T;
-  const int dil_max = 1 << (h->cyc - 1);
-  // bf16 layer implementation (PD_WN_OPT_LAYER 1): GATE + RESSKIP launches.  Not the default: at
-  // B*T = 1722 .. 27552 frames it measured equal to or slower than the fused kernel.
-  const bool two = h->W1p && dil_max <= 16 && h->layer_mode == 1;
+  const bool two = h->W1p && (1 << (h->cyc - 1)) <= 16 && h->layer_mode == 1;
   if (two && lens) {
     set_error("PD_WN_OPT_LAYER 1 (two-kernel layers) does not take ragged batches (lens)");
     return PD_ERR_UNSUPPORTED;
   }
-  if (two) {
-    // bf16: GATE + RESSKIP launches per residual layer (wn_gate_bf16_kernel, wn_resskip_bf16_kernel)
-    __bf16* xa = reinterpret_cast<__bf16*>(ws + Lw.xa);
-    __bf16* condb = reinterpret_cast<__bf16*>(ws + Lw.condb);
-    __bf16* gb = reinterpret_cast<__bf16*>(ws + Lw.g);
-    {
-      ProfScope ps("wn_xa", st);
-      const long long n4 = ((long long)rows * (C > H ? C : H) + 3) / 4;
-      hipLaunchKernelGGL(wn_xa_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, x, dproj, Ly * C, xa, cond, condb,
-                         rows, T, C, H);
-      PD_LAUNCH_CHECK();
-    }
-    const int K1 = 3 * C + H;
-    for (int l = 0; l < Ly; ++l) {
-      WnGateArgs G{};
-      G.xa = xa; G.condb = condb; G.Wp = h->W1p + (size_t)l * 2 * C * K1; G.b1 = h->bl1 + (size_t)l * 2 * C;
-      G.g = gb; G.rows = rows; G.T = T; G.dil = 1 << (l % h->cyc);
-      {
-        ProfScope ps("wn_gate2", st);
-        if (dil_max == 1)
-          hipLaunchKernelGGL(wn_gate_bf16_kernel<1>, dim3(cdiv(rows, WG2_ROWS), C / 64), dim3(512), 0, st, G);
-        else
-          hipLaunchKernelGGL(wn_gate_bf16_kernel<16>, dim3(cdiv(rows, WG2_ROWS), C / 64), dim3(512), 0, st, G);
-        PD_LAUNCH_CHECK();
-      }
-      const bool last = l == Ly - 1;
-      WnResSkipArgs P{};
-      P.g = gb; P.W2f = h->W2f + (size_t)l * 2 * C * C; P.b2 = h->bl2 + (size_t)l * 2 * C;
-      P.x = x; P.skip = skip; P.first = l == 0;
-      P.xa_next = last ? nullptr : xa; P.dp_next = last ? nullptr : dproj + (size_t)(l + 1) * C; P.dp_ld = Ly * C;
-      // the last layer's residual half feeds nothing (wavenet.py:115-119 keeps only skip)
-      P.nt0 = last ? C / 32 : 0;
-      P.rows = rows; P.T = T;
-      {
-        ProfScope ps("wn_resskip2", st);
-        hipLaunchKernelGGL(wn_resskip_bf16_kernel<WN_RS_RQ>, dim3(cdiv(rows, 32 * WN_RS_RQ), (last ? C : 2 * C) / 128),
-                           dim3(256), 0, st, P);
-        PD_LAUNCH_CHECK();
-      }
-    }
-  } else if (stack) {
-    // bf16: the layer groups above, one wn_stack_bf16_kernel launch each, x ping-pongs
-    __bf16* condb = reinterpret_cast<__bf16*>(ws + Lw.condb);
-    {
-      ProfScope ps("wn_condb", st);
-      hipLaunchKernelGGL(wn_xa_kernel, dim3(cdiv(((long long)rows * H + 3) / 4, 256)), dim3(256), 0, st, nullptr,
-                         nullptr, 0, nullptr, cond, condb, rows, T, C, H);
-      PD_LAUNCH_CHECK();
-    }
-    float* xb[2] = {x, ws + Lw.x2};
-    for (int k = 0; k < ngrp; ++k) {
-      const int l0 = grp[k][0], l1 = k + 1 < ngrp ? grp[k + 1][0] : Ly;
-      WnStackArgs P{};
-      P.xin = xb[k & 1]; P.xout = xb[(k + 1) & 1]; P.skip = skip; P.condb = condb;
-      P.dp = dproj; P.dp_ld = Ly * C;
-      P.W1f = h->W1f; P.b1 = h->bl1; P.W2f = h->W2f; P.b2 = h->bl2;
-      P.rows = rows; P.T = T; P.l0 = l0; P.nl = l1 - l0; P.first = l0 == 0; P.L = Ly;
-      P.lens = lens; P.cyc = h->cyc;
-      // output rows per block (PD_WN_OPT_STACK_RO; r04 default 32).  r04: spreading C3's 6888 rows over
-      // all 256 CUs (27 rows per block) measured slower than 216 blocks of 32 (214 vs 202-205 us per
-      // 10 layers, profiles/r04_ab/): every block streams each layer's 1.3 MB of weights from its
-      // XCD's L2, and 32 blocks per XCD instead of 27 share that L2's bandwidth
-      // r05: the halo is the launch's layer count (>= 8, the skip image's first row), and the
-      // default writes every exact row, 64 - 2 hl (44 at 10 layers)
-      // (cycle > 1: the sum of the group's dilations)
-      P.hl = std::max(grp[k][1], 8);
-      P.ro = std::min(h->stack_ro > 0 ? h->stack_ro : 64, 64 - 2 * P.hl);
-      if (fuse_in && l0 == 0) {
-        P.spec = xin; P.Winb = Winb; P.b_in = h->b_in; P.M = M; P.ldw_in = h->ldw_in;
-      }
-      if (fuse_tail && k == ngrp - 1) {   // (not the first launch: it reads mel, this one writes it)
-        P.Wsb = Wsb; P.bs = h->bs; P.Wob = Wob; P.bo = h->bo; P.M = M;
-        P.skip_scale = 1.0f / sqrtf((float)Ly);   // the skip head's segment scale below
-        P.mel = tail->mel; P.c1 = tail->c1; P.c2 = tail->c2; P.sigma = tail->sigma;
-        P.noise = tail->noise; P.noise_bs = tail->noise_bs; P.noise_ld = tail->noise_ld;
-        P.seed = tail->seed; P.stream_id = tail->stream_id; P.uid = tail->uid;
-      }
-      ProfScope ps("wn_stack", st);
-      const dim3 grid((unsigned)cdiv(rows, P.ro));
-      launch_wn_stack(P, grid, h->cyc > 1, st);
-      PD_LAUNCH_CHECK();
-    }
-  } else if (h->W1f) {
-    // bf16, C == 256: one fused launch per residual layer, x ping-pongs x <-> x2
-    float* xb[2] = {x, ws + Lw.x2};
-    for (int l = 0; l < Ly; ++l) {
-      WnLayerArgs P{};
-      P.xin = xb[l & 1]; P.xout = xb[(l + 1) & 1]; P.skip = skip; P.cond = cond;
-      P.dp = dproj + (size_t)l * C; P.dp_ld = Ly * C;
-      P.W1f = h->W1f + (size_t)l * 2 * C * (3 * C + H); P.b1 = h->bl1 + (size_t)l * 2 * C;
-      P.W2f = h->W2f + (size_t)l * 2 * C * C; P.b2 = h->bl2 + (size_t)l * 2 * C;
-      P.B = B; P.T = T; P.H = H; P.dil = 1 << (l % h->cyc); P.first = (l == 0); P.lens = lens;
-      // the next layer's weights (the last layer, or prefetch off: this layer's, already on-die)
-      const int lp = l + 1 < Ly && h->l2_prefetch ? l + 1 : l;
-      P.pfw[0] = h->W1f + (size_t)lp * 2 * C * (3 * C + H);
-      P.pfw[1] = h->W2f + (size_t)lp * 2 * C * C;
-      P.pf_lines[0] = (int)((size_t)2 * C * (3 * C + H) * 2 / 128);
-      P.pf_lines[1] = (int)((size_t)2 * C * C * 2 / 128);
-      ProfScope ps("wn_layer", st);
-      // auto: 64-frame blocks once they still fill every CU (r02: B=32 x 861 frames 73 vs 88 us per
-      // layer), else 32-frame blocks (B=8: 108 blocks of 64 frames leave half the chip idle, 37 vs 27 us)
-      if (h->layer_mode == 2 && cdiv((long long)B * T, 64) >= 256)
-        hipLaunchKernelGGL((wn_layer_bf16_kernel<1024, 2>), dim3(cdiv((long long)B * T, 64)), dim3(512), 0, st, P);
-      else if (h->layer_mode == 3)
-        hipLaunchKernelGGL((wn_layer_bf16_kernel<1024, 2>), dim3(cdiv((long long)B * T, 64)), dim3(512), 0, st, P);
-      else
-        hipLaunchKernelGGL((wn_layer_bf16_kernel<1024, 1>), dim3(cdiv((long long)B * T, 32)), dim3(512), 0, st, P);
-      PD_LAUNCH_CHECK();
-    }
-  } else
-  for (int l = 0; l < Ly; ++l) {
-    const int dil = 1 << (l % h->cyc);
-    // fp32, small batches: the dedicated two-launch layer (wn_f32_layer_kernel) where the GEMM
-    // engine would split K (PD_WN_OPT_F32_LAYER 1), or always (2)
-    const bool f32k = h->f32_layer && C == 256 && H == 256 && h->ldw1 == 3 * C + H &&
-                      (h->f32_layer == 2 || wn_ksplit((long long)B * T, C, h->ldw1, h->ksplit_blocks) > 1);
-    if (f32k) {
-      const dim3 grid((unsigned)cdiv(rows, 32), C / 32);
-      WnF32Args F{};
-      F.rows = rows; F.T = T; F.C = C; F.H = H; F.dil = dil; F.lens = lens;
-      F.a = x; F.cond = cond; F.dp = dproj + (size_t)l * C; F.dp_ld = Ly * C;
-      F.W = h->Wl1 + (size_t)l * 2 * C * h->ldw1; F.ldw = h->ldw1; F.bias = h->bl1 + (size_t)l * 2 * C; F.g = g;
-      {
-        ProfScope ps("wn_gate", st);
-        if (lens)
-          hipLaunchKernelGGL((wn_f32_layer_kernel<true, 32 / WF32_NW, WF32_NW, true>), grid, dim3(WF32_NW * 64), 0, st, F);
-        else
-          hipLaunchKernelGGL((wn_f32_layer_kernel<true, 32 / WF32_NW, WF32_NW>), grid, dim3(WF32_NW * 64), 0, st, F);
-        PD_LAUNCH_CHECK();
-      }
-      WnF32Args Q{};
-      Q.rows = rows; Q.T = T; Q.C = C; Q.H = H;
-      Q.a = g; Q.W = h->Wl2 + (size_t)l * 2 * C * C; Q.ldw = C; Q.bias = h->bl2 + (size_t)l * 2 * C;
-      Q.x = x; Q.skip = skip; Q.first = l == 0;
-      {
-        ProfScope ps("wn_resskip", st);
-        hipLaunchKernelGGL((wn_f32_layer_kernel<false, 8 / WF32_NW, WF32_NW>), grid, dim3(WF32_NW * 64), 0, st, Q);
-        PD_LAUNCH_CHECK();
-      }
-      continue;
-    }
-    {  // z = dilconv(x + dproj) + condproj ; g = sigmoid(z[:C]) * tanh(z[C:])   (wavenet.py:60-67)
-      GemmArgs a = make_gemm(B, T, 2 * C, h->Wl1 + (size_t)l * 2 * C * h->ldw1, h->ldw1,
-                             h->bl1 + (size_t)l * 2 * C, g, BTs * C, C);
-      for (int tap = 0; tap < 3; ++tap) {
-        Seg s = make_seg(x, BTs * C, C, C, (tap - 1) * dil);
-        s.add_vec = dproj + (size_t)l * C;
-        s.add_ld = Ly * C;
-        add_seg(a, s);
-      }
-      add_seg(a, make_seg(cond, BTs * H, H, H, 0));
-      a.half = C;
-      a.ksplit = wn_ksplit((long long)B * T, C, h->ldw1, h->ksplit_blocks);
-      a.part = ws + Lw.part;
-      a.lens = lens; a.lens_mul = 1;
-      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_GATE, U_WN_GATE>(a, st, "wn_gate")));
-    }
-    {  // o = W_out g + b ; x = (x + o[:C]) / sqrt2 ; skip += o[C:]   (wavenet.py:69-72)
-      GemmArgs a = make_gemm(B, T, 2 * C, h->Wl2 + (size_t)l * 2 * C * C, C, h->bl2 + (size_t)l * 2 * C,
-                             x, BTs * C, C);
-      add_seg(a, make_seg(g, BTs * C, C, C, 0));
-      a.half = C;
-      a.out2 = skip; a.out2_bs = BTs * C; a.out2_ld = C;
-      a.flag = (l == 0);
-      a.ksplit = wn_ksplit((long long)B * T, C, C, h->ksplit_blocks);
-      a.part = ws + Lw.part;
-      PD_TRY((launch_gemm<1, 2, 4, 1, EPI_RESSKIP, U_WN_RESSKIP>(a, st, "wn_resskip")));
-    }
-  }
+  if (two) PD_TRY(wn_layers_two(c));
+  else if (stack) PD_TRY(wn_layers_stack(c, grp, ngrp, fuse));
+  else if (h->W1f) PD_TRY(wn_layers_fused(c));
+  else PD_TRY(wn_layers_f32(c));
   if (fuse_tail) {   // skip head, output projection and posterior ran in the last stack launch
     *tail_done = true;
     return PD_OK;
   }
-  // fp32 at small batches: skip head + output projection + posterior in one launch per 32 frames
-  if (tail && !h->W1f && h->f32_layer && C == 256 && M <= 256 &&
-      (h->f32_layer == 2 || wn_ksplit((long long)B * T, C, h->ldw1, h->ksplit_blocks) > 1)) {
-    WnF32TailArgs F{};
-    F.skip = skip; F.scale = 1.0f / sqrtf((float)Ly); F.Ws = h->Ws; F.bs = h->bs; F.Wo = h->Wo; F.bo = h->bo;
-    F.mel = tail->mel; F.c1 = tail->c1; F.c2 = tail->c2; F.sigma = tail->sigma;
-    F.noise = tail->noise; F.noise_bs = tail->noise_bs; F.noise_ld = tail->noise_ld;
-    F.seed = tail->seed; F.stream_id = tail->stream_id; F.uid = tail->uid;
-    F.rows = rows; F.T = T; F.C = C; F.M = M;
-    ProfScope ps("wn_f32_tail", st);
-    hipLaunchKernelGGL(wn_f32_tail_kernel, dim3(cdiv(rows, 32)), dim3(512), 0, st, F);
-    PD_LAUNCH_CHECK();
+  if (tail && !h->W1f && wn_f32_direct(c) && M <= 256) {
+    PD_TRY(wn_f32_tail(c, *tail));
     *tail_done = true;
     return PD_OK;
   }
-  {  // hs = relu(W_skip (sum skip / sqrt(L)) + b)   (wavenet.py:119-121)
-    GemmArgs a = make_gemm(B, T, C, h->Ws, C, h->bs, hs, BTs * C, C);
-    Seg s = make_seg(skip, BTs * C, C, C, 0);
-    s.scale = 1.0f / sqrtf((float)Ly);
-    add_seg(a, s);
-    a.act = ACT_RELU;
-    PD_TRY((launch_small_gemm<EPI_STORE, U_WN_SKIP>(a, st, "wn_skiphead")));
-  }
-  return PD_OK;
+  return wn_skip_head(c);
 }
 
 }  // namespace
