@@ -74,7 +74,7 @@ typedef struct {
   int hidden_size;           /* H: condition channels (encoder_hidden)                   */
   int residual_layers;       /* L: 20 (handler/base_config.yaml:210)                     */
   int residual_channels;     /* C: 256 (base_config.yaml:211), multiple of 32            */
-  int dilation_cycle_length; /* dilation 2^(l % cycle) (wavenet.py:93-96)                */
+  int dilation_cycle_length; /* dilation 2^(l % cycle) (wavenet.py:93-96); min(L, cycle) <= 31 */
 } pd_wavenet_dims;
 
 /* Parameter order = the reference state-dict order (wavenet.py:84-99), all float32
@@ -106,7 +106,8 @@ void pd_wavenet_destroy(pd_wavenet* h);
 /* PD_WN_OPT_L2PF (bf16 fused layer): 1 (default) each layer launch pulls the next layer's weight
  * fragments into every XCD's L2 while it runs; 0 = off. */
 #define PD_WN_OPT_L2PF 2
-/* PD_WN_OPT_STACK (bf16, C = H = 256, dilation_cycle_length 1, T >= 64, PD_WN_OPT_LAYER 2): n = 1..16
+/* PD_WN_OPT_STACK (bf16, C = H = 256, every dilation <= 16 -- min(L, dilation_cycle_length) <= 5 --, L <= 64,
+ * T >= 64, PD_WN_OPT_LAYER 2; other nets take the one-layer kernel whatever the value): n = 1..16
  * residual layers per launch (wn_stack_bf16_kernel: a 64-frame window per 32 output frames stays
  * resident for the n layers; bit-identical to the one-layer kernel), default 10; 0 = one launch
  * per layer. */

@@ -1525,18 +1525,24 @@ int wn_layers_two(const WnCall& c) {
   return PD_OK;
 }
 
+// The net's largest dilation, 2^(min(cyc, L) - 1) (pd_wavenet_create keeps the exponent below 31)
+int wn_max_dil(const pd_wavenet* h) { return 1 << (std::min(h->cyc, h->L) - 1); }
+
 // The stack launches' layer groups [grp[k][0], grp[k + 1][0]): at most stack_nl layers whose dilations sum
-// (grp[k][1]) to at most the window's halo budget (cycle 1: nl layers, halo nl; cycle 5: {1,2,4,8}, {16}, ...)
+// (grp[k][1]) to at most the window's halo budget (cycle 1: nl layers, halo nl; cycle 5: {1,2,4,8}, {16}, ...).
+// 0 groups when a layer's own dilation is over the budget (cycle >= 6): no window holds that layer's taps,
+// and the caller takes the one-layer kernel instead.
 int wn_stack_groups(const pd_wavenet* h, int grp[64][2]) {
   int ngrp = 0;
   for (int l0 = 0; l0 < h->L && ngrp < 64;) {
     int nl = 0, sum = 0;
     while (l0 + nl < h->L && nl < h->stack_nl) {
       const int d = 1 << ((l0 + nl) % h->cyc);
-      if (nl > 0 && sum + d > WST_HMAX) break;
+      if (sum + d > WST_HMAX) break;
       sum += d;
       ++nl;
     }
+    if (nl == 0) return 0;
     grp[ngrp][0] = l0; grp[ngrp][1] = sum;
     ++ngrp;
     l0 += nl;
@@ -1752,10 +1758,13 @@ int wavenet_core(const pd_wavenet* h, float* ws, const WsLayout& Lw, const float
   const WnCall c{h, ws, Lw, cond, dproj, B, T, lens, st};
   if (tail_done) *tail_done = false;
   // (stores through buffer resources: 32-bit byte offsets into [rows][C] fp32)
-  const bool stack = h->W1f && h->stack_nl > 0 && h->layer_mode == 2 && H == WNF_C && T >= 64 && Ly <= 64 &&
-                     (long long)B * T * C * 4 < (1ll << 31);
+  // (and every layer's taps inside the 64-row window's halo budget: cycle >= 6 dilates by 32 and more, which
+  // the one-layer kernel reads from global memory at any distance)
+  const bool stack_fits = h->W1f && h->stack_nl > 0 && h->layer_mode == 2 && H == WNF_C && T >= 64 && Ly <= 64 &&
+                          (long long)B * T * C * 4 < (1ll << 31) && wn_max_dil(h) <= WST_HMAX;
   int grp[64][2];
-  const int ngrp = stack ? wn_stack_groups(h, grp) : 0;
+  const int ngrp = stack_fits ? wn_stack_groups(h, grp) : 0;
+  const bool stack = ngrp > 0;
   // fused input projection / output stage: bf16 mirrors of W_in, W_skip, W_out present
   WnStackFuse fuse;
   fuse.Winb = lookup_bf16(h->Win); fuse.Wsb = lookup_bf16(h->Ws); fuse.Wob = lookup_bf16(h->Wo);
@@ -1771,7 +1780,7 @@ int wavenet_core(const pd_wavenet* h, float* ws, const WsLayout& Lw, const float
     a.act = ACT_RELU;
     PD_TRY((launch_small_gemm<EPI_STORE, U_WN_INPROJ>(a, st, "wn_inproj")));
   }
-  const bool two = h->W1p && (1 << (h->cyc - 1)) <= 16 && h->layer_mode == 1;
+  const bool two = h->W1p && h->cyc <= 5 && h->layer_mode == 1;   // dilations up to 16: the GATE kernel's halo
   if (two && lens) {
     set_error("PD_WN_OPT_LAYER 1 (two-kernel layers) does not take ragged batches (lens)");
     return PD_ERR_UNSUPPORTED;
@@ -1798,7 +1807,7 @@ extern "C" {
 
 int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, int dtype,
                       void* stream, pd_wavenet** out) {
-  PD_CHECK_ARG(dims && params && out, "null pointer");
+  PD_CHECK_ARG(dims && out, "null pointer");
   PD_CHECK_ARG(dtype == PD_DTYPE_F32 || dtype == PD_DTYPE_BF16, "dtype must be PD_DTYPE_F32 or PD_DTYPE_BF16");
   const int M = dims->in_dims, H = dims->hidden_size, L = dims->residual_layers,
             C = dims->residual_channels, cyc = dims->dilation_cycle_length;
@@ -1806,6 +1815,10 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
   PD_CHECK_ARG(H > 0 && H % 4 == 0, "hidden_size must be a positive multiple of 4");
   PD_CHECK_ARG(C > 0 && C % 32 == 0, "residual_channels must be a positive multiple of 32");
   PD_CHECK_ARG(L > 0 && cyc > 0, "residual_layers/dilation_cycle_length must be positive");
+  // layer l dilates by 2^(l % cyc), an int: the largest exponent is min(L, cyc) - 1
+  PD_CHECK_ARG(std::min(L, cyc) <= 31, "dilation_cycle_length: a dilation of 2^31 or more (min(residual_layers, "
+                                       "dilation_cycle_length) must be at most 31)");
+  PD_CHECK_ARG(params, "null pointer");
   PD_TRY(check_params(params, PD_WAVENET_NUM_PARAMS(L)));
   hipStream_t st = (hipStream_t)stream;
 

@@ -101,6 +101,29 @@ def test_create_rejects_bad_dims():
     assert h.value is None
 
 
+def test_wavenet_create_rejects_bad_dims():
+    """pd_wavenet_create checks its dims before its parameter list, as the creates above: with params NULL every
+    bad dim reports its own message, and only good dims get as far as the null pointer.  min(L, cycle) = 32
+    would dilate a layer by 2^31."""
+    lib = _lib.lib()
+    h = _lib.C.c_void_p()
+
+    def wavenet(*dims):
+        rc = lib.pd_wavenet_create(_lib.C.byref(_lib.pd_wavenet_dims(*dims)), None, 0, None, _lib.C.byref(h))
+        return rc, lib.pd_last_error().decode()
+
+    for dims, word in (((6, 256, 20, 256, 1), "in_dims"), ((80, 10, 20, 256, 1), "hidden_size"),
+                       ((80, 256, 20, 48, 1), "residual_channels"), ((80, 256, 0, 256, 1), "residual_layers"),
+                       ((80, 256, 20, 256, 0), "dilation_cycle_length must be positive"),
+                       ((80, 256, 32, 256, 32), "dilation_cycle_length: a dilation")):
+        rc, msg = wavenet(*dims)
+        assert rc == 1 and word in msg and "null pointer" not in msg, (dims, rc, msg)
+    for dims in ((80, 256, 20, 256, 1), (12, 36, 3, 96, 3), (80, 256, 31, 256, 40), (80, 256, 40, 256, 31)):
+        rc, msg = wavenet(*dims)
+        assert rc == 1 and "null pointer" in msg, (dims, rc, msg)
+    assert h.value is None
+
+
 @pytest.mark.parametrize("name", list(VC.PITCH_CASES))
 def test_pitch_ref_matches_reference(name):
     hp, P, ins, d = VC.pitch_case(name)
