@@ -740,6 +740,19 @@ size_t pd_rmvpe_workspace_size(const pd_rmvpe* h, int B, int T);
  * allocation, no synchronisation, capturable.  An output row depends neither on B nor on its batch position. */
 int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* feat, int B, int T, void* workspace,
                      size_t ws_bytes, void* stream);
+/* pd_rmvpe_forward for a ragged batch.  frames: device int32 [B], row b's real mel frames T_b in [1, T]; T stays a
+ * positive multiple of 2^en_de_layers and sizes the tensors and the workspace exactly as above.  Row b is
+ * computed as the image of n_b = T_b rounded up to 2^en_de_layers rows: its input frames in [T_b, n_b) read as
+ * the value 0.0 (network input, as the caller's padding above), whatever mel holds there or past n_b is never
+ * used (it may be NaN), and at level l every pixel with y >= n_b >> l lies outside the image, for every conv
+ * and for the recurrence, whose reverse direction starts at frame n_b - 1 from h = 0.  hidden[b][t] and
+ * feat[b][t] for t < T_b equal, bit for bit, pd_rmvpe_forward of that row alone with T = n_b; for t >= T_b they
+ * are unspecified.  A frames[b] outside [1, T] is clamped into it (that row's output is unspecified, every
+ * access stays inside the row).  frames == NULL returns PD_ERR_ARG.  Same launches as pd_rmvpe_forward (conv
+ * tiles that lie past their row's height return at once); stream-ordered, no allocation, no synchronisation,
+ * capturable. */
+int pd_rmvpe_forward_ragged(const pd_rmvpe* h, const float* mel, const int* frames, float* hidden, float* feat, int B,
+                            int T, void* workspace, size_t ws_bytes, void* stream);
 /* to_local_average_f0 (modules/rmvpe/utils.py:8-23): hidden [B][T][n_class] -> f0 [B][T] in Hz.  c = the first
  * index of the row maximum, or center[b][t] (int64 [B][T], device) when center is non-NULL, clamped into
  * [0, n_class); over i in [max(c - 4, 0), min(c + 5, n_class)): cents = sum h_i (20 i + cents_const) /
@@ -778,6 +791,15 @@ int pd_rmvpe_viterbi(const float* hidden,      /* [B][T][n_class], device       
                      long long* path,          /* [B][T], device                                     */
                      double* logp,             /* [B] or NULL                                        */
                      int B, int T, int n_class, int width, void* workspace, size_t ws_bytes, void* stream);
+/* pd_rmvpe_viterbi for a ragged batch.  frames: device int32 [B]; row b's path runs over its first frames[b]
+ * frames of hidden [B][T][n_class] (the row stride stays T): path[b][t] for t < frames[b] and logp[b] (of the
+ * row's own last frame) equal pd_rmvpe_viterbi of those frames alone, path[b][t] = 0 for t >= frames[b].  The
+ * frames past a row's length are never used by the recurrence (they may hold anything, NaN included).  A
+ * frames[b] outside [1, T] is clamped into it.  frames == NULL returns PD_ERR_ARG; the workspace is that of
+ * (B, T). */
+int pd_rmvpe_viterbi_ragged(const float* hidden, const double* log_band, double log_off, double log_init,
+                            long long* path, double* logp, const int* frames, int B, int T, int n_class, int width,
+                            void* workspace, size_t ws_bytes, void* stream);
 
 /* The f0 curve on another frame grid (component/pe/rmvpe.py:57-72: interp_f0, then resample_align_curve of the
  * curve and of its unvoiced flags, utils/pitch_utils.py:45-51, 86-98) for each row of f0 [B][n]:
@@ -791,6 +813,14 @@ int pd_rmvpe_viterbi(const float* hidden,      /* [B][T][n_class], device       
  * f0_out [B][length] float32, uv_out [B][length] bytes (0 / 1).  One launch, one block per row, stream-ordered. */
 int pd_f0_align(const float* f0, float* f0_out, unsigned char* uv_out, int B, int n, int m, int length, double t_src,
                 double t_dst, int interp_uv, void* stream);
+/* pd_f0_align for a ragged batch.  rows: device int32 [B][3] = (n_b, m_b, length_b) per row; f0 [B][n_stride],
+ * f0_out [B][out_stride], uv_out [B][out_stride].  Row b is pd_f0_align of its first n_b source frames onto
+ * length_b frames; f0_out[b][i] = 0 and uv_out[b][i] = 1 for i >= length_b.  The caller checks n_b >= 2,
+ * m_b >= 1 and 1 <= length_b <= out_stride where it holds the values on the host; the kernel clamps n_b into
+ * [2, n_stride], m_b to >= 1 and length_b into [0, out_stride] so that every access stays inside the row.
+ * n_stride >= 2, out_stride >= 1, rows != NULL (PD_ERR_ARG otherwise); n_stride <= 262144. */
+int pd_f0_align_ragged(const float* f0, float* f0_out, unsigned char* uv_out, const int* rows, int B, int n_stride,
+                       int out_stride, double t_src, double t_dst, int interp_uv, void* stream);
 
 /* ================================================================ harmonic-noise separation
  * pd_vr -- CascadedNet of modules/vr (nets.py, layers.py) with is_complex = True, its zero-padded STFT and its

@@ -192,12 +192,17 @@ _SIGS = {
     "pd_rmvpe_destroy": (None, [_VP]),
     "pd_rmvpe_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "pd_rmvpe_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_rmvpe_forward_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "pd_rmvpe_decode": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_double, _VP]),
     "pd_rmvpe_viterbi_chunk": (C.c_int, []),
     "pd_rmvpe_viterbi_workspace_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "pd_rmvpe_viterbi": (C.c_int, [_VP, _VP, C.c_double, C.c_double, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                    C.c_size_t, _VP]),
+    "pd_rmvpe_viterbi_ragged": (C.c_int, [_VP, _VP, C.c_double, C.c_double, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, _VP, C.c_size_t, _VP]),
     "pd_f0_align": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _VP]),
+    "pd_f0_align_ragged": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                     _VP]),
     "pd_vr_num_params": (C.c_int, [C.POINTER(pd_vr_dims)]),
     "pd_vr_create": (C.c_int, [C.POINTER(pd_vr_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
     "pd_vr_destroy": (None, [_VP]),

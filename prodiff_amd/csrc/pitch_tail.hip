@@ -109,7 +109,8 @@ __global__ __launch_bounds__(VT_MAXN) void vt_forward_kernel(const double* __res
                                                              double log_init, unsigned short* __restrict__ states_all,
                                                              unsigned short* __restrict__ maps_all,
                                                              long long* __restrict__ path_all, double* __restrict__ logp,
-                                                             long long* __restrict__ stamps, int T, int n, int w) {
+                                                             long long* __restrict__ stamps,
+                                                             const int* __restrict__ frames, int Ts, int n, int w) {
   __shared__ double vbuf[2][VT_PAD + VT_MAXN + VT_PAD];
   constexpr int NW = VT_MAXN / 64;
   __shared__ double wave_v[2][NW];
@@ -120,11 +121,13 @@ __global__ __launch_bounds__(VT_MAXN) void vt_forward_kernel(const double* __res
 
   const int b = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
   const bool live = j < n;
+  // the row's own length (ragged: frames[b] clamped into [1, Ts]) inside its slices of Ts frames: one scalar per block
+  const int T = frames ? __builtin_amdgcn_readfirstlane(min(max(frames[b], 1), Ts)) : Ts;
   const int chunks = (T + VT_CHUNK - 1) / VT_CHUNK;
-  const double* lp = lp_all + (long long)b * T * n;
-  unsigned short* states = states_all + (long long)b * T * n;
-  unsigned short* maps = maps_all + (long long)b * chunks * n;
-  long long* path = path_all + (long long)b * T;
+  const double* lp = lp_all + (long long)b * Ts * n;
+  unsigned short* states = states_all + (long long)b * Ts * n;
+  unsigned short* maps = maps_all + (long long)b * ((Ts + VT_CHUNK - 1) / VT_CHUNK) * n;
+  long long* path = path_all + (long long)b * Ts;
   const double ninf = -INFINITY;
   const long long c_start = clock64();
   long long c_back = 0;
@@ -281,6 +284,7 @@ __global__ __launch_bounds__(VT_MAXN) void vt_forward_kernel(const double* __res
       path[t] = (long long)states[(long long)t * n + ends[t / VT_CHUNK - klo]];
     __syncthreads();
   }
+  for (int t = T + j; t < Ts; t += blockDim.x) path[t] = 0;     // ragged: past the row's own frames
   if (b == 0 && j == 0) {     // read by tools/bench_pitch_tail.py only; nothing is computed from them
     const long long c_end = clock64();
     stamps[0] = c_end - c_start;
@@ -352,11 +356,17 @@ __device__ float filled_f0(const float* __restrict__ f0, const VoicedMap& vm, in
 
 __global__ __launch_bounds__(FA_THREADS) void f0_align_kernel(const float* __restrict__ f0_all, float* __restrict__ out_all,
                                                               unsigned char* __restrict__ uv_all, int n, int m, int length,
-                                                              double ts, double td, int interp_uv) {
+                                                              double ts, double td, int interp_uv,
+                                                              const int* __restrict__ rows, int n_stride, int out_stride) {
   __shared__ unsigned long long bits[FA_WORDS];
   __shared__ unsigned long long summ[FA_WORDS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* f0 = f0_all + (long long)blockIdx.x * n;
+  const float* f0 = f0_all + (long long)blockIdx.x * n_stride;
+  if (rows) {     // ragged: the row's own (n, m, length), clamped so that every access stays inside the row
+    n = __builtin_amdgcn_readfirstlane(min(max(rows[3 * blockIdx.x], 2), n_stride));
+    m = __builtin_amdgcn_readfirstlane(max(rows[3 * blockIdx.x + 1], 1));
+    length = __builtin_amdgcn_readfirstlane(min(max(rows[3 * blockIdx.x + 2], 0), out_stride));
+  }
   const int nwords = (n + 63) >> 6;
   for (int wd = wave; wd < nwords; wd += FA_THREADS / 64) {
     const int idx = wd * 64 + lane;
@@ -374,8 +384,12 @@ __global__ __launch_bounds__(FA_THREADS) void f0_align_kernel(const float* __res
   }
   __syncthreads();
   const VoicedMap vm{bits, summ, (nwords + 63) >> 6};
-  float* out = out_all + (long long)blockIdx.x * length;
-  unsigned char* uvo = uv_all + (long long)blockIdx.x * length;
+  float* out = out_all + (long long)blockIdx.x * out_stride;
+  unsigned char* uvo = uv_all + (long long)blockIdx.x * out_stride;
+  for (int i = length + tid; i < out_stride; i += FA_THREADS) {     // ragged: past the row's own length
+    out[i] = 0.f;
+    uvo[i] = 1;
+  }
   const double x_last = ts * (double)(n - 1);
   for (int i = tid; i < length; i += FA_THREADS) {
     const double x = (double)min(i, m - 1) * td;       // past the resampled curve: its last value
@@ -416,8 +430,14 @@ size_t pd_rmvpe_viterbi_workspace_size(int B, int T, int n_class, int width) {
   return vt_layout(B, T, n_class).total;
 }
 
-int pd_rmvpe_viterbi(const float* hidden, const double* log_band, double log_off, double log_init, long long* path,
-                     double* logp, int B, int T, int n_class, int width, void* workspace, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// pd_rmvpe_viterbi (frames = null) and pd_rmvpe_viterbi_ragged
+int viterbi_impl(const float* hidden, const double* log_band, double log_off, double log_init, long long* path,
+                 double* logp, const int* frames, int B, int T, int n_class, int width, void* workspace, size_t ws_bytes,
+                 void* stream) {
   PD_CHECK_ARG(hidden && log_band && path, "null pointer");
   PD_CHECK_ARG(B >= 1 && T >= 1 && n_class >= 1 && width >= 1, "B, T, n_class and width must be positive");
   if (!vt_supported(n_class, width)) {
@@ -436,10 +456,10 @@ int pd_rmvpe_viterbi(const float* hidden, const double* log_band, double log_off
   unsigned short* states = (unsigned short*)(ws + l.states);
   unsigned short* maps = (unsigned short*)(ws + l.maps);
   long long* stamps = (long long*)(ws + l.stamps);
-  const long long frames = (long long)B * T;
+  const long long total = (long long)B * T;     // every frame, also those past a ragged row's length
   {
     ProfScope ps("viterbi_logprob", st);
-    hipLaunchKernelGGL(vt_logprob_kernel, dim3(cdiv(frames, 4)), dim3(256), 0, st, hidden, lp, frames, n_class);
+    hipLaunchKernelGGL(vt_logprob_kernel, dim3(cdiv(total, 4)), dim3(256), 0, st, hidden, lp, total, n_class);
     PD_LAUNCH_CHECK();
   }
   {
@@ -447,13 +467,45 @@ int pd_rmvpe_viterbi(const float* hidden, const double* log_band, double log_off
     const dim3 block(round_up(n_class, 64));
     if (width <= VT_REGW)
       hipLaunchKernelGGL(vt_forward_kernel<true>, dim3(B), block, 0, st, lp, log_band, log_off, log_init, states, maps, path,
-                         logp, stamps, T, n_class, width);
+                         logp, stamps, frames, T, n_class, width);
     else
       hipLaunchKernelGGL(vt_forward_kernel<false>, dim3(B), block, 0, st, lp, log_band, log_off, log_init, states, maps, path,
-                         logp, stamps, T, n_class, width);
+                         logp, stamps, frames, T, n_class, width);
     PD_LAUNCH_CHECK();
   }
   return PD_OK;
+}
+
+int align_impl(const float* f0, float* f0_out, unsigned char* uv_out, const int* rows, int B, int n, int m, int length,
+               int n_stride, int out_stride, double t_src, double t_dst, int interp_uv, void* stream) {
+  PD_CHECK_ARG(t_src > 0.0 && t_dst > 0.0, "time steps must be positive");
+  if (n_stride > FA_MAXN) {
+    set_error("f0_align: " + std::to_string(n_stride) + " source frames (supported: " + std::to_string(FA_MAXN) + ")");
+    return PD_ERR_UNSUPPORTED;
+  }
+  ProfScope ps("f0_align", (hipStream_t)stream);
+  hipLaunchKernelGGL(f0_align_kernel, dim3(B), dim3(FA_THREADS), 0, (hipStream_t)stream, f0, f0_out, uv_out, n, m, length,
+                     t_src, t_dst, interp_uv, rows, n_stride, out_stride);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pd_rmvpe_viterbi(const float* hidden, const double* log_band, double log_off, double log_init, long long* path,
+                     double* logp, int B, int T, int n_class, int width, void* workspace, size_t ws_bytes, void* stream) {
+  return viterbi_impl(hidden, log_band, log_off, log_init, path, logp, nullptr, B, T, n_class, width, workspace, ws_bytes,
+                      stream);
+}
+
+int pd_rmvpe_viterbi_ragged(const float* hidden, const double* log_band, double log_off, double log_init, long long* path,
+                            double* logp, const int* frames, int B, int T, int n_class, int width, void* workspace,
+                            size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(frames, "null pointer");
+  return viterbi_impl(hidden, log_band, log_off, log_init, path, logp, frames, B, T, n_class, width, workspace, ws_bytes,
+                      stream);
 }
 
 int pd_f0_align(const float* f0, float* f0_out, unsigned char* uv_out, int B, int n, int m, int length, double t_src,
@@ -461,16 +513,15 @@ int pd_f0_align(const float* f0, float* f0_out, unsigned char* uv_out, int B, in
   PD_CHECK_ARG(f0 && f0_out && uv_out, "null pointer");
   PD_CHECK_ARG(B >= 1 && length >= 1, "B and length must be positive");
   PD_CHECK_ARG(n >= 2 && m >= 1, "the curve needs two source frames and one resampled frame");
-  PD_CHECK_ARG(t_src > 0.0 && t_dst > 0.0, "time steps must be positive");
-  if (n > FA_MAXN) {
-    set_error("f0_align: " + std::to_string(n) + " source frames (supported: " + std::to_string(FA_MAXN) + ")");
-    return PD_ERR_UNSUPPORTED;
-  }
-  ProfScope ps("f0_align", (hipStream_t)stream);
-  hipLaunchKernelGGL(f0_align_kernel, dim3(B), dim3(FA_THREADS), 0, (hipStream_t)stream, f0, f0_out, uv_out, n, m, length,
-                     t_src, t_dst, interp_uv);
-  PD_LAUNCH_CHECK();
-  return PD_OK;
+  return align_impl(f0, f0_out, uv_out, nullptr, B, n, m, length, n, length, t_src, t_dst, interp_uv, stream);
+}
+
+int pd_f0_align_ragged(const float* f0, float* f0_out, unsigned char* uv_out, const int* rows, int B, int n_stride,
+                       int out_stride, double t_src, double t_dst, int interp_uv, void* stream) {
+  PD_CHECK_ARG(f0 && f0_out && uv_out && rows, "null pointer");
+  PD_CHECK_ARG(B >= 1 && out_stride >= 1, "B and out_stride must be positive");
+  PD_CHECK_ARG(n_stride >= 2, "the curve needs two source frames");
+  return align_impl(f0, f0_out, uv_out, rows, B, 0, 0, 0, n_stride, out_stride, t_src, t_dst, interp_uv, stream);
 }
 
 }  // extern "C"

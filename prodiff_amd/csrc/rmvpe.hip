@@ -23,6 +23,11 @@
 //   gru_kernel        the recurrence, one block per direction and group of 16 batch rows (the M side of
 //                     v_mfma_f32_16x16x4_f32), 8 waves x 32 hidden units x the three gates; W_hh streams from
 //                     L2 every step, h lives in LDS.  No block waits on another; the time loop has T trips.
+//   ragged batches    (pd_rmvpe_forward_ragged) frames[b] real frames per row: row b's image is n_b = frames[b]
+//                     rounded up to 2^en_de_layers rows tall, n_b >> l at level l.  The conv kernels read pixels
+//                     below that height as the zeros of the image border and neither compute nor write them (a
+//                     tile that lies wholly below returns at once); the recurrence runs a row over its own n_b
+//                     frames.  The height is one scalar per block.  Without `frames` every row is T tall.
 //   the GRU input projection and the Linear head run on the implicit-GEMM engine (gemm.h).
 //
 // Every output element is one f32 fmaf chain in a fixed order that does not depend on B, on the batch row
@@ -76,6 +81,18 @@ __global__ __launch_bounds__(256) void pack_whh_kernel(float* __restrict__ dst, 
 }
 
 // ------------------------------------------------------------------ forward kernels
+// A ragged batch's per-row frame counts: device int32 [B] or null (every row T frames); unit = 2^en_de_layers
+struct RowFrames {
+  const int* frames;
+  int T, unit;
+};
+
+// Frames of row b's image: frames[b] clamped into [1, T] and rounded up to the unit (T is a multiple of it)
+__device__ __forceinline__ int padded_frames(const RowFrames& rf, int b) {
+  const int f = min(max(rf.frames[b], 1), rf.T);
+  return (f + rf.unit - 1) & ~(rf.unit - 1);
+}
+
 struct ConvArgs {
   const float* src0;   // [B][Hs][Ws][c0]
   const float* src1;   // [B][Hs][Ws][c1] or null (c1 = 0)
@@ -92,6 +109,8 @@ struct ConvArgs {
   float* out;          // [B][H][W][cout]
   int cout;
   int tc, tr, tiles_x; // tile columns and rows (tc * tr = 128), tiles per image row
+  RowFrames rf;        // ragged: image b is padded_frames(b) >> lvl rows tall inside its H-row allocation
+  int lvl;
 };
 
 template <bool SC>
@@ -102,7 +121,12 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
   const int y0 = ty * a.tr, x0 = tx * a.tc;
   const int wc = a.tc + 2, winpix = (a.tr + 2) * wc;
+  // this image's own height: blockIdx.z is the image, so it is one scalar, and the test below is block-uniform
+  int Hb = a.H;
+  if (a.rf.frames) Hb = __builtin_amdgcn_readfirstlane(padded_frames(a.rf, b) >> a.lvl);
+  if (y0 >= Hb) return;
   const int Hs = a.stuffed ? a.H >> 1 : a.H, Ws = a.stuffed ? a.W >> 1 : a.W;
+  const int Hsb = a.stuffed ? Hb >> 1 : Hb;
   // the A operand of this lane: pixel m of the tile, channels 8 h .. 8 h + 7 of the chunk
   const int m = wave * 32 + r, pr = m / a.tc, pc = m - pr * a.tc;
   const float* abase = xs + (pr * wc + pc) * CV_LD + h * 8;
@@ -131,10 +155,10 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
       const int p = idx >> 2, q = idx & 3;
       const int wy = p / wc, wx = p - wy * wc;
       const int gy = y0 - 1 + wy, gx = x0 - 1 + wx;
-      bool ok = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+      bool ok = gy >= 0 && gy < Hb && gx >= 0 && gx < a.W;
       int sy = gy, sx = gx;
       if (a.stuffed) { ok = ok && !(gy & 1) && !(gx & 1); sy = gy >> 1; sx = gx >> 1; }
-      sy = min(max(sy, 0), Hs - 1);
+      sy = min(max(sy, 0), Hsb - 1);
       sx = min(max(sx, 0), Ws - 1);
       float4 v = *reinterpret_cast<const float4*>(src + (((long long)b * Hs + sy) * Ws + sx) * cs + coff + q * 4);
       if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -164,7 +188,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
     const int mm = wave * 32 + mfma_row(reg, h);
     const int qr = mm / a.tc, qc = mm - qr * a.tc;
     const int gy = y0 + qr, gx = x0 + qc;
-    if (gy >= a.H || gx >= a.W) continue;
+    if (gy >= Hb || gx >= a.W) continue;
     const long long o = (((long long)b * a.H + gy) * a.W + gx) * a.cout + n;
     float v = acc[reg] + bv;
     if (a.relu) v = fmaxf(v, 0.f);
@@ -175,12 +199,13 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
 }
 
 // First conv: out[b][y][x][co] = relu(sum_tap w[co][tap] * bn(mel)[y + dy - 1][x + dx - 1] + bias[co]) and the
-// 1x1 shortcut sc[..][co] = ws[co] * bn(mel)[y][x] + bs[co]; bn(mel) is zero outside the image.
+// 1x1 shortcut sc[..][co] = ws[co] * bn(mel)[y][x] + bs[co]; bn(mel) is zero outside the image.  Ragged: the image
+// is padded_frames(b) rows tall, and its rows from frames[b] on read as the value 0.0 whatever mel holds there.
 __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ mel, const float* __restrict__ inbn,
                                                       const float* __restrict__ w, const float* __restrict__ bias,
                                                       const float* __restrict__ ws, const float* __restrict__ bs,
                                                       float* __restrict__ out, float* __restrict__ sc, int H, int W,
-                                                      int cout, long long total) {
+                                                      int cout, long long total, const RowFrames rf) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int co = (int)(idx % cout);
@@ -189,13 +214,20 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
   const long long by = pix / W;
   const int y = (int)(by % H);
   const long long b = by / H;
+  int Hb = H, real = H;
+  if (rf.frames) {
+    Hb = padded_frames(rf, (int)b);
+    real = min(max(rf.frames[b], 1), H);
+    if (y >= Hb) return;
+  }
   const float scale = inbn[0], shift = inbn[1];
   float acc = 0.f, centre = 0.f;
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
     const int gy = y + tap / 3 - 1, gx = x + tap % 3 - 1;
-    const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const float raw = mel[(b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)];
+    const bool ok = gy >= 0 && gy < Hb && gx >= 0 && gx < W;
+    float raw = mel[(b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)];
+    raw = gy < real ? raw : 0.f;
     const float v = ok ? __builtin_fmaf(raw, scale, shift) : 0.f;
     if (tap == 4) centre = v;
     acc = __builtin_fmaf(w[co * 9 + tap], v, acc);
@@ -207,17 +239,22 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
 // cnn: Conv2d(cin, 3, 3x3, padding 1) with bias; feat[b][t][c * F + f], the K order is tap, then channel
 __global__ __launch_bounds__(256) void conv_out_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ feat,
-                                                       int H, int W, int cin, long long total) {
+                                                       int H, int W, int cin, long long total, const RowFrames rf) {
   const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
   if (pix >= total) return;
   const int f = (int)(pix % W);
   const long long by = pix / W;
   const int y = (int)(by % H);
   const long long b = by / H;
+  int Hb = H;
+  if (rf.frames) {
+    Hb = padded_frames(rf, (int)b);
+    if (y >= Hb) return;
+  }
   float acc[3] = {0.f, 0.f, 0.f};
   for (int tap = 0; tap < 9; ++tap) {
     const int gy = y + tap / 3 - 1, gx = f + tap % 3 - 1;
-    const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
+    const bool ok = gy >= 0 && gy < Hb && gx >= 0 && gx < W;
     const float* px = x + ((b * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)) * cin;
     for (int ci = 0; ci < cin; ci += 4) {
       float4 v = *reinterpret_cast<const float4*>(px + ci);
@@ -268,6 +305,7 @@ struct GruArgs {
   const float* bhh;   // [2][768]
   float* out;         // [B][T][512]
   int B, T;
+  RowFrames rf;       // ragged: row b takes part in the frames t < padded_frames(b) only
 };
 
 __device__ __forceinline__ float sigmoid_exp(float v) { return 1.f / (1.f + expf(-v)); }
@@ -279,11 +317,24 @@ __device__ __forceinline__ float tanh_exp(float v) { return 2.f / (1.f + expf(-2
 // row r from LDS, B: W_hh of unit r), one 16-byte read per operand, chunk and tile; the weights of the next chunk
 // (at a step's end: of the next step's first chunk) are in flight under the current chunk's MFMAs.  D: column =
 // lane & 15, row = 4 g + register, so a lane holds r, z and n of the same eight (row, unit) pairs.
+// Ragged: the loop has as many trips as the block's longest row has frames; a row's state and output are written
+// only at its own frames (a select on the store: every lane runs every step and meets every barrier), so in the
+// reverse direction its state is still zero when the walk reaches its last frame.  RAGGED is a template argument
+// so that the equal-length kernel stays the code it was.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void gru_kernel(const GruArgs a) {
   __shared__ __attribute__((aligned(16))) float hs[GRU_ROWS * GRU_LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
   const int dir = blockIdx.x, b0 = blockIdx.y * GRU_ROWS, nb = min(GRU_ROWS, a.B - b0);
   for (int i = tid; i < GRU_ROWS * GRU_LD; i += 512) hs[i] = 0.f;
+  int steps = a.T, nfr[4] = {0, 0, 0, 0};   // nfr: frames of this lane's rows 4 g + i, 0 for a row past the batch
+  if (RAGGED) {
+    steps = 0;
+    for (int i = 0; i < nb; ++i) steps = max(steps, padded_frames(a.rf, b0 + i));
+    steps = __builtin_amdgcn_readfirstlane(steps);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) nfr[i] = 4 * g + i < nb ? padded_frames(a.rf, b0 + 4 * g + i) : 0;
+  }
   const float* bh = a.bhh + dir * 3 * GRU_H;
   float bhr[2], bhz[2], bhn[2];
 #pragma unroll
@@ -317,8 +368,8 @@ __global__ __launch_bounds__(512) void gru_kernel(const GruArgs a) {
   f32x4 w0[6], w1[6];
   load_w(w0, 0);
   __syncthreads();
-  for (int step = 0; step < a.T; ++step) {
-    const int t = dir ? a.T - 1 - step : step;
+  for (int step = 0; step < steps; ++step) {
+    const int t = dir ? steps - 1 - step : step;
     float xr[8], xz[8], xn[8];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -361,7 +412,7 @@ __global__ __launch_bounds__(512) void gru_kernel(const GruArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = 4 * g + i, n = wave * 32 + s * 16 + r;
-        if (row < nb) {
+        if (RAGGED ? t < nfr[i] : row < nb) {
           hs[row * GRU_LD + n] = hnew[s * 4 + i];
           a.out[((long long)(b0 + row) * a.T + t) * (2 * GRU_H) + dir * GRU_H + n] = hnew[s * 4 + i];
         }
@@ -510,8 +561,9 @@ const char* const TAG_CONVT[6] = {"rmvpe_convT_l0", "rmvpe_convT_l1", "rmvpe_con
 
 int launch_conv(const ConvW& cw, const float* src0, int c0, const float* src1, int c1, int B, int H, int W,
                 bool stuffed, const Block* sc, float* sc_out, const float* resid, float* out, hipStream_t st,
-                int lvl) {
+                int lvl, const RowFrames& rf) {
   ConvArgs a{};
+  a.rf = rf; a.lvl = lvl;
   a.src0 = src0; a.src1 = src1 ? src1 : src0; a.c0 = c0; a.c1 = src1 ? c1 : 0;
   a.H = H; a.W = W; a.stuffed = stuffed ? 1 : 0;
   a.wp = cw.w; a.bias = cw.b; a.relu = 1;
@@ -537,13 +589,13 @@ int launch_conv(const ConvW& cw, const float* src0, int c0, const float* src1, i
 
 // ConvBlockRes: x (c0 [+ c1 from x1] channels) -> out; h1 and scb are scratch, none of the four may alias
 int run_block(const Block& bk, const float* x, int c0, const float* x1, int c1, int B, int H, int W, float* h1,
-              float* scb, float* out, hipStream_t st, int lvl) {
+              float* scb, float* out, hipStream_t st, int lvl, const RowFrames& rf) {
   if (bk.sc) {
-    PD_TRY(launch_conv(bk.c1, x, c0, x1, c1, B, H, W, false, &bk, scb, nullptr, h1, st, lvl));
-    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, out, st, lvl));
+    PD_TRY(launch_conv(bk.c1, x, c0, x1, c1, B, H, W, false, &bk, scb, nullptr, h1, st, lvl, rf));
+    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, out, st, lvl, rf));
   } else {
-    PD_TRY(launch_conv(bk.c1, x, c0, nullptr, 0, B, H, W, false, nullptr, nullptr, nullptr, h1, st, lvl));
-    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, x, out, st, lvl));
+    PD_TRY(launch_conv(bk.c1, x, c0, nullptr, 0, B, H, W, false, nullptr, nullptr, nullptr, h1, st, lvl, rf));
+    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, x, out, st, lvl, rf));
   }
   return PD_OK;
 }
@@ -698,14 +750,20 @@ size_t pd_rmvpe_workspace_size(const pd_rmvpe* h, int B, int T) {
   return plan_ws(h->d, B, T).total * sizeof(float);
 }
 
-int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* feat, int B, int T, void* workspace,
-                     size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// pd_rmvpe_forward (frames = null) and pd_rmvpe_forward_ragged
+int forward_impl(const pd_rmvpe* h, const float* mel, const int* frames, float* hidden, float* feat, int B, int T,
+                 void* workspace, size_t ws_bytes, void* stream) {
   PD_CHECK_ARG(h && mel && hidden, "null pointer");
   PD_CHECK_ARG(B > 0 && B <= 65535, "B must lie in [1, 65535]");
   const pd_rmvpe_dims& d = h->d;
   const int L = d.en_de_layers, c0 = d.en_out_channels, F = d.n_mels;
   PD_CHECK_ARG(T > 0 && T % (1 << L) == 0, "T must be a positive multiple of 2^en_de_layers");
   PD_CHECK_ARG((long long)B * T * F * c0 < (1ll << 31), "B * T too large for one call");
+  const RowFrames rf{frames, T, 1 << L};
   const WsPlan wsp = plan_ws(d, B, T);
   if (!workspace || ws_bytes < wsp.total * sizeof(float) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
     set_error("rmvpe: workspace smaller than pd_rmvpe_workspace_size (or not 16-byte aligned)");
@@ -734,12 +792,12 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
         {
           ProfScope ps("rmvpe_conv_in", st);
           hipLaunchKernelGGL(conv_in_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, mel, h->inbn, h->w_in, h->b_in,
-                             h->ws_in, h->bs_in, h1, scb, H, W, cout, total);
+                             h->ws_in, h->bs_in, h1, scb, H, W, cout, total, rf);
           PD_LAUNCH_CHECK();
         }
-        PD_TRY(launch_conv(lv[0].c2, h1, cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, dst, st, i));
+        PD_TRY(launch_conv(lv[0].c2, h1, cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, dst, st, i, rf));
       } else {
-        PD_TRY(run_block(lv[j], cur, lv[j].cin, nullptr, 0, B, H, W, h1, scb, dst, st, i));
+        PD_TRY(run_block(lv[j], cur, lv[j].cin, nullptr, 0, B, H, W, h1, scb, dst, st, i, rf));
       }
       cur = dst;
     }
@@ -759,7 +817,7 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
       for (int j = 0; j < d.n_blocks; ++j) {
         const Block& bk = h->inter[i][j];
         float* dst = cur == ping ? pong : ping;
-        PD_TRY(run_block(bk, cur, bk.cin, nullptr, 0, B, H, W, h1, scb, dst, st, L));
+        PD_TRY(run_block(bk, cur, bk.cin, nullptr, 0, B, H, W, h1, scb, dst, st, L, rf));
         cur = dst;
       }
   }
@@ -768,13 +826,13 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
     const int lvl = L - 1 - i, H = T >> lvl, W = F >> lvl, cout = c0 << lvl;
     float* upb = cur == ping ? pong : ping;
     PD_TRY(launch_conv(h->up[i], cur, 2 * cout, nullptr, 0, B, H, W, true, nullptr, nullptr, nullptr, upb, st,
-                       lvl));
+                       lvl, rf));
     cur = upb;
     for (int j = 0; j < d.n_blocks; ++j) {
       const Block& bk = h->dec[i][j];
       float* dst = cur == ping ? pong : ping;
-      if (j == 0) PD_TRY(run_block(bk, cur, cout, skip[lvl], cout, B, H, W, h1, scb, dst, st, lvl));
-      else PD_TRY(run_block(bk, cur, cout, nullptr, 0, B, H, W, h1, scb, dst, st, lvl));
+      if (j == 0) PD_TRY(run_block(bk, cur, cout, skip[lvl], cout, B, H, W, h1, scb, dst, st, lvl, rf));
+      else PD_TRY(run_block(bk, cur, cout, nullptr, 0, B, H, W, h1, scb, dst, st, lvl, rf));
       cur = dst;
     }
   }
@@ -783,7 +841,7 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
     const long long total = (long long)B * T * F;
     ProfScope ps("rmvpe_conv_out", st);
     hipLaunchKernelGGL(conv_out_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, cur, h->w_cnn, h->b_cnn, featb, T, F,
-                       c0, total);
+                       c0, total, rf);
     PD_LAUNCH_CHECK();
   }
   // ---- fc
@@ -795,10 +853,11 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
     GemmArgs g = make_gemm(B, T, 6 * GRU_H, h->w_ih, feat_c, h->b_ih, xp, (long long)T * 6 * GRU_H, 6 * GRU_H);
     add_seg(g, make_seg(featb, (long long)T * feat_c, feat_c, feat_c, 0));
     PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_RMVPE_XPROJ>(g, st, "rmvpe_gru_xproj")));
-    GruArgs ga{xp, h->w_hh, h->b_hh, go, B, T};
+    GruArgs ga{xp, h->w_hh, h->b_hh, go, B, T, rf};
     {
       ProfScope ps("rmvpe_gru", st);
-      hipLaunchKernelGGL(gru_kernel, dim3(2, cdiv(B, GRU_ROWS)), dim3(512), 0, st, ga);
+      if (frames) hipLaunchKernelGGL(gru_kernel<true>, dim3(2, cdiv(B, GRU_ROWS)), dim3(512), 0, st, ga);
+      else hipLaunchKernelGGL(gru_kernel<false>, dim3(2, cdiv(B, GRU_ROWS)), dim3(512), 0, st, ga);
       PD_LAUNCH_CHECK();
     }
     fc_src = go;
@@ -814,6 +873,21 @@ int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* 
     PD_LAUNCH_CHECK();
   }
   return PD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pd_rmvpe_forward(const pd_rmvpe* h, const float* mel, float* hidden, float* feat, int B, int T, void* workspace,
+                     size_t ws_bytes, void* stream) {
+  return forward_impl(h, mel, nullptr, hidden, feat, B, T, workspace, ws_bytes, stream);
+}
+
+int pd_rmvpe_forward_ragged(const pd_rmvpe* h, const float* mel, const int* frames, float* hidden, float* feat, int B,
+                            int T, void* workspace, size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(frames, "null pointer");
+  return forward_impl(h, mel, frames, hidden, feat, B, T, workspace, ws_bytes, stream);
 }
 
 int pd_rmvpe_decode(const float* hidden, float* f0, int B, int T, int n_class, float thred, const long long* center,

@@ -7,6 +7,12 @@ with torch ops (F.conv2d, F.batch_norm, F.conv_transpose2d, nn.GRU) in eager mod
 JSON line.
 
     python tools/bench_rmvpe.py [--calls 100] [--warmup 5] [--batch 8] [--seconds 10] [--no-torch]
+    python tools/bench_rmvpe.py --ragged N [--calls 30]
+
+--ragged N times ``RMVPE.get_pitch_batch`` (44.1 kHz audio to f0 on the mel grid, hop 512) on clips of the first N
+lengths of tests/golden/ds_lengths.json three ways: (a) one ragged call on the list of clips, (b) one call per clip
+(the only way without ragged batches), (c) one equal-length call on the clips padded to the longest (its results
+are not the clips' own; only its time is of interest).  Prints one JSON line with median, min and p90 of each.
 
 The conv floor: 2 x pixels x 9 C_in C_out FLOP per conv on the f32 MFMA (157.3 TFLOP/s dense).
 """
@@ -102,8 +108,52 @@ def torch_e2e0(P, model, mel, gru):
     return torch.sigmoid(F.linear(gru(x)[0], P["fc.1.weight"], P["fc.1.bias"]))
 
 
+def bench_ragged(a):
+    dev = torch.device("cuda:0")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "tests", "golden", "ds_lengths.json")) as f:
+        ds = json.load(f)
+    sr, hop = int(ds["sr"]), int(ds["hop"])
+    lengths = [int(v) for v in ds["frames"][:a.ragged]]
+    if len(lengths) < a.ragged:
+        raise SystemExit(f"ds_lengths.json holds {len(lengths)} lengths")
+    pe = RM.RMVPE({})
+    pe.model.load_state_dict({k: torch.from_numpy(v) for k, v in
+                              synth.synth_rmvpe_params(synth.rmvpe_param_shapes(**FULL), a.seed).items()})
+    pe.model.to(dev)
+    g = torch.Generator().manual_seed(0)
+    clips = [((torch.rand(n * hop, generator=g) * 2 - 1) * 0.3).to(dev) for n in lengths]
+    padded = torch.zeros(len(clips), max(lengths) * hop, device=dev)
+    for b, c in enumerate(clips):
+        padded[b, :c.numel()] = c
+    singles = [c[None] for c in clips]
+
+    def ragged():
+        return pe.get_pitch_batch(clips, sr, lengths, hop_size=hop)
+
+    def one_by_one():
+        return [pe.get_pitch_batch(c, sr, n, hop_size=hop) for c, n in zip(singles, lengths)]
+
+    def padded_call():
+        return pe.get_pitch_batch(padded, sr, max(lengths), hop_size=hop)
+
+    f0, uv = ragged()
+    same = all(torch.equal(f0[b, :n], r[0][0]) and torch.equal(uv[b, :n], r[1][0])
+               for b, (n, r) in enumerate(zip(lengths, one_by_one())))
+    line = {"bench": "rmvpe_ragged", "N": len(lengths), "seconds": [round(n * hop / sr, 2) for n in lengths],
+            "calls": a.calls, "device": torch.cuda.get_device_name(0), "lib": _lib.lib().pd_build_config().decode(),
+            "ragged_equals_single_calls": bool(same)}
+    for key, fn in (("ragged", ragged), ("single_calls", one_by_one), ("padded", padded_call)):
+        med, best, p90 = time_calls(fn, a.calls, a.warmup)
+        line[key + "_ms"] = {"median": round(med, 3), "min": round(best, 3), "p90": round(p90, 3)}
+    print(json.dumps(line), flush=True)
+    pe.model.close()
+    pe.mel_extractor.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", type=int, default=0, metavar="N")
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
@@ -111,6 +161,8 @@ def main():
     ap.add_argument("--seed", type=int, default=44)
     ap.add_argument("--no-torch", action="store_true")
     a = ap.parse_args()
+    if a.ragged:
+        return bench_ragged(a)
     dev = torch.device("cuda:0")
     B, Lw = a.batch, int(round(a.seconds * 16000))
     shapes = synth.rmvpe_param_shapes(**FULL)
