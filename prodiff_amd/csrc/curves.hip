@@ -476,23 +476,22 @@ int pd_curves_create(const pd_curves_dims* dims, void* stream, pd_curves** out) 
   PD_CHECK_ARG(dims && out, "null pointer");
   PD_TRY(check_dims(*dims));
   hipStream_t st = (hipStream_t)stream;
-  pd_curves* h = new pd_curves();
+  std::unique_ptr<pd_curves> h(new pd_curves());
   h->d = *dims;
   h->p.sr = dims->samplerate; h->p.win = dims->win_size; h->p.hop = dims->hop_size;
   h->p.nbins = dims->win_size / 2 + 1; h->p.hw = dims->half_width;
   WeightPool& wp = h->weights;
+  pd_curves* hp = h.get();
   wp.add(&h->w, (size_t)h->p.win);
   wp.add(&h->tw, 2 * (size_t)h->p.win);
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "curves"));
-    hipLaunchKernelGGL(cv_table_kernel, dim3(cdiv(h->p.win, 256)), dim3(256), 0, st, h->w,
-                       reinterpret_cast<float2*>(h->tw), h->p.win);
+  wp.then([=]() {   // one kernel writes the window and the twiddles
+    hipLaunchKernelGGL(cv_table_kernel, dim3(cdiv(hp->p.win, 256)), dim3(256), 0, st, hp->w,
+                       reinterpret_cast<float2*>(hp->tw), hp->p.win);
     PD_LAUNCH_CHECK();
     return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  });
+  PD_TRY(wp.commit(st, "curves"));
+  *out = h.release();
   return PD_OK;
 }
 

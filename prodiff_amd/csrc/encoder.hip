@@ -370,37 +370,24 @@ int FftStack::init(int hidden, int layers, int ffn_kernel, int num_heads, const 
   return PD_OK;
 }
 
-void FftStack::plan(WeightPool& wp) {
+void FftStack::add_to(WeightPool& wp, ParamView& pv) {
   ln1g.resize(L); ln1b.resize(L); Wqkv.resize(L); Wo.resize(L); ln2g.resize(L);
   ln2b.resize(L); W1.resize(L); b1.resize(L); W2.resize(L); b2.resize(L);
   // GEMM weights packed as W[n][k]
   for (int l = 0; l < L; ++l) {
-    wp.add(&ln1g[l], H); wp.add(&ln1b[l], H);
-    wp.add(&Wqkv[l], (size_t)3 * H * H); wp.add(&Wo[l], (size_t)H * H);
-    wp.add(&ln2g[l], H); wp.add(&ln2b[l], H);
-    wp.add(&W1[l], (size_t)F * K * H); wp.add(&b1[l], F);
-    wp.add(&W2[l], (size_t)H * F); wp.add(&b2[l], H);
+    wp.add_copy(&ln1g[l], H, pv.next());
+    wp.add_copy(&ln1b[l], H, pv.next());
+    wp.add_copy(&Wqkv[l], (size_t)3 * H * H, pv.next());   // in_proj_weight [3H, H] = W[n][k]
+    wp.add_copy(&Wo[l], (size_t)H * H, pv.next());
+    wp.add_copy(&ln2g[l], H, pv.next());
+    wp.add_copy(&ln2b[l], H, pv.next());
+    wp.add_conv(&W1[l], pv.next(), F, H, K, H);            // ffn_1 [F, H, K]
+    wp.add_copy(&b1[l], F, pv.next());
+    wp.add_copy(&W2[l], (size_t)H * F, pv.next());
+    wp.add_copy(&b2[l], H, pv.next());
   }
-  wp.add(&lnfg, H); wp.add(&lnfb, H);
-}
-
-int FftStack::pack(const float* const* params, int& p, hipStream_t st) {
-  auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
-  for (int l = 0; l < L; ++l) {
-    PD_TRY(cp(ln1g[l], params[p++], H));
-    PD_TRY(cp(ln1b[l], params[p++], H));
-    PD_TRY(cp(Wqkv[l], params[p++], (size_t)3 * H * H));   // in_proj_weight [3H, H] = W[n][k]
-    PD_TRY(cp(Wo[l], params[p++], (size_t)H * H));
-    PD_TRY(cp(ln2g[l], params[p++], H));
-    PD_TRY(cp(ln2b[l], params[p++], H));
-    PD_TRY(pack_conv(W1[l], K * H, 0, 0, H, params[p++], F, H, K, st));   // ffn_1 [F, H, K]
-    PD_TRY(cp(b1[l], params[p++], F));
-    PD_TRY(cp(W2[l], params[p++], (size_t)H * F));
-    PD_TRY(cp(b2[l], params[p++], H));
-  }
-  PD_TRY(cp(lnfg, params[p++], H));
-  PD_TRY(cp(lnfb, params[p++], H));
-  return PD_OK;
+  wp.add_copy(&lnfg, H, pv.next());
+  wp.add_copy(&lnfb, H, pv.next());
 }
 
 FftWs fft_ws(const FftStack& s, size_t R, size_t base) {
@@ -560,42 +547,28 @@ int pd_cond_create(const pd_cond_dims* dims, const float* const* params, int dty
   PD_CHECK_ARG(!d.use_gender_id || d.use_lang_id, "use_gender_id needs use_lang_id (gender ids index lang_embed)");
   PD_TRY(check_params(params, pd_cond_num_params(dims)));
   hipStream_t st = (hipStream_t)stream;
-  pd_cond* h = new pd_cond();
+  std::unique_ptr<pd_cond> h(new pd_cond());
   h->d = d;
   h->H = d.hidden_size;
   h->enc.init(d.hidden_size, d.enc_layers, d.enc_ffn_kernel_size, d.num_heads, "pd_cond");   // checked above
   const int H = h->H;
-  // pool layout (floats, 64-aligned)
+  // the pool's slots (64-float aligned), each filled from the next parameter
   WeightPool& wp = h->weights;
-  h->enc.plan(wp);
-  wp.add(&h->emb, (size_t)d.vocab_size * H);
-  if (d.use_dur_embed) { wp.add(&h->dur_w, H); wp.add(&h->dur_b, H); }
-  if (d.use_spk_id) wp.add(&h->spk, (size_t)d.num_spk * H);
-  if (d.use_gender_id) wp.add(&h->gender, (size_t)2 * H);
-  if (d.use_lang_id) wp.add(&h->lang, (size_t)d.num_langs * H);
-  wp.add(&h->pw, H); wp.add(&h->pb, H);
-  if (d.use_voicing_embed) { wp.add(&h->vw, H); wp.add(&h->vb, H); }
-  if (d.use_breath_embed) { wp.add(&h->bw, H); wp.add(&h->bb, H); }
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "condition-encoder"));
-    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
-    int p = 0;
-    PD_TRY(h->enc.pack(params, p, st));
-    PD_TRY(cp(h->emb, params[p++], (size_t)d.vocab_size * H));
-    if (d.use_dur_embed) { PD_TRY(cp(h->dur_w, params[p++], H)); PD_TRY(cp(h->dur_b, params[p++], H)); }
-    if (d.use_spk_id) PD_TRY(cp(h->spk, params[p++], (size_t)d.num_spk * H));
-    if (d.use_gender_id) PD_TRY(cp(h->gender, params[p++], (size_t)2 * H));
-    if (d.use_lang_id) PD_TRY(cp(h->lang, params[p++], (size_t)d.num_langs * H));
-    PD_TRY(cp(h->pw, params[p++], H));
-    PD_TRY(cp(h->pb, params[p++], H));
-    if (d.use_voicing_embed) { PD_TRY(cp(h->vw, params[p++], H)); PD_TRY(cp(h->vb, params[p++], H)); }
-    if (d.use_breath_embed) { PD_TRY(cp(h->bw, params[p++], H)); PD_TRY(cp(h->bb, params[p++], H)); }
-    if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
-    return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  ParamView pv{params, pd_cond_num_params(dims)};
+  h->enc.add_to(wp, pv);
+  wp.add_copy(&h->emb, (size_t)d.vocab_size * H, pv.next());
+  if (d.use_dur_embed) { wp.add_copy(&h->dur_w, H, pv.next()); wp.add_copy(&h->dur_b, H, pv.next()); }
+  if (d.use_spk_id) wp.add_copy(&h->spk, (size_t)d.num_spk * H, pv.next());
+  if (d.use_gender_id) wp.add_copy(&h->gender, (size_t)2 * H, pv.next());
+  if (d.use_lang_id) wp.add_copy(&h->lang, (size_t)d.num_langs * H, pv.next());
+  wp.add_copy(&h->pw, H, pv.next());
+  wp.add_copy(&h->pb, H, pv.next());
+  if (d.use_voicing_embed) { wp.add_copy(&h->vw, H, pv.next()); wp.add_copy(&h->vb, H, pv.next()); }
+  if (d.use_breath_embed) { wp.add_copy(&h->bw, H, pv.next()); wp.add_copy(&h->bb, H, pv.next()); }
+  PD_TRY(pv.done("pd_cond"));
+  PD_TRY(wp.commit(st, "condition-encoder"));
+  if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
+  *out = h.release();
   return PD_OK;
 }
 

@@ -2995,125 +2995,117 @@ int fd_create(const fd_dims* dims, const float* const* params, int dtype, void* 
   PD_CHECK_ARG(dims->num_blocks >= 1 && dims->num_blocks <= 4, "num_blocks in [1,4]");
   PD_TRY(check_params(params, FD_NUM_PARAMS(dims->num_blocks)));
   hipStream_t st = (hipStream_t)stream;
-  fd_model* m = new fd_model();
+  std::unique_ptr<fd_model> m(new fd_model());
   m->nblocks = dims->num_blocks;
   m->dtype = dtype;
   int hop = 1;
   for (int n = 0; n < m->nblocks; ++n) {
     m->ratios[n] = dims->upsample_ratios[n];
-    if (m->ratios[n] < 2 || m->ratios[n] > 16) { delete m; set_error("upsample ratio in [2,16]"); return PD_ERR_ARG; }
+    if (m->ratios[n] < 2 || m->ratios[n] > 16) { set_error("upsample ratio in [2,16]"); return PD_ERR_ARG; }
     hop *= m->ratios[n];
     m->hops[n] = hop;
   }
-  // allocation plan
-  WeightPool& wp = m->weights;
-  wp.add(&m->fc1_w, (size_t)EMB_MID * EMB_IN); wp.add(&m->fc1_b, EMB_MID);
-  wp.add(&m->fc2_w, (size_t)EMB_OUT * EMB_MID); wp.add(&m->fc2_b, EMB_OUT);
-  wp.add(&m->first_w, 224); wp.add(&m->first_b, CI);
-  wp.add(&m->final_w, 224); wp.add(&m->final_b, 1);
+  // The parameters, taken in ABI order (include/prodiff_hip.h, FD_PARAM_ORDER) into named locals: the pool below
+  // holds them in another order.
+  ParamView pv{params, FD_NUM_PARAMS(m->nblocks)};
+  const float *first_w = pv.next(), *first_b = pv.next();
+  const float *fc1_w = pv.next(), *fc1_b = pv.next();
+  const float *fc2_w = pv.next(), *fc2_b = pv.next();
+  struct BlkSrc {
+    const float *up_w, *up_b, *kin_w, *kin_b, *kres_w[6], *kres_b[6], *kk_w, *kk_b, *kb_w, *kb_b, *fct_w, *fct_b,
+        *cv_w[NLY], *cv_b[NLY];
+  } bsrc[4];
   for (int n = 0; n < m->nblocks; ++n) {
-    auto& K = m->blk[n];
-    wp.add(&K.up_w, (size_t)2 * m->ratios[n] * CI * CI); wp.add(&K.up_b, CI);
-    wp.add(&K.upf_w, (size_t)2 * m->ratios[n] * CI * CI);
-    wp.add(&K.fct_w, (size_t)CC * EMB_OUT); wp.add(&K.fct_b, CC);
-    wp.add(&K.kin_w, (size_t)HK * 5 * 96); wp.add(&K.kin_b, HK);
-    for (int j = 0; j < 6; ++j) { wp.add(&K.kres_w[j], (size_t)HK * 3 * HK); wp.add(&K.kres_b[j], HK); }
-    wp.add(&K.kk_w, (size_t)NLY * KPERLAYER * 3 * HK); wp.add(&K.kk_b, (size_t)NLY * KPERLAYER);
-    wp.add(&K.kb_w, (size_t)2 * CI * NLY * 3 * HK); wp.add(&K.kb_b, (size_t)2 * CI * NLY);
-    for (int i = 0; i < NLY; ++i) { wp.add(&K.cv_w[i], (size_t)CI * 96); wp.add(&K.cv_b[i], CI); }
+    BlkSrc& s = bsrc[n];
+    s.up_w = pv.next(); s.up_b = pv.next();
+    s.kin_w = pv.next(); s.kin_b = pv.next();
+    for (int j = 0; j < 6; ++j) { s.kres_w[j] = pv.next(); s.kres_b[j] = pv.next(); }
+    s.kk_w = pv.next(); s.kk_b = pv.next();
+    s.kb_w = pv.next(); s.kb_b = pv.next();
+    s.fct_w = pv.next(); s.fct_b = pv.next();
+    for (int i = 0; i < NLY; ++i) { s.cv_w[i] = pv.next(); s.cv_b[i] = pv.next(); }
+  }
+  struct DnSrc { const float *rw, *rb, *w0, *b0, *w1, *b1, *w2, *b2; } dsrc[4];
+  for (int n = 0; n < m->nblocks; ++n)
+    dsrc[n] = {pv.next(), pv.next(), pv.next(), pv.next(), pv.next(), pv.next(), pv.next(), pv.next()};
+  const float *final_w = pv.next(), *final_b = pv.next();
+  PD_TRY(pv.done("fd_create"));
+
+  // The pool, slot by slot
+  WeightPool& wp = m->weights;
+  wp.add_copy(&m->fc1_w, (size_t)EMB_MID * EMB_IN, fc1_w); wp.add_copy(&m->fc1_b, EMB_MID, fc1_b);
+  wp.add_copy(&m->fc2_w, (size_t)EMB_OUT * EMB_MID, fc2_w); wp.add_copy(&m->fc2_b, EMB_OUT, fc2_b);
+  wp.add_copy(&m->first_w, 224, first_w); wp.add_copy(&m->first_b, CI, first_b);
+  wp.add(&m->final_w, 224, [=](float* dst) {
+    hipLaunchKernelGGL(pack_final_kernel, dim3(1), dim3(256), 0, st, dst, final_w);
+    PD_LAUNCH_CHECK();
+    return PD_OK;
+  });
+  wp.add_copy(&m->final_b, 1, final_b);
+  for (int n = 0; n < m->nblocks; ++n) {
+    fd_model::Block* K = &m->blk[n];
+    const BlkSrc s = bsrc[n];
+    const int r = m->ratios[n];
+    const size_t nup = (size_t)2 * r * CI * CI;
+    wp.add(&K->up_w, nup, [=](float* dst) {
+      hipLaunchKernelGGL(pack_upsample_kernel, dim3(cdiv(nup, 256)), dim3(256), 0, st, dst, s.up_w, 2 * r);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+    wp.add_copy(&K->up_b, CI, s.up_b);
+    wp.add(&K->upf_w, nup, [=](float* dst) {   // the phase form of up_w, packed just above
+      hipLaunchKernelGGL(pack_upsample_phase_kernel, dim3(cdiv(nup, 256)), dim3(256), 0, st, dst, K->up_w, r);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+    wp.add_copy(&K->fct_w, (size_t)CC * EMB_OUT, s.fct_w); wp.add_copy(&K->fct_b, CC, s.fct_b);
+    wp.add_conv(&K->kin_w, s.kin_w, HK, CC, 5, 96); wp.add_copy(&K->kin_b, HK, s.kin_b);
+    for (int j = 0; j < 6; ++j) {
+      wp.add_conv(&K->kres_w[j], s.kres_w[j], HK, HK, 3, HK); wp.add_copy(&K->kres_b[j], HK, s.kres_b[j]);
+    }
+    // one kernel packs the kernel-predictor's conv into both slots
+    const size_t nkk = (size_t)NLY * KPERLAYER * 3 * HK;
+    wp.add(&K->kk_w, nkk); wp.add(&K->kk_b, (size_t)NLY * KPERLAYER);
+    wp.then([=]() {
+      hipLaunchKernelGGL(pack_kernel_conv_kernel, dim3(cdiv(nkk, 256)), dim3(256), 0, st, K->kk_w, K->kk_b, s.kk_w,
+                         s.kk_b);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+    wp.add_conv(&K->kb_w, s.kb_w, 2 * CI * NLY, HK, 3, HK); wp.add_copy(&K->kb_b, (size_t)2 * CI * NLY, s.kb_b);
+    for (int i = 0; i < NLY; ++i) {
+      wp.add_conv(&K->cv_w[i], s.cv_w[i], CI, CI, 3, CI); wp.add_copy(&K->cv_b[i], CI, s.cv_b[i]);
+    }
   }
   for (int n = 0; n < m->nblocks; ++n) {
     auto& D = m->dn[n];
-    wp.add(&D.c0_w, (size_t)CI * 96); wp.add(&D.c0_b, CI);
-    wp.add(&D.c1_w, (size_t)CI * 96); wp.add(&D.c1_b, CI);
-    wp.add(&D.c2_w, (size_t)CI * 128); wp.add(&D.c2_b, CI);
+    const DnSrc s = dsrc[n];
+    wp.add_conv(&D.c0_w, s.w0, CI, CI, 3, CI); wp.add_copy(&D.c0_b, CI, s.b0);
+    wp.add_conv(&D.c1_w, s.w1, CI, CI, 3, CI); wp.add_copy(&D.c1_b, CI, s.b1);
+    wp.add(&D.c2_w, (size_t)CI * 128, [=](float* dst) {   // [CI][3 taps of CI | the 1x1 residual conv]
+      PD_TRY(pack_conv(dst, 128, 0, 0, CI, s.w2, CI, CI, 3, st));
+      return pack_conv(dst, 128, 0, 96, CI, s.rw, CI, CI, 1, st);
+    });
+    wp.add(&D.c2_b, CI, [=](float* dst) { return add_vectors(dst, s.b2, s.rb, CI, st); });
   }
-
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "FastDiff"));
-    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
-    int p = 0;
-    auto nxt = [&]() { const float* q = params[p++]; return q; };
-    // order: see include/prodiff_hip.h (FD_PARAM_ORDER)
-    {
-      const float* w = nxt(); const float* b = nxt();
-      PD_TRY(cp(m->first_w, w, 224)); PD_TRY(cp(m->first_b, b, CI));
-    }
-    PD_TRY(cp(m->fc1_w, nxt(), (size_t)EMB_MID * EMB_IN)); PD_TRY(cp(m->fc1_b, nxt(), EMB_MID));
-    PD_TRY(cp(m->fc2_w, nxt(), (size_t)EMB_OUT * EMB_MID)); PD_TRY(cp(m->fc2_b, nxt(), EMB_OUT));
+  PD_TRY(wp.commit(st, "FastDiff"));
+  if (dtype == PD_DTYPE_BF16) {
+    PD_TRY(wp.mirror_bf16(st));
+    // pre-scaled kernel-predictor weights of every block (bf16 rows, fp32 biases)
+    const size_t nw = (size_t)NLY * KPERLAYER * 3 * HK, nbias = (size_t)NLY * KPERLAYER;
+    PD_TRY(m->kps.alloc(m->nblocks * (nw * sizeof(__bf16) + nbias * sizeof(float)),
+                        "the FastDiff pre-scaled kernel-predictor weights"));
+    float* kps = static_cast<float*>(m->kps.get());
     for (int n = 0; n < m->nblocks; ++n) {
       auto& K = m->blk[n];
-      const int r = m->ratios[n];
-      {
-        const float* w = nxt();
-        hipLaunchKernelGGL(pack_upsample_kernel, dim3(cdiv(CI * CI * 2 * r, 256)), dim3(256), 0, st, K.up_w, w, 2 * r);
-        PD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pack_upsample_phase_kernel, dim3(cdiv(CI * CI * 2 * r, 256)), dim3(256), 0, st, K.upf_w,
-                           K.up_w, r);
-        PD_LAUNCH_CHECK();
-        PD_TRY(cp(K.up_b, nxt(), CI));
-      }
-      PD_TRY(pack_conv(K.kin_w, 5 * 96, 0, 0, 96, nxt(), HK, CC, 5, st));
-      PD_TRY(cp(K.kin_b, nxt(), HK));
-      for (int j = 0; j < 6; ++j) {
-        PD_TRY(pack_conv(K.kres_w[j], 3 * HK, 0, 0, HK, nxt(), HK, HK, 3, st));
-        PD_TRY(cp(K.kres_b[j], nxt(), HK));
-      }
-      {
-        const float* w = nxt(); const float* b = nxt();
-        const long long total = (long long)NLY * KPERLAYER * HK * 3;
-        hipLaunchKernelGGL(pack_kernel_conv_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, K.kk_w, K.kk_b, w, b);
-        PD_LAUNCH_CHECK();
-      }
-      PD_TRY(pack_conv(K.kb_w, 3 * HK, 0, 0, HK, nxt(), 2 * CI * NLY, HK, 3, st));
-      PD_TRY(cp(K.kb_b, nxt(), 2 * CI * NLY));
-      PD_TRY(cp(K.fct_w, nxt(), (size_t)CC * EMB_OUT));
-      PD_TRY(cp(K.fct_b, nxt(), CC));
-      for (int i = 0; i < NLY; ++i) {
-        PD_TRY(pack_conv(K.cv_w[i], 96, 0, 0, CI, nxt(), CI, CI, 3, st));
-        PD_TRY(cp(K.cv_b[i], nxt(), CI));
-      }
-    }
-    for (int n = 0; n < m->nblocks; ++n) {
-      auto& D = m->dn[n];
-      const float* rw = nxt(); const float* rb = nxt();
-      const float* w0 = nxt(); const float* b0 = nxt();
-      const float* w1 = nxt(); const float* b1 = nxt();
-      const float* w2 = nxt(); const float* b2 = nxt();
-      PD_TRY(pack_conv(D.c0_w, 96, 0, 0, CI, w0, CI, CI, 3, st)); PD_TRY(cp(D.c0_b, b0, CI));
-      PD_TRY(pack_conv(D.c1_w, 96, 0, 0, CI, w1, CI, CI, 3, st)); PD_TRY(cp(D.c1_b, b1, CI));
-      PD_TRY(pack_conv(D.c2_w, 128, 0, 0, CI, w2, CI, CI, 3, st));
-      PD_TRY(pack_conv(D.c2_w, 128, 0, 96, CI, rw, CI, CI, 1, st));
-      PD_TRY(add_vectors(D.c2_b, b2, rb, CI, st));
-    }
-    {
-      const float* w = nxt(); const float* b = nxt();
-      hipLaunchKernelGGL(pack_final_kernel, dim3(1), dim3(256), 0, st, m->final_w, w);
+      K.kks_b = kps + n * nbias;
+      K.kks_w = reinterpret_cast<__bf16*>(kps + m->nblocks * nbias) + n * nw;
+      hipLaunchKernelGGL(kp_prescale_kernel, dim3(cdiv((long long)nw, 256)), dim3(256), 0, st, K.kk_w, K.kk_b, K.kks_w,
+                         K.kks_b);
       PD_LAUNCH_CHECK();
-      PD_TRY(cp(m->final_b, b, 1));
     }
-    if (p != FD_NUM_PARAMS(m->nblocks)) { set_error("fd_create: parameter count mismatch"); return PD_ERR_ARG; }
-    if (dtype == PD_DTYPE_BF16) {
-      PD_TRY(wp.mirror_bf16(st));
-      // pre-scaled kernel-predictor weights of every block (bf16 rows, fp32 biases)
-      const size_t nw = (size_t)NLY * KPERLAYER * 3 * HK, nbias = (size_t)NLY * KPERLAYER;
-      PD_TRY(m->kps.alloc(m->nblocks * (nw * sizeof(__bf16) + nbias * sizeof(float)),
-                          "the FastDiff pre-scaled kernel-predictor weights"));
-      float* kps = static_cast<float*>(m->kps.get());
-      for (int n = 0; n < m->nblocks; ++n) {
-        auto& K = m->blk[n];
-        K.kks_b = kps + n * nbias;
-        K.kks_w = reinterpret_cast<__bf16*>(kps + m->nblocks * nbias) + n * nw;
-        hipLaunchKernelGGL(kp_prescale_kernel, dim3(cdiv((long long)nw, 256)), dim3(256), 0, st, K.kk_w, K.kk_b, K.kks_w,
-                           K.kks_b);
-        PD_LAUNCH_CHECK();
-      }
-    }
-    return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete m; return rc; }
-  *out = m;
+  }
+  *out = m.release();
   return PD_OK;
 }
 

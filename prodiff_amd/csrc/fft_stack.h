@@ -36,11 +36,10 @@ struct FftStack {
   // PD_ERR_ARG / PD_ERR_UNSUPPORTED (with the error text set, prefixed by `who`) for dims the kernels do not take
   int init(int hidden, int layers, int ffn_kernel, int num_heads, const char* who);
   int num_params() const { return 10 * L + 2; }
-  // the stack must not move between plan() and the pool's commit()
-  void plan(WeightPool& wp);
-  // layers.l.op.{layer_norm1.weight, .bias, self_attn.in_proj_weight, self_attn.out_proj.weight, layer_norm2.weight,
-  // .bias, ffn.ffn_1.weight, .bias, ffn.ffn_2.weight, .bias} for l < L, then layer_norm.{weight,bias}, from params[p]
-  int pack(const float* const* params, int& p, hipStream_t st);
+  // Adds the stack's slots, each filled from the next parameter: layers.l.op.{layer_norm1.weight, .bias,
+  // self_attn.in_proj_weight, self_attn.out_proj.weight, layer_norm2.weight, .bias, ffn.ffn_1.weight, .bias,
+  // ffn.ffn_2.weight, .bias} for l < L, then layer_norm.{weight,bias}.  The stack must not move until the pool's commit().
+  void add_to(WeightPool& wp, ParamView& pv);
 };
 
 // Workspace of one stack call over R = B * T tokens, as float offsets from the caller's base.

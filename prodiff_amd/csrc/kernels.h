@@ -1,5 +1,7 @@
 // Small utility kernels shared by the WaveNet and FastDiff paths.
 #pragma once
+#include <functional>
+#include <memory>
 #include <tuple>
 #include <type_traits>
 #include <utility>
@@ -127,26 +129,55 @@ int convert_f32_bf16(const float* src, __bf16* dst, long long n, hipStream_t st)
 // copy of any weight pointer inside a mirrored pool (same element offset).
 const __bf16* lookup_bf16(const float* p);
 
+// The parameter list of a create call, taken in ABI order: every create walks it once with next().  A view over no
+// list (params null) only counts -- next() returns null -- which is how pd_rmvpe_num_params runs rmvpe's walk.
+struct ParamView {
+  const float* const* params = nullptr;
+  int n = 0, used = 0;
+  const float* next() { const int i = used++; return params && i < n ? params[i] : nullptr; }
+  // PD_ERR_ARG unless the walk took exactly n parameters
+  int done(const char* who) const;
+};
+
 // The packed weights of one native handle: a single fp32 device allocation cut into 64-float
-// aligned slots, and (PD_DTYPE_BF16) its bf16 mirror.  Plan with add(), then commit() allocates,
-// zeroes the pool on the stream (so the alignment padding reads 0) and points every slot into
-// it.  The destructor takes the mirror out of lookup_bf16's registry before it frees anything:
-// a handle that holds one by value needs no cleanup code of its own.
+// aligned slots, and (PD_DTYPE_BF16) its bf16 mirror.  A create states each weight once, in pool
+// order: add() reserves the slot and remembers the fill that packs it, then() remembers a step
+// that is no single slot's fill (a pack that writes several slots, or reads one packed earlier).
+// commit() allocates, zeroes the pool on the stream (so the alignment padding reads 0), points
+// every slot into it and runs the fills and steps in the order they were added, on that stream,
+// up to the first error.  Nothing touches the device before commit(); an uncommitted pool, or one
+// whose commit() failed, only drops its fills.  The destructor takes the mirror out of
+// lookup_bf16's registry before it frees anything: a handle that holds a pool by value needs no
+// cleanup code of its own.
 class WeightPool {
  public:
+  using Fill = std::function<int(float* dst)>;   // packs one slot; returns a PD_* code
+  using Step = std::function<int()>;
   WeightPool() = default;
   WeightPool(const WeightPool&) = delete;
   WeightPool& operator=(const WeightPool&) = delete;
   ~WeightPool();
-  // *slot must stay where it is until commit()
-  void add(float** slot, size_t n);
-  void add(const float** slot, size_t n) { add(const_cast<float**>(slot), n); }
+  // *slot must stay where it is until commit().  Without a fill the slot is written by another slot's fill or by a
+  // step (or stays zero).
+  void add(float** slot, size_t n, Fill fill = nullptr);
+  void add(const float** slot, size_t n, Fill fill = nullptr) { add(const_cast<float**>(slot), n, std::move(fill)); }
+  // slot of n floats = src[0 .. n)
+  void add_copy(float** slot, size_t n, const float* src);
+  void add_copy(const float** slot, size_t n, const float* src) { add_copy(const_cast<float**>(slot), n, src); }
+  // slot [Cout][taps * cpad] = pack_conv of Conv1d's src [Cout][Cin][taps], each tap's Cin padded to cpad
+  void add_conv(float** slot, const float* src, int Cout, int Cin, int taps, int cpad);
+  void add_conv(const float** slot, const float* src, int Cout, int Cin, int taps, int cpad) {
+    add_conv(const_cast<float**>(slot), src, Cout, Cin, taps, cpad);
+  }
+  void then(Step step);
   int commit(hipStream_t st, const char* what);
   // allocates the mirror, converts the pool as it is on the stream at this point, registers it
   int mirror_bf16(hipStream_t st);
   const __bf16* bf16() const { return bf_; }   // null without a mirror
  private:
-  std::vector<std::pair<float**, size_t>> plan_;
+  struct Item { float** slot; size_t n; Fill fill; };   // slot null: a step
+  std::vector<Item> plan_;
+  hipStream_t st_ = nullptr;   // commit()'s stream, for the fills of add_copy / add_conv
   float* pool_ = nullptr;
   __bf16* bf_ = nullptr;
   size_t n_ = 0;   // floats in the pool, padding included

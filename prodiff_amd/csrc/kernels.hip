@@ -457,20 +457,40 @@ const __bf16* lookup_bf16(const float* p) {
   return nullptr;
 }
 
-void WeightPool::add(float** slot, size_t n) { plan_.push_back({slot, n}); }
+void WeightPool::add(float** slot, size_t n, Fill fill) { plan_.push_back({slot, n, std::move(fill)}); }
+
+void WeightPool::add_copy(float** slot, size_t n, const float* src) {
+  add(slot, n, [this, n, src](float* dst) { return copy_f32(dst, src, n, st_); });
+}
+
+void WeightPool::add_conv(float** slot, const float* src, int Cout, int Cin, int taps, int cpad) {
+  add(slot, (size_t)Cout * taps * cpad, [=](float* dst) {
+    return pack_conv(dst, taps * cpad, 0, 0, cpad, src, Cout, Cin, taps, st_);
+  });
+}
+
+void WeightPool::then(Step step) {
+  plan_.push_back({nullptr, 0, [step = std::move(step)](float*) { return step(); }});
+}
 
 int WeightPool::commit(hipStream_t st, const char* what) {
   size_t off = 0;
-  for (auto& p : plan_) off += (p.second + 63) / 64 * 64;
+  for (auto& p : plan_) off += (p.n + 63) / 64 * 64;
   if (!dev_alloc((void**)&pool_, off * sizeof(float))) {
     set_error(std::string("hipMalloc failed for ") + what + " weights");
     return PD_ERR_HIP;
   }
   n_ = off;
+  st_ = st;
   off = 0;
-  for (auto& p : plan_) { *p.first = pool_ + off; off += (p.second + 63) / 64 * 64; }
-  plan_.clear();
+  for (auto& p : plan_) {
+    if (p.slot) *p.slot = pool_ + off;
+    off += (p.n + 63) / 64 * 64;
+  }
   PD_HIP(hipMemsetAsync(pool_, 0, n_ * sizeof(float), st));
+  for (auto& p : plan_)
+    if (p.fill) PD_TRY(p.fill(p.slot ? *p.slot : nullptr));
+  plan_.clear();
   return PD_OK;
 }
 
@@ -508,6 +528,13 @@ int check_params(const float* const* params, int n) {
   for (int i = 0; i < n; ++i)
     if (!params[i]) { set_error("argument: null parameter " + std::to_string(i)); return PD_ERR_ARG; }
   return PD_OK;
+}
+
+int ParamView::done(const char* who) const {
+  if (used == n) return PD_OK;
+  set_error(std::string(who) + ": the create walk took " + std::to_string(used) + " of " + std::to_string(n) +
+            " parameters");
+  return PD_ERR_ARG;
 }
 
 int copy_f32(float* dst, const float* src, size_t n, hipStream_t st) {

@@ -312,28 +312,29 @@ int mel_create(const pd_mel_dims* dims, const float* mel_basis, bool centered, v
     p.min_len = p.nf / 2 + 1;
   }
   hipStream_t st = (hipStream_t)stream;
-  pd_mel* h = new pd_mel();
+  std::unique_ptr<pd_mel> h(new pd_mel());
   h->d = *dims;
   h->p = p;
   h->centered = centered;
   WeightPool& wp = h->weights;
-  const size_t tab = (size_t)p.nrows * p.nbp;
+  const size_t tab = (size_t)p.nrows * p.nbp, nbt = (size_t)p.nbp * p.mp;
+  pd_mel* hp = h.get();
   wp.add(&h->tc, tab);
   wp.add(&h->ts, tab);
-  wp.add(&h->bt, (size_t)p.nbp * p.mp);
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "mel"));
-    hipLaunchKernelGGL(mel_table_kernel, dim3(cdiv((long long)tab, 256)), dim3(256), 0, st, h->tc, h->ts, p.nf, p.nrows,
+  wp.then([=]() {   // one kernel writes both tables
+    hipLaunchKernelGGL(mel_table_kernel, dim3(cdiv((long long)tab, 256)), dim3(256), 0, st, hp->tc, hp->ts, p.nf, p.nrows,
                        p.wn, p.woff, p.nb, p.nbp);
     PD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mel_basis_pack_kernel, dim3(cdiv((long long)p.nbp * p.mp, 256)), dim3(256), 0, st, mel_basis,
-                       h->bt, p.n_mels, p.size, p.nb, p.nbp, p.mp);
+    return PD_OK;
+  });
+  wp.add(&h->bt, nbt, [=](float* dst) {
+    hipLaunchKernelGGL(mel_basis_pack_kernel, dim3(cdiv((long long)nbt, 256)), dim3(256), 0, st, mel_basis, dst, p.n_mels,
+                       p.size, p.nb, p.nbp, p.mp);
     PD_LAUNCH_CHECK();
     return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  });
+  PD_TRY(wp.commit(st, "mel"));
+  *out = h.release();
   return PD_OK;
 }
 

@@ -2040,7 +2040,7 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
     PD_CHECK_ARG(co >= 256 ? co % 256 == 0 : 256 % co == 0, "stage channels must divide 256 or be a multiple of it");
   }
   hipStream_t st = (hipStream_t)stream;
-  nsf_model* m = new nsf_model();
+  std::unique_ptr<nsf_model> m(new nsf_model());
   m->d = d;
   m->dim = d.harmonic_num + 1;
   m->C0 = d.upsample_initial_channel;
@@ -2048,11 +2048,17 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
   for (int i = 0; i < d.num_upsamples; ++i) m->upp *= d.upsample_rates[i];
   m->convs_per_block = (d.resblock == 1 ? 2 : 1) * d.num_dilations;
 
-  // --- pool layout: slots in the order the pool holds them (the vectors are sized first, so
-  // the slot addresses stay put until commit)
+  // --- the pool: slots in the order it holds them, each with its fill (the vectors are sized first, so the slot
+  // addresses stay put until commit).  The parameter list gives the noise convs, conv_pre and the upsamplers as three
+  // groups; the pool keeps each stage's noise conv beside its upsampler, so those pointers are taken first.
   WeightPool& wp = m->weights;
-  const int dim = m->dim;
-  wp.add(&m->lin_w, dim); wp.add(&m->lin_b, 1);
+  ParamView pv{params, np};
+  wp.add_copy(&m->lin_w, m->dim, pv.next());
+  wp.add_copy(&m->lin_b, 1, pv.next());
+  const float *nc_w[6], *nc_b[6], *up_w[6], *up_b[6];
+  for (int i = 0; i < d.num_upsamples; ++i) { nc_w[i] = pv.next(); nc_b[i] = pv.next(); }
+  const float *pre_w = pv.next(), *pre_b = pv.next();
+  for (int i = 0; i < d.num_upsamples; ++i) { up_w[i] = pv.next(); up_b[i] = pv.next(); }
   m->ups.resize(d.num_upsamples);
   for (int i = 0; i < d.num_upsamples; ++i) {
     NsfUps& U = m->ups[i];
@@ -2069,24 +2075,38 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
     } else {
       U.nc_k = 1; U.nc_stride = 1; U.nc_pad = 0;
     }
-    wp.add(&U.nc_w, (size_t)U.cout * U.nc_k);
-    wp.add(&U.nc_b, U.cout);
+    const NsfUps* u = &U;   // its dims, for the fills
+    const float* ncw = nc_w[i];
+    wp.add(&U.nc_w, (size_t)u->cout * u->nc_k, [=](float* dst) {
+      hipLaunchKernelGGL(nsf_pack_noise_kernel, dim3(cdiv((long long)u->cout * u->nc_k, 256)), dim3(256), 0, st, dst, ncw,
+                         u->cout, u->nc_k);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+    wp.add_copy(&U.nc_b, u->cout, nc_b[i]);
     const int p = (U.k - U.u) / 2;
     U.w.resize(U.u);
     U.qmin.resize(U.u);
+    const float* upw = up_w[i];
     for (int phi = 0; phi < U.u; ++phi) {
-      wp.add(&U.w[phi], (size_t)U.cout * U.ntap * U.kpad);
+      wp.add(&U.w[phi], (size_t)u->cout * u->ntap * u->kpad, [=](float* dst) {
+        const long long n = (long long)u->cout * u->ntap * u->cin;
+        hipLaunchKernelGGL(nsf_pack_ups_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dst, upw, u->cin, u->cout, u->k, u->u,
+                           phi, u->ntap, u->kpad);
+        PD_LAUNCH_CHECK();
+        return PD_OK;
+      });
       const int num = p - phi;              // first q with q*u + phi - p >= 0
       U.qmin[phi] = num > 0 ? (num + U.u - 1) / U.u : 0;
     }
-    wp.add(&U.b, U.cout);
+    wp.add_copy(&U.b, u->cout, up_b[i]);
   }
-  auto conv_init = [&](NsfConv& c, int cin, int cout, int taps, int dil) {
+  auto conv_init = [&](NsfConv& c, int cin, int cout, int taps, int dil, const float* w, const float* b) {
     c.cin = cin; c.cout = cout; c.taps = taps; c.dil = dil; c.kpad = round_up(cin, GEMM_BK);
-    wp.add(&c.w, (size_t)cout * taps * c.kpad);
-    wp.add(&c.b, cout);
+    wp.add_conv(&c.w, w, cout, cin, taps, c.kpad);
+    wp.add_copy(&c.b, cout, b);
   };
-  conv_init(m->pre, d.num_mels, m->C0, 7, 1);
+  conv_init(m->pre, d.num_mels, m->C0, 7, 1, pre_w, pre_b);
   m->res.resize((size_t)d.num_upsamples * d.num_kernels * m->convs_per_block);
   size_t r = 0;
   for (int i = 0; i < d.num_upsamples; ++i) {
@@ -2096,54 +2116,18 @@ int nsf_create(const nsf_dims* dims, const float* const* params, int dtype, void
       for (int q = 0; q < m->convs_per_block; ++q) {
         // ResBlock1: convs1.{0..D-1} (dilated) then convs2.{0..D-1} (dilation 1); ResBlock2: convs.{0..D-1}
         int dil = (d.resblock == 1 && q >= d.num_dilations) ? 1 : d.resblock_dilation_sizes[j][q % d.num_dilations];
-        conv_init(m->res[r++], c, c, k, dil);
+        const float *w = pv.next(), *b = pv.next();
+        conv_init(m->res[r++], c, c, k, dil, w, b);
       }
     }
   }
-  conv_init(m->post, m->C0 >> d.num_upsamples, 1, 7, 1);
-
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "NSF-HiFiGAN"));
-    // the handle reads its weights through const pointers; packing is the one place that writes them
-    auto W = [](const float* q) { return const_cast<float*>(q); };
-    auto cp = [&](const float* dst, const float* src, size_t n) { return copy_f32(W(dst), src, n, st); };
-    int p = 0;
-    PD_TRY(cp(m->lin_w, params[p++], dim));
-    PD_TRY(cp(m->lin_b, params[p++], 1));
-    for (int i = 0; i < d.num_upsamples; ++i) {
-      NsfUps& U = m->ups[i];
-      hipLaunchKernelGGL(nsf_pack_noise_kernel, dim3(cdiv((long long)U.cout * U.nc_k, 256)), dim3(256), 0, st,
-                         W(U.nc_w), params[p++], U.cout, U.nc_k);
-      PD_LAUNCH_CHECK();
-      PD_TRY(cp(U.nc_b, params[p++], U.cout));
-    }
-    PD_TRY(pack_conv(W(m->pre.w), 7 * m->pre.kpad, 0, 0, m->pre.kpad, params[p++], m->C0, d.num_mels, 7, st));
-    PD_TRY(cp(m->pre.b, params[p++], m->C0));
-    for (int i = 0; i < d.num_upsamples; ++i) {
-      NsfUps& U = m->ups[i];
-      const float* w = params[p++];
-      for (int phi = 0; phi < U.u; ++phi) {
-        long long n = (long long)U.cout * U.ntap * U.cin;
-        hipLaunchKernelGGL(nsf_pack_ups_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, W(U.w[phi]), w, U.cin,
-                           U.cout, U.k, U.u, phi, U.ntap, U.kpad);
-        PD_LAUNCH_CHECK();
-      }
-      PD_TRY(cp(U.b, params[p++], U.cout));
-    }
-    for (NsfConv& c : m->res) {
-      PD_TRY(pack_conv(W(c.w), c.taps * c.kpad, 0, 0, c.kpad, params[p++], c.cout, c.cin, c.taps, st));
-      PD_TRY(cp(c.b, params[p++], c.cout));
-    }
-    PD_TRY(pack_conv(W(m->post.w), 7 * m->post.kpad, 0, 0, m->post.kpad, params[p++], 1, m->post.cin, 7, st));
-    PD_TRY(cp(m->post.b, params[p++], 1));
-    if (p != np) { set_error("nsf_create: parameter count mismatch"); return PD_ERR_ARG; }
-    // PD_DTYPE_BF16: every GEMM weight then streams as bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
-    if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
-    return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete m; return rc; }
-  *out = m;
+  const float *post_w = pv.next(), *post_b = pv.next();
+  conv_init(m->post, m->C0 >> d.num_upsamples, 1, 7, 1, post_w, post_b);
+  PD_TRY(pv.done("nsf_create"));
+  PD_TRY(wp.commit(st, "NSF-HiFiGAN"));
+  // PD_DTYPE_BF16: every GEMM weight then streams as bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
+  if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
+  *out = m.release();
   return PD_OK;
 }
 

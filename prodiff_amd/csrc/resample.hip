@@ -315,21 +315,18 @@ int pd_resample_create(const pd_resample_dims* dims, void* stream, pd_resample**
   double base;
   PD_TRY(make_plan(*dims, &p, &base));
   hipStream_t st = (hipStream_t)stream;
-  pd_resample* h = new pd_resample();
+  std::unique_ptr<pd_resample> h(new pd_resample());
   h->d = *dims;
   h->p = p;
   const size_t tab = (size_t)p.KP * p.NP;
-  h->weights.add(&h->tab, tab);
-  auto run = [&]() -> int {
-    PD_TRY(h->weights.commit(st, "resample"));
-    hipLaunchKernelGGL(resample_table_kernel, dim3(cdiv((long long)tab, 256)), dim3(256), 0, st, h->tab, p,
+  h->weights.add(&h->tab, tab, [=](float* dst) {
+    hipLaunchKernelGGL(resample_table_kernel, dim3(cdiv((long long)tab, 256)), dim3(256), 0, st, dst, p,
                        dims->lowpass_filter_width, base, dims->method, dims->beta);
     PD_LAUNCH_CHECK();
     return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  });
+  PD_TRY(h->weights.commit(st, "resample"));
+  *out = h.release();
   return PD_OK;
 }
 

@@ -488,28 +488,6 @@ bool dims_ok(const pd_rmvpe_dims& d) {
   return true;
 }
 
-int block_params(int cin, int cout) { return 10 + (cin != cout ? 2 : 0); }
-
-int count_params(const pd_rmvpe_dims& d) {
-  const int L = d.en_de_layers, c0 = d.en_out_channels;
-  int n = 4;
-  for (int i = 0; i < L; ++i) {
-    const int cin = i == 0 ? 1 : c0 << (i - 1), cout = c0 << i;
-    n += block_params(cin, cout) + (d.n_blocks - 1) * block_params(cout, cout);
-  }
-  for (int i = 0; i < d.inter_layers; ++i) {
-    const int cin = i == 0 ? c0 << (L - 1) : c0 << L, cout = c0 << L;
-    n += block_params(cin, cout) + (d.n_blocks - 1) * block_params(cout, cout);
-  }
-  for (int i = 0; i < L; ++i) {
-    const int cout = c0 << (L - 1 - i);
-    n += 5 + block_params(2 * cout, cout) + (d.n_blocks - 1) * block_params(cout, cout);
-  }
-  n += 2;                       // cnn
-  n += d.n_gru ? 8 + 2 : 2;     // fc
-  return n;
-}
-
 }  // namespace
 
 struct pd_rmvpe {
@@ -600,146 +578,136 @@ int run_block(const Block& bk, const float* x, int c0, const float* x1, int c1, 
   return PD_OK;
 }
 
+// The create walk over the architecture h->d describes: it takes the parameters in ABI order and adds every pool
+// slot with its fill.  pd_rmvpe_num_params runs it with a counting view on a handle it never commits.
+void add_weights(pd_rmvpe* h, ParamView& pv, hipStream_t st) {
+  const pd_rmvpe_dims& d = h->d;
+  WeightPool& wp = h->weights;
+  const int L = d.en_de_layers, c0 = d.en_out_channels;
+  struct Bn { const float *g, *beta, *mean, *var; };   // weight, bias, running_mean, running_var
+  auto next_bn = [&]() { return Bn{pv.next(), pv.next(), pv.next(), pv.next()}; };
+  auto add_bn_bias = [&](float** slot, size_t n, Bn bn, int cout) {
+    wp.add(slot, n, [=](float* dst) { return fold_bn_bias(dst, bn.g, bn.beta, bn.mean, bn.var, cout, st); });
+  };
+  {
+    const Bn bn = next_bn();   // encoder.bn -> {scale, shift}
+    wp.add(&h->inbn, 2, [=](float* dst) {
+      hipLaunchKernelGGL(input_bn_kernel, dim3(1), dim3(64), 0, st, dst, bn.g, bn.beta, bn.mean, bn.var);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+  }
+  // a 3x3 conv (or a decoder's transposed one) and the BatchNorm behind it, folded in
+  auto add_convw = [&](ConvW& cw, int cin, int cout, bool transposed) {
+    cw.cin = cin; cw.cout = cout;
+    const float* w = pv.next();
+    const Bn bn = next_bn();
+    wp.add(&cw.w, packed_conv(cin, 0, cout, 9), [=](float* dst) {
+      return pack_conv_tiles(dst, w, bn.g, bn.var, cout, cin, 0, 9, transposed ? TAPS_FLIPPED_T : TAPS_STORED, st);
+    });
+    add_bn_bias(&cw.b, (size_t)ctiles(cout) * 32, bn, cout);
+  };
+  auto add_block = [&](Block& bk, int cin, int cout) {
+    bk.cin = cin; bk.cout = cout; bk.sc = cin != cout;
+    const bool first = cin == 1;   // the first conv [c0][1][3][3] and its shortcut keep the plain layout
+    if (first) {
+      bk.c1.cin = 1; bk.c1.cout = cout;
+      const float* w = pv.next();
+      const Bn bn = next_bn();
+      wp.add(&h->w_in, (size_t)cout * 9, [=](float* dst) {
+        hipLaunchKernelGGL(fold_rows_kernel, dim3(cdiv(cout * 9, 256)), dim3(256), 0, st, dst, w, bn.g, bn.var, cout, 9);
+        PD_LAUNCH_CHECK();
+        return PD_OK;
+      });
+      add_bn_bias(&h->b_in, cout, bn, cout);
+    } else {
+      add_convw(bk.c1, cin, cout, false);
+    }
+    add_convw(bk.c2, cout, cout, false);
+    if (!bk.sc) return;
+    const float *w = pv.next(), *b = pv.next();   // the 1x1 shortcut
+    if (first) {
+      wp.add_copy(&h->ws_in, cout, w);
+      wp.add_copy(&h->bs_in, cout, b);
+    } else {
+      wp.add(&bk.ws, packed_conv(cin, 0, cout, 1), [=](float* dst) {
+        return pack_conv_tiles(dst, w, nullptr, nullptr, cout, cin, 0, 1, TAPS_STORED, st);
+      });
+      wp.add(&bk.bs, (size_t)ctiles(cout) * 32, [=](float* dst) { return copy_f32(dst, b, cout, st); });
+    }
+  };
+  auto add_stage = [&](std::vector<Block>& v, int cin, int cout) {
+    v.resize(d.n_blocks);   // sized before any slot address is taken
+    for (int j = 0; j < d.n_blocks; ++j) add_block(v[j], j == 0 ? cin : cout, cout);
+  };
+  h->enc.resize(L); h->inter.resize(d.inter_layers); h->dec.resize(L); h->up.resize(L);
+  for (int i = 0; i < L; ++i) add_stage(h->enc[i], i == 0 ? 1 : c0 << (i - 1), c0 << i);
+  for (int i = 0; i < d.inter_layers; ++i) add_stage(h->inter[i], i == 0 ? c0 << (L - 1) : c0 << L, c0 << L);
+  for (int i = 0; i < L; ++i) {
+    const int cout = c0 << (L - 1 - i);
+    add_convw(h->up[i], 2 * cout, cout, true);
+    add_stage(h->dec[i], 2 * cout, cout);
+  }
+  wp.add_copy(&h->w_cnn, (size_t)3 * c0 * 9, pv.next());
+  wp.add_copy(&h->b_cnn, 3, pv.next());
+  const int feat_c = 3 * d.n_mels;
+  if (d.n_gru) {
+    // the parameters come per direction {weight_ih, weight_hh, bias_ih, bias_hh}; each slot holds both directions
+    const float* g[2][4];
+    for (int dir = 0; dir < 2; ++dir)
+      for (int k = 0; k < 4; ++k) g[dir][k] = pv.next();
+    auto add_dirs = [&](float** slot, size_t per, int k) {
+      wp.add(slot, 2 * per, [=](float* dst) {
+        for (int dir = 0; dir < 2; ++dir) PD_TRY(copy_f32(dst + dir * per, g[dir][k], per, st));
+        return PD_OK;
+      });
+    };
+    add_dirs(&h->w_ih, (size_t)3 * GRU_H * feat_c, 0);
+    add_dirs(&h->b_ih, 3 * GRU_H, 2);
+    const size_t whh = (size_t)3 * GRU_H * GRU_H;
+    wp.add(&h->w_hh, 2 * whh, [=](float* dst) {
+      for (int dir = 0; dir < 2; ++dir) {
+        hipLaunchKernelGGL(pack_whh_kernel, dim3(cdiv(whh, 256)), dim3(256), 0, st, dst + dir * whh, g[dir][1]);
+        PD_LAUNCH_CHECK();
+      }
+      return PD_OK;
+    });
+    add_dirs(&h->b_hh, 3 * GRU_H, 3);
+    h->fc_in = 2 * GRU_H;
+  } else {
+    h->fc_in = feat_c;
+  }
+  wp.add_copy(&h->w_fc, (size_t)d.n_class * h->fc_in, pv.next());
+  wp.add_copy(&h->b_fc, d.n_class, pv.next());
+}
+
 }  // namespace
 
 extern "C" {
 
 int pd_rmvpe_num_params(const pd_rmvpe_dims* dims) {
   if (!dims || !dims_ok(*dims)) return 0;
-  return count_params(*dims);
+  pd_rmvpe h;
+  h.d = *dims;
+  ParamView count;
+  add_weights(&h, count, nullptr);
+  return count.used;
 }
 
 int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int dtype, void* stream, pd_rmvpe** out) {
   PD_CHECK_ARG(dims && params && out, "null pointer");
   if (dtype != PD_DTYPE_F32) { set_error("rmvpe: fp32 only"); return PD_ERR_UNSUPPORTED; }
   if (!dims_ok(*dims)) { set_error("rmvpe: dimensions outside the supported set (include/prodiff_hip.h)"); return PD_ERR_UNSUPPORTED; }
-  const pd_rmvpe_dims d = *dims;
-  const int np = count_params(d);
+  const int np = pd_rmvpe_num_params(dims);
   PD_TRY(check_params(params, np));
   hipStream_t st = (hipStream_t)stream;
-  pd_rmvpe* h = new pd_rmvpe();
-  h->d = d;
-  WeightPool& wp = h->weights;
-  const int L = d.en_de_layers, c0 = d.en_out_channels;
-
-  // plan: walk the parameter list once, reserving pool slots and remembering what to pack from where
-  struct ConvJob { ConvW* cw; int w, bn; bool transposed; };       // weight index, first BN index
-  struct ScJob { Block* bk; int w; };
-  std::vector<ConvJob> convs;
-  std::vector<ScJob> scs;
-  int p = 0;
-  const int p_inbn = p; p += 4;
-  wp.add(&h->inbn, 2);
-  int p_first = -1;
-  auto plan_convw = [&](ConvW& cw, int cin, int cout, bool transposed) {
-    cw.cin = cin; cw.cout = cout;
-    wp.add(&cw.w, packed_conv(cin, 0, cout, 9));
-    wp.add(&cw.b, (size_t)ctiles(cout) * 32);
-    convs.push_back({&cw, p, p + 1, transposed});
-    p += 5;
-  };
-  auto plan_block = [&](Block& bk, int cin, int cout) {
-    bk.cin = cin; bk.cout = cout; bk.sc = cin != cout;
-    if (cin == 1) {           // the first conv and its shortcut keep the plain layout
-      p_first = p;
-      bk.c1.cin = 1; bk.c1.cout = cout;
-      wp.add(&h->w_in, (size_t)cout * 9);
-      wp.add(&h->b_in, cout);
-      p += 5;
-    } else {
-      plan_convw(bk.c1, cin, cout, false);
-    }
-    plan_convw(bk.c2, cout, cout, false);
-    if (bk.sc) {
-      if (cin == 1) {
-        wp.add(&h->ws_in, cout);
-        wp.add(&h->bs_in, cout);
-      } else {
-        wp.add(&bk.ws, packed_conv(cin, 0, cout, 1));
-        wp.add(&bk.bs, (size_t)ctiles(cout) * 32);
-        scs.push_back({&bk, p});
-      }
-      p += 2;
-    }
-  };
-  auto plan_stage = [&](std::vector<Block>& v, int cin, int cout) {
-    v.resize(d.n_blocks);   // sized before any slot address is taken
-    for (int j = 0; j < d.n_blocks; ++j) plan_block(v[j], j == 0 ? cin : cout, cout);
-  };
-  h->enc.resize(L); h->inter.resize(d.inter_layers); h->dec.resize(L); h->up.resize(L);
-  for (int i = 0; i < L; ++i) plan_stage(h->enc[i], i == 0 ? 1 : c0 << (i - 1), c0 << i);
-  for (int i = 0; i < d.inter_layers; ++i) plan_stage(h->inter[i], i == 0 ? c0 << (L - 1) : c0 << L, c0 << L);
-  for (int i = 0; i < L; ++i) {
-    const int cout = c0 << (L - 1 - i);
-    plan_convw(h->up[i], 2 * cout, cout, true);
-    plan_stage(h->dec[i], 2 * cout, cout);
-  }
-  const int p_cnn = p; p += 2;
-  wp.add(&h->w_cnn, (size_t)3 * c0 * 9);
-  wp.add(&h->b_cnn, 3);
-  const int feat_c = 3 * d.n_mels;
-  const int p_fc0 = p;
-  if (d.n_gru) {
-    wp.add(&h->w_ih, (size_t)6 * GRU_H * feat_c);
-    wp.add(&h->b_ih, 6 * GRU_H);
-    wp.add(&h->w_hh, (size_t)6 * GRU_H * GRU_H);
-    wp.add(&h->b_hh, 6 * GRU_H);
-    p += 8;
-    h->fc_in = 2 * GRU_H;
-  } else {
-    h->fc_in = feat_c;
-  }
-  const int p_fc = p; p += 2;
-  wp.add(&h->w_fc, (size_t)d.n_class * h->fc_in);
-  wp.add(&h->b_fc, d.n_class);
-
-  auto run = [&]() -> int {
-    if (p != np) { set_error("rmvpe: parameter walk does not match pd_rmvpe_num_params"); return PD_ERR_ARG; }
-    PD_TRY(wp.commit(st, "rmvpe"));
-    hipLaunchKernelGGL(input_bn_kernel, dim3(1), dim3(64), 0, st, h->inbn, params[p_inbn], params[p_inbn + 1],
-                       params[p_inbn + 2], params[p_inbn + 3]);
-    PD_LAUNCH_CHECK();
-    {   // first conv: conv.0.weight [c0][1][3][3], conv.1 BN; shortcut after the block's second conv
-      const int q = p_first;
-      hipLaunchKernelGGL(fold_rows_kernel, dim3(cdiv(c0 * 9, 256)), dim3(256), 0, st, h->w_in, params[q],
-                         params[q + 1], params[q + 4], c0, 9);
-      PD_LAUNCH_CHECK();
-      PD_TRY(fold_bn_bias(h->b_in, params[q + 1], params[q + 2], params[q + 3], params[q + 4], c0, st));
-      PD_TRY(copy_f32(h->ws_in, params[q + 10], c0, st));
-      PD_TRY(copy_f32(h->bs_in, params[q + 11], c0, st));
-    }
-    for (const ConvJob& j : convs) {
-      const ConvW& cw = *j.cw;
-      const float* const* bn = params + j.bn;   // weight, bias, running_mean, running_var
-      PD_TRY(pack_conv_tiles(cw.w, params[j.w], bn[0], bn[3], cw.cout, cw.cin, 0, 9,
-                             j.transposed ? TAPS_FLIPPED_T : TAPS_STORED, st));
-      PD_TRY(fold_bn_bias(cw.b, bn[0], bn[1], bn[2], bn[3], cw.cout, st));
-    }
-    for (const ScJob& j : scs) {
-      const Block& bk = *j.bk;
-      PD_TRY(pack_conv_tiles(bk.ws, params[j.w], nullptr, nullptr, bk.cout, bk.cin, 0, 1, TAPS_STORED, st));
-      PD_TRY(copy_f32(bk.bs, params[j.w + 1], bk.cout, st));
-    }
-    PD_TRY(copy_f32(h->w_cnn, params[p_cnn], (size_t)3 * c0 * 9, st));
-    PD_TRY(copy_f32(h->b_cnn, params[p_cnn + 1], 3, st));
-    if (d.n_gru) {
-      for (int dir = 0; dir < 2; ++dir) {
-        const float* const* g = params + p_fc0 + 4 * dir;   // weight_ih, weight_hh, bias_ih, bias_hh
-        PD_TRY(copy_f32(h->w_ih + (size_t)dir * 3 * GRU_H * feat_c, g[0], (size_t)3 * GRU_H * feat_c, st));
-        hipLaunchKernelGGL(pack_whh_kernel, dim3(cdiv(3 * GRU_H * GRU_H, 256)), dim3(256), 0, st,
-                           h->w_hh + (size_t)dir * 3 * GRU_H * GRU_H, g[1]);
-        PD_LAUNCH_CHECK();
-        PD_TRY(copy_f32(h->b_ih + dir * 3 * GRU_H, g[2], 3 * GRU_H, st));
-        PD_TRY(copy_f32(h->b_hh + dir * 3 * GRU_H, g[3], 3 * GRU_H, st));
-      }
-    }
-    PD_TRY(copy_f32(h->w_fc, params[p_fc], (size_t)d.n_class * h->fc_in, st));
-    PD_TRY(copy_f32(h->b_fc, params[p_fc + 1], d.n_class, st));
-    return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  std::unique_ptr<pd_rmvpe> h(new pd_rmvpe());
+  h->d = *dims;
+  ParamView pv{params, np};
+  add_weights(h.get(), pv, st);
+  PD_TRY(pv.done("pd_rmvpe"));
+  PD_TRY(h->weights.commit(st, "rmvpe"));
+  *out = h.release();
   return PD_OK;
 }
 

@@ -219,47 +219,33 @@ int pd_pitch_cond_create(const pd_pitch_cond_dims* dims, const float* const* par
   PD_CHECK_ARG(params, "null pointer");
   PD_TRY(check_params(params, pd_pitch_cond_num_params(dims)));
   hipStream_t st = (hipStream_t)stream;
-  pd_pitch_cond* h = new pd_pitch_cond();
+  std::unique_ptr<pd_pitch_cond> h(new pd_pitch_cond());
   h->d = d;
   h->enc.init(d.hidden_size, d.enc_layers, d.enc_ffn_kernel_size, d.num_heads, "pd_pitch_cond");   // checked above
   h->note.init(d.note_hidden_size, d.note_layers, d.note_ffn_kernel_size, d.note_heads, "pd_pitch_cond");
   const int H = h->enc.H, Hn = h->note.H;
   const size_t V = (size_t)d.vocab_size + 1;
   WeightPool& wp = h->weights;
-  h->enc.plan(wp);
-  wp.add(&h->emb, V * H);
-  wp.add(&h->dur_w, H); wp.add(&h->dur_b, H);
-  h->note.plan(wp);
-  wp.add(&h->mw, Hn); wp.add(&h->mb, Hn); wp.add(&h->ndw, Hn); wp.add(&h->ndb, Hn);
-  wp.add(&h->Wol, (size_t)H * Hn); wp.add(&h->bol, H);
-  if (d.use_spk_id) wp.add(&h->spk, (size_t)d.num_spk * H);
-  wp.add(&h->dpw, H); wp.add(&h->dpb, H);
-  wp.add(&h->E, (size_t)2 * H);
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "pitch-condition"));
-    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
-    int p = 0;
-    PD_TRY(h->enc.pack(params, p, st));
-    PD_TRY(cp(h->emb, params[p++], V * H));
-    PD_TRY(cp(h->dur_w, params[p++], H));
-    PD_TRY(cp(h->dur_b, params[p++], H));
-    PD_TRY(h->note.pack(params, p, st));
-    PD_TRY(cp(h->mw, params[p++], Hn));
-    PD_TRY(cp(h->mb, params[p++], Hn));
-    PD_TRY(cp(h->ndw, params[p++], Hn));
-    PD_TRY(cp(h->ndb, params[p++], Hn));
-    PD_TRY(cp(h->Wol, params[p++], (size_t)H * Hn));   // [H, Hn] = W[n][k]
-    PD_TRY(cp(h->bol, params[p++], H));
-    if (d.use_spk_id) PD_TRY(cp(h->spk, params[p++], (size_t)d.num_spk * H));
-    PD_TRY(cp(h->dpw, params[p++], H));
-    PD_TRY(cp(h->dpb, params[p++], H));
-    PD_TRY(cp(h->E, params[p++], (size_t)2 * H));
-    if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
-    return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  ParamView pv{params, pd_pitch_cond_num_params(dims)};
+  h->enc.add_to(wp, pv);
+  wp.add_copy(&h->emb, V * H, pv.next());
+  wp.add_copy(&h->dur_w, H, pv.next());
+  wp.add_copy(&h->dur_b, H, pv.next());
+  h->note.add_to(wp, pv);
+  wp.add_copy(&h->mw, Hn, pv.next());
+  wp.add_copy(&h->mb, Hn, pv.next());
+  wp.add_copy(&h->ndw, Hn, pv.next());
+  wp.add_copy(&h->ndb, Hn, pv.next());
+  wp.add_copy(&h->Wol, (size_t)H * Hn, pv.next());   // [H, Hn] = W[n][k]
+  wp.add_copy(&h->bol, H, pv.next());
+  if (d.use_spk_id) wp.add_copy(&h->spk, (size_t)d.num_spk * H, pv.next());
+  wp.add_copy(&h->dpw, H, pv.next());
+  wp.add_copy(&h->dpb, H, pv.next());
+  wp.add_copy(&h->E, (size_t)2 * H, pv.next());
+  PD_TRY(pv.done("pd_pitch_cond"));
+  PD_TRY(wp.commit(st, "pitch-condition"));
+  if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
+  *out = h.release();
   return PD_OK;
 }
 
@@ -380,46 +366,31 @@ int pd_dur_create(const pd_dur_dims* dims, const float* const* params, int dtype
   PD_CHECK_ARG(params, "null pointer");
   PD_TRY(check_params(params, pd_dur_num_params(dims)));
   hipStream_t st = (hipStream_t)stream;
-  pd_dur* h = new pd_dur();
+  std::unique_ptr<pd_dur> h(new pd_dur());
   h->d = d;
   h->enc.init(d.hidden_size, d.enc_layers, d.enc_ffn_kernel_size, d.num_heads, "pd_dur");   // checked above
   const int H = h->enc.H, C = d.n_chans, k = d.kernel_size, NL = d.n_layers;
   WeightPool& wp = h->weights;
-  h->enc.plan(wp);
-  wp.add(&h->emb, (size_t)d.vocab_size * H);
-  wp.add(&h->onset, (size_t)2 * H);
-  wp.add(&h->wdw, H); wp.add(&h->wdb, H);
+  ParamView pv{params, pd_dur_num_params(dims)};
+  h->enc.add_to(wp, pv);
+  wp.add_copy(&h->emb, (size_t)d.vocab_size * H, pv.next());
+  wp.add_copy(&h->onset, (size_t)2 * H, pv.next());
+  wp.add_copy(&h->wdw, H, pv.next());
+  wp.add_copy(&h->wdb, H, pv.next());
   h->Wc.resize(NL); h->bc.resize(NL); h->lng.resize(NL); h->lnb.resize(NL);
   for (int l = 0; l < NL; ++l) {
     const int Cin = l ? C : H;
-    wp.add(&h->Wc[l], (size_t)C * k * Cin); wp.add(&h->bc[l], C);
-    wp.add(&h->lng[l], C); wp.add(&h->lnb[l], C);
+    wp.add_conv(&h->Wc[l], pv.next(), C, Cin, k, Cin);   // conv.l.1 [C, Cin, k]
+    wp.add_copy(&h->bc[l], C, pv.next());
+    wp.add_copy(&h->lng[l], C, pv.next());
+    wp.add_copy(&h->lnb[l], C, pv.next());
   }
-  wp.add(&h->lw, C); wp.add(&h->lb, 1);
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "duration-predictor"));
-    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
-    int p = 0;
-    PD_TRY(h->enc.pack(params, p, st));
-    PD_TRY(cp(h->emb, params[p++], (size_t)d.vocab_size * H));
-    PD_TRY(cp(h->onset, params[p++], (size_t)2 * H));
-    PD_TRY(cp(h->wdw, params[p++], H));
-    PD_TRY(cp(h->wdb, params[p++], H));
-    for (int l = 0; l < NL; ++l) {
-      const int Cin = l ? C : H;
-      PD_TRY(pack_conv(h->Wc[l], k * Cin, 0, 0, Cin, params[p++], C, Cin, k, st));   // conv.l.1 [C, Cin, k]
-      PD_TRY(cp(h->bc[l], params[p++], C));
-      PD_TRY(cp(h->lng[l], params[p++], C));
-      PD_TRY(cp(h->lnb[l], params[p++], C));
-    }
-    PD_TRY(cp(h->lw, params[p++], C));
-    PD_TRY(cp(h->lb, params[p++], 1));
-    if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
-    return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  wp.add_copy(&h->lw, C, pv.next());
+  wp.add_copy(&h->lb, 1, pv.next());
+  PD_TRY(pv.done("pd_dur"));
+  PD_TRY(wp.commit(st, "duration-predictor"));
+  if (dtype == PD_DTYPE_BF16) PD_TRY(wp.mirror_bf16(st));
+  *out = h.release();
   return PD_OK;
 }
 

@@ -827,7 +827,7 @@ int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, 
   const pd_vr_dims d = *dims;
   PD_TRY(check_params(params, CASCADE_PARAMS));
   hipStream_t st = (hipStream_t)stream;
-  pd_vr* h = new pd_vr();
+  std::unique_ptr<pd_vr> h(new pd_vr());
   h->d = d;
   h->C = d.is_mono ? 1 : 2;
   h->nin = 2 * h->C;
@@ -837,101 +837,104 @@ int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, 
   h->nbk = round_up(h->nb, 16);
   h->cx = round_up(h->nin + 3 * d.nout / 4, 4);   // X's pixel stride: whole 16-byte rows, so the vector loads apply
   WeightPool& wp = h->weights;
+  ParamView pv{params, CASCADE_PARAMS};
 
-  struct ConvJob { Conv* cw; int w; bool bn; };
-  struct LstmJob { Net* nt; int p; int bins; };
-  std::vector<ConvJob> convs;
-  std::vector<LstmJob> lstms;
-  int p = 0;
-  auto plan_conv = [&](Conv& cw, int c0, int c1, int cout, int taps, bool bn) {
+  // a conv and (bn) the BatchNorm behind it, folded in; without one the bias slot stays zero
+  auto add_conv = [&](Conv& cw, int c0, int c1, int cout, int taps, bool bn) {
     cw.c0 = c0; cw.c1 = c1; cw.cout = cout; cw.taps = taps;
-    wp.add(&cw.w, packed_conv(c0, c1, cout, taps));
-    wp.add(&cw.b, (size_t)ctiles(cout) * 32);
-    convs.push_back({&cw, p, bn});
-    p += bn ? 5 : 1;
+    const float* w = pv.next();
+    const float *g = nullptr, *beta = nullptr, *mean = nullptr, *var = nullptr;   // weight, bias, running_mean, running_var
+    if (bn) { g = pv.next(); beta = pv.next(); mean = pv.next(); var = pv.next(); }
+    wp.add(&cw.w, packed_conv(c0, c1, cout, taps), [=](float* dst) {
+      return pack_conv_tiles(dst, w, g, var, cout, c0, c1, taps, TAPS_SWAPPED, st);
+    });
+    const size_t nb = (size_t)ctiles(cout) * 32;
+    if (bn) wp.add(&cw.b, nb, [=](float* dst) { return fold_bn_bias(dst, g, beta, mean, var, cout, st); });
+    else wp.add(&cw.b, nb);
   };
-  auto plan_net = [&](Net& nt, int cin, int n, int bins, int nout_lstm, int tail_out) {
+  auto add_net = [&](Net& nt, int cin, int n, int bins, int nout_lstm, int tail_out) {
     nt.cin = cin; nt.n = n; nt.hid = nout_lstm / 2;
-    plan_conv(nt.enc1, cin, 0, n, 9, true);
+    add_conv(nt.enc1, cin, 0, n, 9, true);
     const int wd[5] = {n, 2 * n, 4 * n, 6 * n, 8 * n};
     for (int l = 1; l < 5; ++l) {
-      plan_conv(nt.enc[l - 1][0], wd[l - 1], 0, wd[l], 9, true);
-      plan_conv(nt.enc[l - 1][1], wd[l], 0, wd[l], 9, true);
+      add_conv(nt.enc[l - 1][0], wd[l - 1], 0, wd[l], 9, true);
+      add_conv(nt.enc[l - 1][1], wd[l], 0, wd[l], 9, true);
     }
-    plan_conv(nt.aspp[0], 8 * n, 0, 8 * n, 1, true);
-    plan_conv(nt.aspp[1], 8 * n, 0, 8 * n, 1, true);
-    for (int i = 2; i < 5; ++i) plan_conv(nt.aspp[i], 8 * n, 0, 8 * n, 9, true);
-    plan_conv(nt.bott, 40 * n, 0, 8 * n, 1, true);
-    plan_conv(nt.dec[0], 8 * n, 6 * n, 6 * n, 9, true);
-    plan_conv(nt.dec[1], 6 * n, 4 * n, 4 * n, 9, true);
-    plan_conv(nt.dec[2], 4 * n, 2 * n, 2 * n, 9, true);
-    plan_conv(nt.lconv, 2 * n, 0, 1, 1, true);
-    const int Hh = nt.hid;
-    wp.add(&nt.wih, (size_t)bins * 8 * Hh);
-    wp.add(&nt.bl, 8 * Hh);
-    wp.add(&nt.whh, (size_t)8 * Hh * Hh);
-    wp.add(&nt.wd, (size_t)2 * Hh * bins);
-    wp.add(&nt.bd, bins);
-    lstms.push_back({&nt, p, bins});
-    p += 8 + 6;
-    plan_conv(nt.dec1, 2 * n + 1, n, n, 9, true);
+    add_conv(nt.aspp[0], 8 * n, 0, 8 * n, 1, true);
+    add_conv(nt.aspp[1], 8 * n, 0, 8 * n, 1, true);
+    for (int i = 2; i < 5; ++i) add_conv(nt.aspp[i], 8 * n, 0, 8 * n, 9, true);
+    add_conv(nt.bott, 40 * n, 0, 8 * n, 1, true);
+    add_conv(nt.dec[0], 8 * n, 6 * n, 6 * n, 9, true);
+    add_conv(nt.dec[1], 6 * n, 4 * n, 4 * n, 9, true);
+    add_conv(nt.dec[2], 4 * n, 2 * n, 2 * n, 9, true);
+    add_conv(nt.lconv, 2 * n, 0, 1, 1, true);
+    // the LSTM: per direction {weight_ih, weight_hh, bias_ih, bias_hh}, each slot holding both directions, then
+    // dense.0.{weight, bias} and dense.1 BatchNorm1d {weight, bias, running_mean, running_var}
+    const int Hh = nt.hid, G = 4 * Hh;
+    const float *g[2][4], *dn[6];
+    for (int dir = 0; dir < 2; ++dir)
+      for (int k = 0; k < 4; ++k) g[dir][k] = pv.next();
+    for (int k = 0; k < 6; ++k) dn[k] = pv.next();
+    wp.add(&nt.wih, (size_t)bins * 2 * G, [=](float* dst) {
+      for (int dir = 0; dir < 2; ++dir) {
+        hipLaunchKernelGGL(vr_pack_linear_kernel, dim3(cdiv((long long)G * bins, 256)), dim3(256), 0, st, dst, g[dir][0],
+                           (const float*)nullptr, (const float*)nullptr, G, bins, 2 * G, dir * G);
+        PD_LAUNCH_CHECK();
+      }
+      return PD_OK;
+    });
+    wp.add(&nt.bl, (size_t)2 * G, [=](float* dst) {
+      for (int dir = 0; dir < 2; ++dir) PD_TRY(add_vectors(dst + dir * G, g[dir][2], g[dir][3], G, st));
+      return PD_OK;
+    });
+    const size_t whh = (size_t)G * Hh;
+    wp.add(&nt.whh, 2 * whh, [=](float* dst) {
+      for (int dir = 0; dir < 2; ++dir) PD_TRY(copy_f32(dst + dir * whh, g[dir][1], whh, st));
+      return PD_OK;
+    });
+    wp.add(&nt.wd, (size_t)2 * Hh * bins, [=](float* dst) {
+      hipLaunchKernelGGL(vr_pack_linear_kernel, dim3(cdiv((long long)bins * 2 * Hh, 256)), dim3(256), 0, st, dst, dn[0],
+                         dn[2], dn[5], bins, 2 * Hh, bins, 0);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+    wp.add(&nt.bd, bins, [=](float* dst) {
+      hipLaunchKernelGGL(vr_dense_bias_kernel, dim3(cdiv(bins, 256)), dim3(256), 0, st, dst, dn[1], dn[2], dn[3], dn[4],
+                         dn[5], bins);
+      PD_LAUNCH_CHECK();
+      return PD_OK;
+    });
+    add_conv(nt.dec1, 2 * n + 1, n, n, 9, true);
     nt.has_tail = tail_out > 0;
-    if (tail_out > 0) plan_conv(nt.tail, n, 0, tail_out, 1, true);
+    if (tail_out > 0) add_conv(nt.tail, n, 0, tail_out, 1, true);
   };
   const int nin = h->nin, no = d.nout, q = no / 4, lb = h->F / 4;   // lb: LSTM input bins of a band net
-  plan_net(h->nets[0], nin, no / 2, lb, d.nout_lstm, q);
-  plan_net(h->nets[1], nin, q, lb, d.nout_lstm / 2, 0);
-  plan_net(h->nets[2], nin + q, no, lb, d.nout_lstm, no / 2);
-  plan_net(h->nets[3], nin + q, no / 2, lb, d.nout_lstm / 2, 0);
-  plan_net(h->nets[4], nin + 3 * q, no, 2 * lb, d.nout_lstm, 0);
-  plan_conv(h->out, no, 0, nin, 1, false);
-  p += 1;   // aux_out.weight: training only
-  const int p_window = p++;
+  add_net(h->nets[0], nin, no / 2, lb, d.nout_lstm, q);
+  add_net(h->nets[1], nin, q, lb, d.nout_lstm / 2, 0);
+  add_net(h->nets[2], nin + q, no, lb, d.nout_lstm, no / 2);
+  add_net(h->nets[3], nin + q, no / 2, lb, d.nout_lstm / 2, 0);
+  add_net(h->nets[4], nin + 3 * q, no, 2 * lb, d.nout_lstm, 0);
+  add_conv(h->out, no, 0, nin, 1, false);
+  pv.next();   // aux_out.weight: training only
+  // one kernel writes the four DFT tables and the window
+  const float* window = pv.next();
   const size_t ftab = (size_t)d.n_fft * h->nbp, itab = (size_t)h->nbk * d.n_fft;
   wp.add(&h->fc, ftab);
   wp.add(&h->fs, ftab);
   wp.add(&h->ic, itab);
   wp.add(&h->is, itab);
   wp.add(&h->win, d.n_fft);
-
-  auto run = [&]() -> int {
-    if (p != CASCADE_PARAMS) { set_error("vr: parameter walk does not match pd_vr_num_params"); return PD_ERR_ARG; }
-    PD_TRY(wp.commit(st, "vr"));
-    for (const ConvJob& j : convs) {
-      const Conv& cw = *j.cw;
-      const float* const* bn = params + j.w + 1;   // weight, bias, running_mean, running_var
-      PD_TRY(pack_conv_tiles(cw.w, params[j.w], j.bn ? bn[0] : nullptr, j.bn ? bn[3] : nullptr, cw.cout, cw.c0, cw.c1,
-                             cw.taps, TAPS_SWAPPED, st));
-      if (j.bn) PD_TRY(fold_bn_bias(cw.b, bn[0], bn[1], bn[2], bn[3], cw.cout, st));
-    }
-    for (const LstmJob& j : lstms) {
-      const Net& nt = *j.nt;
-      const int Hh = nt.hid, G = 4 * Hh, bins = j.bins;
-      for (int dir = 0; dir < 2; ++dir) {
-        const float* const* g = params + j.p + 4 * dir;   // weight_ih, weight_hh, bias_ih, bias_hh
-        hipLaunchKernelGGL(vr_pack_linear_kernel, dim3(cdiv((long long)G * bins, 256)), dim3(256), 0, st, nt.wih, g[0],
-                           (const float*)nullptr, (const float*)nullptr, G, bins, 2 * G, dir * G);
-        PD_LAUNCH_CHECK();
-        PD_TRY(copy_f32(nt.whh + (size_t)dir * G * Hh, g[1], (size_t)G * Hh, st));
-        PD_TRY(add_vectors(nt.bl + dir * G, g[2], g[3], G, st));
-      }
-      const float* const* dn = params + j.p + 8;   // dense.0.{weight,bias}, dense.1 BatchNorm1d
-      hipLaunchKernelGGL(vr_pack_linear_kernel, dim3(cdiv((long long)bins * 2 * Hh, 256)), dim3(256), 0, st, nt.wd, dn[0],
-                         dn[2], dn[5], bins, 2 * Hh, bins, 0);
-      PD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(vr_dense_bias_kernel, dim3(cdiv(bins, 256)), dim3(256), 0, st, nt.bd, dn[1], dn[2], dn[3], dn[4],
-                         dn[5], bins);
-      PD_LAUNCH_CHECK();
-    }
+  pd_vr* hp = h.get();
+  wp.then([=]() {
     const long long tt = (long long)std::max(ftab, itab);
-    hipLaunchKernelGGL(vr_table_kernel, dim3(cdiv(tt, 256)), dim3(256), 0, st, h->fc, h->fs, h->ic, h->is, h->win,
-                       params[p_window], d.n_fft, h->nb, h->nbp, h->nbk);
+    hipLaunchKernelGGL(vr_table_kernel, dim3(cdiv(tt, 256)), dim3(256), 0, st, hp->fc, hp->fs, hp->ic, hp->is, hp->win,
+                       window, d.n_fft, hp->nb, hp->nbp, hp->nbk);
     PD_LAUNCH_CHECK();
     return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  });
+  PD_TRY(pv.done("pd_vr"));
+  PD_TRY(wp.commit(st, "vr"));
+  *out = h.release();
   return PD_OK;
 }
 

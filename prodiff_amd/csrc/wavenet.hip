@@ -1822,79 +1822,76 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
   PD_TRY(check_params(params, PD_WAVENET_NUM_PARAMS(L)));
   hipStream_t st = (hipStream_t)stream;
 
-  pd_wavenet* h = new pd_wavenet();
+  std::unique_ptr<pd_wavenet> h(new pd_wavenet());
   h->M = M; h->H = H; h->L = L; h->C = C; h->cyc = cyc; h->dtype = dtype;
   h->ldw_in = round_up(M, GEMM_BK);
   h->ldw1 = 3 * C + round_up(H, GEMM_BK);
+  const int ldw1 = h->ldw1;
   WeightPool& wp = h->weights;
-  wp.add(&h->Win, (size_t)C * h->ldw_in); wp.add(&h->b_in, (size_t)C);
-  wp.add(&h->W1, (size_t)4 * C * C); wp.add(&h->b1, (size_t)4 * C);
-  wp.add(&h->W2, (size_t)C * 4 * C); wp.add(&h->b2, (size_t)C);
-  wp.add(&h->Wd, (size_t)L * C * C); wp.add(&h->bd, (size_t)L * C);
-  wp.add(&h->Wl1, (size_t)L * 2 * C * h->ldw1); wp.add(&h->bl1, (size_t)L * 2 * C);
-  wp.add(&h->Wl2, (size_t)L * 2 * C * C); wp.add(&h->bl2, (size_t)L * 2 * C);
-  wp.add(&h->Ws, (size_t)C * C); wp.add(&h->bs, (size_t)C);
-  wp.add(&h->Wo, (size_t)M * C); wp.add(&h->bo, (size_t)M);
-  auto run = [&]() -> int {
-    PD_TRY(wp.commit(st, "WaveNet"));
-    auto cp = [&](float* dst, const float* src, size_t n) { return copy_f32(dst, src, n, st); };
-    int p = 0;
-    PD_TRY(pack_conv(h->Win, h->ldw_in, 0, 0, h->ldw_in, params[p++], C, M, 1, st));
-    PD_TRY(cp(h->b_in, params[p++], C));
-    PD_TRY(cp(h->W1, params[p++], (size_t)4 * C * C));
-    PD_TRY(cp(h->b1, params[p++], 4 * C));
-    PD_TRY(cp(h->W2, params[p++], (size_t)4 * C * C));
-    PD_TRY(cp(h->b2, params[p++], C));
+  ParamView pv{params, PD_WAVENET_NUM_PARAMS(L)};
+  wp.add_conv(&h->Win, pv.next(), C, M, 1, h->ldw_in);
+  wp.add_copy(&h->b_in, C, pv.next());
+  wp.add_copy(&h->W1, (size_t)4 * C * C, pv.next());
+  wp.add_copy(&h->b1, (size_t)4 * C, pv.next());
+  wp.add_copy(&h->W2, (size_t)4 * C * C, pv.next());
+  wp.add_copy(&h->b2, C, pv.next());
+  // The parameters come layer by layer; the pool holds each kind of tensor for all L layers in one slot.
+  struct LayerSrc { const float *dil_w, *dil_b, *dif_w, *dif_b, *con_w, *con_b, *out_w, *out_b; };
+  std::vector<LayerSrc> ly(L);
+  for (LayerSrc& s : ly) s = {pv.next(), pv.next(), pv.next(), pv.next(), pv.next(), pv.next(), pv.next(), pv.next()};
+  // slot of L rows of `per` floats: row l = layer l's `src` tensor
+  auto add_rows = [&](float** slot, size_t per, const float* LayerSrc::*src) {
+    wp.add(slot, L * per, [=](float* dst) {
+      for (int l = 0; l < L; ++l) PD_TRY(copy_f32(dst + l * per, ly[l].*src, per, st));
+      return PD_OK;
+    });
+  };
+  add_rows(&h->Wd, (size_t)C * C, &LayerSrc::dif_w);
+  add_rows(&h->bd, C, &LayerSrc::dif_b);
+  const size_t per1 = (size_t)2 * C * ldw1;   // [2C][dilated conv's 3 taps of C | conditioner's H, padded]
+  wp.add(&h->Wl1, L * per1, [=](float* dst) {
     for (int l = 0; l < L; ++l) {
-      const float* dil_w = params[p++];
-      const float* dil_b = params[p++];
-      const float* dif_w = params[p++];
-      const float* dif_b = params[p++];
-      const float* con_w = params[p++];
-      const float* con_b = params[p++];
-      const float* out_w = params[p++];
-      const float* out_b = params[p++];
-      float* W1l = h->Wl1 + (size_t)l * 2 * C * h->ldw1;
-      PD_TRY(pack_conv(W1l, h->ldw1, 0, 0, C, dil_w, 2 * C, C, 3, st));
-      PD_TRY(pack_conv(W1l, h->ldw1, 0, 3 * C, round_up(H, GEMM_BK), con_w, 2 * C, H, 1, st));
-      PD_TRY(add_vectors(h->bl1 + (size_t)l * 2 * C, dil_b, con_b, 2 * C, st));
-      PD_TRY(cp(h->Wd + (size_t)l * C * C, dif_w, (size_t)C * C));
-      PD_TRY(cp(h->bd + (size_t)l * C, dif_b, C));
-      PD_TRY(cp(h->Wl2 + (size_t)l * 2 * C * C, out_w, (size_t)2 * C * C));
-      PD_TRY(cp(h->bl2 + (size_t)l * 2 * C, out_b, 2 * C));
-    }
-    PD_TRY(cp(h->Ws, params[p++], (size_t)C * C));
-    PD_TRY(cp(h->bs, params[p++], C));
-    PD_TRY(cp(h->Wo, params[p++], (size_t)M * C));
-    PD_TRY(cp(h->bo, params[p++], M));
-    if (dtype == PD_DTYPE_BF16) {
-      PD_TRY(wp.mirror_bf16(st));
-      if (C == WNF_C && 3 * C + H == 1024) {   // H == 256: the fused kernel is built for K1 = 1024
-        const int K1 = 3 * C + H;
-        const size_t per = (size_t)4 * C * K1 + (size_t)2 * C * C;
-        PD_TRY(h->frag.alloc((size_t)L * per * sizeof(__bf16), "the WaveNet fragment-order weights"));
-        h->W1f = static_cast<__bf16*>(h->frag.get());
-        h->W2f = h->W1f + (size_t)L * 2 * C * K1;
-        h->W1p = h->W2f + (size_t)L * 2 * C * C;
-        for (int l = 0; l < L; ++l) {
-          const long long n1 = (long long)2 * C * K1, n2 = (long long)2 * C * C;
-          hipLaunchKernelGGL(pack_frag_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, h->W1f + l * n1,
-                             h->Wl1 + (size_t)l * 2 * C * h->ldw1, 2 * C, K1, h->ldw1);
-          PD_LAUNCH_CHECK();
-          hipLaunchKernelGGL(pack_frag_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, st, h->W2f + l * n2,
-                             h->Wl2 + (size_t)l * 2 * C * C, 2 * C, C, C);
-          PD_LAUNCH_CHECK();
-          hipLaunchKernelGGL(pack_frag_pair_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, h->W1p + l * n1,
-                             h->Wl1 + (size_t)l * 2 * C * h->ldw1, C, K1, h->ldw1);
-          PD_LAUNCH_CHECK();
-        }
-      }
+      PD_TRY(pack_conv(dst + l * per1, ldw1, 0, 0, C, ly[l].dil_w, 2 * C, C, 3, st));
+      PD_TRY(pack_conv(dst + l * per1, ldw1, 0, 3 * C, round_up(H, GEMM_BK), ly[l].con_w, 2 * C, H, 1, st));
     }
     return PD_OK;
-  };
-  const int rc = run();
-  if (rc != PD_OK) { delete h; return rc; }
-  *out = h;
+  });
+  wp.add(&h->bl1, (size_t)L * 2 * C, [=](float* dst) {
+    for (int l = 0; l < L; ++l) PD_TRY(add_vectors(dst + (size_t)l * 2 * C, ly[l].dil_b, ly[l].con_b, 2 * C, st));
+    return PD_OK;
+  });
+  add_rows(&h->Wl2, (size_t)2 * C * C, &LayerSrc::out_w);
+  add_rows(&h->bl2, (size_t)2 * C, &LayerSrc::out_b);
+  wp.add_copy(&h->Ws, (size_t)C * C, pv.next());
+  wp.add_copy(&h->bs, C, pv.next());
+  wp.add_copy(&h->Wo, (size_t)M * C, pv.next());
+  wp.add_copy(&h->bo, M, pv.next());
+  PD_TRY(pv.done("pd_wavenet"));
+  PD_TRY(wp.commit(st, "WaveNet"));
+  if (dtype == PD_DTYPE_BF16) {
+    PD_TRY(wp.mirror_bf16(st));
+    if (C == WNF_C && 3 * C + H == 1024) {   // H == 256: the fused kernel is built for K1 = 1024
+      const int K1 = 3 * C + H;
+      const size_t per = (size_t)4 * C * K1 + (size_t)2 * C * C;
+      PD_TRY(h->frag.alloc((size_t)L * per * sizeof(__bf16), "the WaveNet fragment-order weights"));
+      h->W1f = static_cast<__bf16*>(h->frag.get());
+      h->W2f = h->W1f + (size_t)L * 2 * C * K1;
+      h->W1p = h->W2f + (size_t)L * 2 * C * C;
+      for (int l = 0; l < L; ++l) {
+        const long long n1 = (long long)2 * C * K1, n2 = (long long)2 * C * C;
+        hipLaunchKernelGGL(pack_frag_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, h->W1f + l * n1,
+                           h->Wl1 + (size_t)l * 2 * C * h->ldw1, 2 * C, K1, h->ldw1);
+        PD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pack_frag_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, st, h->W2f + l * n2,
+                           h->Wl2 + (size_t)l * 2 * C * C, 2 * C, C, C);
+        PD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pack_frag_pair_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, h->W1p + l * n1,
+                           h->Wl1 + (size_t)l * 2 * C * h->ldw1, C, K1, h->ldw1);
+        PD_LAUNCH_CHECK();
+      }
+    }
+  }
+  *out = h.release();
   return PD_OK;
 }
 

@@ -47,6 +47,21 @@ def test_full_model_parameter_count():
     assert sum(int(np.prod(s)) for s in shapes.values()) - stats == 90423165
 
 
+@pytest.mark.parametrize("n_gru", [0, 1])
+@pytest.mark.parametrize("en_de_layers", [1, 5])
+@pytest.mark.parametrize("n_blocks", [1, 4])
+@pytest.mark.parametrize("inter_layers", [1, 4])
+def test_num_params_is_the_length_of_the_param_table(n_gru, en_de_layers, n_blocks, inter_layers):
+    """pd_rmvpe_num_params counts by running the create walk itself: every branch of that walk (with and without
+    the GRU, one level or five, blocks with and without a shortcut, one or several per stage) against the table."""
+    from prodiff_amd import _lib
+    model = dict(n_blocks=n_blocks, n_gru=n_gru, en_de_layers=en_de_layers, inter_layers=inter_layers,
+                 en_out_channels=16)
+    dims = _lib.pd_rmvpe_dims(n_blocks, n_gru, en_de_layers, inter_layers, 16, synth.RMVPE_N_MELS,
+                              synth.RMVPE_N_CLASS, synth.RMVPE_GRU_HIDDEN)
+    assert _lib.lib().pd_rmvpe_num_params(_lib.C.byref(dims)) == len(synth.rmvpe_param_shapes(**model))
+
+
 def test_draw_rules():
     P = synth.synth_rmvpe_params(synth.rmvpe_param_shapes(**RC.CASES["rmvpe_slim"][0]), 3)
     for k, v in P.items():
