@@ -900,6 +900,35 @@ int pd_vr_istft(const pd_vr* h, const float* spec_re, const float* spec_im, cons
  * non-NULL.  The spectrum and the mask live in the workspace; nothing spectrum-sized is copied between the stages. */
 int pd_vr_separate(const pd_vr* h, const float* wav, float* harmonic, float* aperiodic, int B, int L, void* workspace,
                    size_t ws_bytes, void* stream);
+/* pd_vr_separate for a ragged batch.  lens: device int32 [B], row b's samples L_b in [1, L]; L (the longest row)
+ * stays the row stride of wav, harmonic and aperiodic and sizes the workspace exactly as above.  Row b is computed
+ * from its first L_b samples as the clip run alone: T_b = pd_vr_frames(L_b) frames with the lead pd_vr_lead(L_b) in
+ * the STFT and the iSTFT; at U-Net level l every pixel with t >= T_b >> l lies outside the image, for every conv
+ * (the ASPP's dilated taps and the frequency mean's 1x1 conv included: rows of 2, 4 and 6 bottom frames sit side by
+ * side), the bilinear x2 gather's index and weight arithmetic uses the row's own heights, and both LSTM directions
+ * run T_b / 2 trips, the reverse one from frame T_b / 2 - 1 and zero state.  Whatever wav holds past L_b, or the
+ * workspace past T_b, is never used (it may be NaN).  harmonic[b][c][i] and aperiodic[b][c][i] for i < L_b equal,
+ * bit for bit, pd_vr_separate of that row alone with L = L_b; for L_b <= i < L both are written as 0.  A lens[b]
+ * outside [1, L] is clamped into it (every access stays inside the row).  lens == NULL returns PD_ERR_ARG.  The
+ * launches are those of pd_vr_separate (a tile that lies wholly past its row's height returns at once, before any
+ * barrier; the iSTFT's grid covers the L / hop + 2 segments a row of any length can have); stream-ordered, no
+ * allocation, no synchronisation, capturable. */
+int pd_vr_separate_ragged(const pd_vr* h, const float* wav, const int* lens, float* harmonic, float* aperiodic, int B,
+                          int L, void* workspace, size_t ws_bytes, void* stream);
+/* Its three stages.  pd_vr_stft_ragged and pd_vr_istft_ragged take lens: device int32 [rows], one sample count per
+ * row (clamped into [1, L]); the row's frames and lead follow from it as pd_vr_frames and pd_vr_lead give them, so
+ * the equal-length calls' `lead` has no counterpart.  T, a multiple of 32 that holds the frames of L samples, is the
+ * row stride of the spectra; frames at or past a row's own count are neither written by the STFT nor read by the
+ * iSTFT, which writes y (and resid) as 0 from the row's length up to L.
+ * pd_vr_mask_ragged takes frames: device int32 [B], each a positive multiple of 32 and at most T (rounded down to a
+ * multiple of 32 inside [32, T] otherwise); the mask past a row's frames is unspecified. */
+int pd_vr_stft_ragged(const pd_vr* h, const float* wav, const int* lens, float* re, float* im, int rows, int L, int T,
+                      void* stream);
+int pd_vr_mask_ragged(const pd_vr* h, const float* spec_re, const float* spec_im, const int* frames, float* mask_re,
+                      float* mask_im, int B, int T, void* workspace, size_t ws_bytes, void* stream);
+int pd_vr_istft_ragged(const pd_vr* h, const float* spec_re, const float* spec_im, const float* mask_re,
+                       const float* mask_im, const float* wav, const int* lens, float* y, float* resid, int rows, int T,
+                       int L, void* stream);
 
 /* ======================================================================== variance curves
  * pd_curves -- get_kth_harmonic, get_energy, get_voicing, get_breath and get_tension of
@@ -923,7 +952,8 @@ int pd_vr_separate(const pd_vr* h, const float* wav, float* harmonic, float* ape
  *             then the smoothing taps (cross-correlation, (k - 1) / 2 replicated frames on the left, the rest on the
  *             right: Conv1d padding = 'same', padding_mode = 'replicate'), then with `norm` clamp to [db_min, db_max]
  *             and (x - db_min) / (db_max - db_min).
- * Sums run in double and round once; the mask decision is f32 as above.  Rows of a batch have equal length. */
+ * Sums run in double and round once; the mask decision is f32 as above.  Rows of a batch have equal length in the
+ * calls below; the *_ragged calls at the end of the section take per-row sizes. */
 typedef struct pd_curves pd_curves;
 
 typedef struct {
@@ -969,6 +999,27 @@ int pd_curves_forward(const pd_curves* h, const float* sp, const float* ap, cons
                       int tension_domain, int mel_len, const float* taps, int kernel_size, int norm, float db_min,
                       float db_max, float* voicing, float* breath, float* tension, float* base, int B, int L, int T_f0,
                       void* workspace, size_t ws_bytes, void* stream);
+/* The three calls above for a ragged batch.  rows: device int32 [B][3] = (L_b, mel_len_b, T_f0_b) per row (a call
+ * that takes no f0, or no mel_len, ignores that value); L, mel_len and T_f0 stay the row strides of the waveforms,
+ * the curves and f0 and size the workspace.  Row b is that row run alone: the reflect or constant padding at its own
+ * end, T_b = L_b / hop + 1 frames, f0 padded on the right with its last value and interpolated over its own T_f0_b
+ * frames, amplitude_to_db's maximum over its own mel_len_b frames, the smoothing's edge clamp at mel_len_b.  What
+ * the inputs hold past a row's sizes is never used (it may be NaN).  The outputs below mel_len_b and L_b equal, bit
+ * for bit, the equal-length call of that row alone; past them they are written as 0.  Each L_b must exceed
+ * win_size / 2 and lie in (win_size / 2, L], mel_len_b in [1, mel_len], T_f0_b in [1, T_f0]: the caller checks this
+ * where it holds the values on the host, the kernels clamp into these ranges so that every access stays inside the
+ * row.  rows == NULL returns PD_ERR_ARG.  Same launches as the equal-length calls (a block that lies wholly past its
+ * row's frames returns at once, before any barrier); stream-ordered, no allocation, capturable. */
+int pd_curves_kth_harmonic_ragged(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid,
+                                  const int* rows, int B, int L, int T_f0, void* workspace, size_t ws_bytes,
+                                  void* stream);
+int pd_curves_energy_ragged(const pd_curves* h, const float* wav, int pad_mode, int domain, int mel_len,
+                            const float* taps, int kernel_size, int norm, float db_min, float db_max, float* out,
+                            const int* rows, int B, int L, void* workspace, size_t ws_bytes, void* stream);
+int pd_curves_forward_ragged(const pd_curves* h, const float* sp, const float* ap, const float* f0, int pad_mode,
+                             int tension_domain, int mel_len, const float* taps, int kernel_size, int norm,
+                             float db_min, float db_max, float* voicing, float* breath, float* tension, float* base,
+                             const int* rows, int B, int L, int T_f0, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

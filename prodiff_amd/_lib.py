@@ -224,6 +224,19 @@ _SIGS = {
     "pd_curves_smooth": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP]),
     "pd_curves_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, C.c_float,
                                     C.c_float, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    # ragged batches: the equal-length call's arguments plus the device int32 size array (the two transforms'
+    # per-row lead follows from the sizes, so their scalar `lead` is gone)
+    "pd_vr_separate_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_vr_stft_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "pd_vr_mask_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_vr_istft_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "pd_curves_kth_harmonic_ragged": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP,
+                                                C.c_size_t, _VP]),
+    "pd_curves_energy_ragged": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int, C.c_float,
+                                          C.c_float, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_curves_forward_ragged": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int,
+                                           C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
+                                           _VP, C.c_size_t, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 

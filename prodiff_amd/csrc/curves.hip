@@ -14,6 +14,11 @@
 // the curve arithmetic (dB, tension, logit) likewise evaluate in double from f32 inputs and round once, the
 // smoothing sums its f32 taps times f32 curve values in double.  The mask decision itself is fp32, operation for
 // operation what the reference computes (exp2f(log2f(f0)) * win / sr, - hw, + hw, the comparisons).
+//
+// Ragged batches (pd_curves_*_ragged): every kernel has a second template instance (RG) that takes the row's own
+// (L_b, mel_len_b, T_f0_b) from a device int32 [B][3] where the equal-length instance takes the launch's; strides and
+// grids stay those of the longest row, a block past its row's frames returns before any barrier, and the outputs
+// past a row's sizes are written as 0.
 #include <cmath>
 #include <string>
 
@@ -49,6 +54,20 @@ __global__ __launch_bounds__(256) void cv_table_kernel(float* __restrict__ w, fl
   tw[n] = make_float2((float)cospi(x), (float)sinpi(x));
 }
 
+// ---------------------------------------------------------------- ragged batches
+// rows: device int32 [B][3] = (L_b, mel_len_b, T_f0_b), null in the equal-length calls.  Every kernel below is a
+// template on RG; its equal-length instance reads no row sizes.  The values are clamped so that every access stays
+// inside the row: L_b into (win / 2, L], mel_len_b into [1, mel_len], T_f0_b into [1, T_f0].
+__device__ __forceinline__ int cv_row_samples(const int* rows, int b, int L, int win) {
+  return min(max(rows[3 * b], min(win / 2 + 1, L)), L);
+}
+__device__ __forceinline__ int cv_row_mel(const int* rows, int b, int mel_len) {
+  return min(max(rows[3 * b + 1], 1), mel_len);
+}
+__device__ __forceinline__ int cv_row_f0(const int* rows, int b, int T_f0) {
+  return min(max(rows[3 * b + 2], 1), T_f0);
+}
+
 // ---------------------------------------------------------------- f0 preparation
 struct F0Args {
   const float* f0;   // [B][T_f0]
@@ -57,6 +76,8 @@ struct F0Args {
   int T_f0, Tn, T;
   float kmul;        // k + 1
   CvPlan p;
+  const int* rows;   // RG
+  int L;
 };
 
 // f0 * (k + 1), padded on the right with its last value
@@ -67,37 +88,45 @@ __device__ __forceinline__ float cv_f0_at(const float* row, int i, int T_f0, flo
 // One wave per row.  interp_f0 (utils/pitch_utils.py:45-51) over the whole padded array: log2 of the voiced
 // frames, np.interp (double) across the unvoiced ones, flat beyond the first and last voiced frame, rounded to
 // f32, then 2 ** (.) for every frame; an all-unvoiced row keeps the reference's -inf, so f0 = 0 and no bin.
+// RG: the row's own frame counts; the strides stay T_f0, Tn and T.
+template <bool RG>
 __global__ __launch_bounds__(64) void cv_f0_kernel(const F0Args a) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const float* row = a.f0 + (long long)b * a.T_f0;
   int* prev = a.prev + (long long)b * a.Tn;
+  int T_f0 = a.T_f0, Tn = a.Tn, T = a.T;
+  if (RG) {
+    T_f0 = cv_row_f0(a.rows, b, a.T_f0);
+    T = cv_row_samples(a.rows, b, a.L, a.p.win) / a.p.hop + 1;
+    Tn = max(T, T_f0);
+  }
   int carry = -1;
-  for (int base = 0; base < a.Tn; base += 64) {
+  for (int base = 0; base < Tn; base += 64) {
     const int i = base + lane;
-    const bool voiced = i < a.Tn && cv_f0_at(row, i, a.T_f0, a.kmul) != 0.f;
+    const bool voiced = i < Tn && cv_f0_at(row, i, T_f0, a.kmul) != 0.f;
     const unsigned long long m = __ballot(voiced);
     const unsigned long long below = m & ((2ull << lane) - 1ull);
-    if (i < a.Tn) prev[i] = below ? base + 63 - __clzll((long long)below) : carry;
+    if (i < Tn) prev[i] = below ? base + 63 - __clzll((long long)below) : carry;
     if (m) carry = base + 63 - __clzll((long long)m);
   }
   carry = -1;   // now the first voiced frame after the chunk
-  for (int base = (a.Tn - 1) / 64 * 64; base >= 0; base -= 64) {
+  for (int base = (Tn - 1) / 64 * 64; base >= 0; base -= 64) {
     const int i = base + lane;
-    const bool voiced = i < a.Tn && cv_f0_at(row, i, a.T_f0, a.kmul) != 0.f;
+    const bool voiced = i < Tn && cv_f0_at(row, i, T_f0, a.kmul) != 0.f;
     const unsigned long long m = __ballot(voiced);
     const unsigned long long above = m >> lane;
     const int nx = above ? i + __ffsll((unsigned long long)above) - 1 : carry;
     if (m) carry = base + __ffsll((unsigned long long)m) - 1;
-    if (i >= a.T) continue;
+    if (i >= T) continue;
     const int pv = prev[i];   // written by this same thread above
     float lf;
     if (pv < 0 && nx < 0) {
       lf = -INFINITY;
     } else if (pv < 0 || nx < 0 || pv == nx) {
-      lf = log2f(cv_f0_at(row, pv < 0 ? nx : pv, a.T_f0, a.kmul));
+      lf = log2f(cv_f0_at(row, pv < 0 ? nx : pv, T_f0, a.kmul));
     } else {
-      const double fl = (double)log2f(cv_f0_at(row, pv, a.T_f0, a.kmul));
-      const double fr = (double)log2f(cv_f0_at(row, nx, a.T_f0, a.kmul));
+      const double fl = (double)log2f(cv_f0_at(row, pv, T_f0, a.kmul));
+      const double fr = (double)log2f(cv_f0_at(row, nx, T_f0, a.kmul));
       const double slope = (fr - fl) / (double)(nx - pv);
       lf = (float)__dadd_rn(__dmul_rn(slope, (double)(i - pv)), fl);
     }
@@ -144,12 +173,17 @@ struct AnArgs {
   float* coef;         // [B][T][8][2]
   int L, T;
   CvPlan p;
+  const int* rows;     // RG
 };
 
+// RG: the row reflects at its own end; a frame past the row's frames returns at once.
+template <bool RG>
 __global__ __launch_bounds__(CV_NT) void cv_analysis_kernel(const AnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float2 stw[];   // [win]
   __shared__ double red[CV_NW * 2 * CV_MAXB];
   const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int L = RG ? cv_row_samples(a.rows, b, a.L, a.p.win) : a.L;
+  if (RG && t > L / a.p.hop) return;
   const int2 fb = a.bins[(long long)b * a.T + t];
   if (fb.y == 0) return;   // the whole block: nothing reads an empty frame's coefficients
   const int win = a.p.win, half = win / 2;
@@ -159,7 +193,7 @@ __global__ __launch_bounds__(CV_NT) void cv_analysis_kernel(const AnArgs a) {
 #pragma unroll
   for (int q = 0; q < 2 * CV_MAXB; ++q) acc[q] = 0.0;
   for (int m = tid; m < win; m += CV_NT) {
-    const long long s = reflect_index((long long)t * a.p.hop + m - half, a.L);
+    const long long s = reflect_index((long long)t * a.p.hop + m - half, L);
     const double xw = (double)__fmul_rn(wrow[s], a.w[m]);
     int idx = (int)(((long long)fb.x * m) % win);
 #pragma unroll
@@ -193,19 +227,32 @@ struct SyArgs {
   float* resid;       // [B][L] or null
   int L, T;
   CvPlan p;
+  const int* rows;    // RG
 };
 
 // y[n] = sum_t w[m] x_t[m] / sum_t w[m]^2 over the frames t with m = n + win/2 - t hop in [0, win) (torch.istft,
 // center = True), x_t = irfft of the kept bins: Re(X) cos / N for DC and Nyquist, 2 Re(X e^{+2 pi i k m / N}) / N else.
+// RG: the row's own frames; the samples from the row's length up to L are written as 0.
+template <bool RG>
 __global__ __launch_bounds__(256) void cv_synth_kernel(const SyArgs a) {
   extern __shared__ __attribute__((aligned(16))) float2 stw[];   // [win]
   const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   const int win = a.p.win, hop = a.p.hop, half = win / 2;
+  int L = a.L, T = a.T;
+  if (RG) {
+    L = cv_row_samples(a.rows, b, a.L, win);
+    T = L / hop + 1;
+    if (n >= L && n < a.L) {
+      a.y[(long long)b * a.L + n] = 0.f;
+      if (a.resid) a.resid[(long long)b * a.L + n] = 0.f;
+    }
+    if ((long long)blockIdx.x * 256 >= L) return;   // the whole block, before the barrier
+  }
   cv_stage_table(stw, a.tw, win, threadIdx.x, 256);
-  if (n >= a.L) return;
+  if (n >= L) return;
   const long long pp = n + half;
-  const int t_hi = (int)min(pp / hop, (long long)a.T - 1);
+  const int t_hi = (int)min(pp / hop, (long long)T - 1);
   const int t_lo = pp >= win ? (int)((pp - win) / hop + 1) : 0;
   double acc = 0.0, env = 0.0;
   for (int t = t_lo; t <= t_hi; ++t) {
@@ -242,21 +289,26 @@ struct RmsArgs {
   RmsJob job[CV_MAX_JOBS];
   int L, T, constant_pad;
   CvPlan p;
+  const int* rows;    // RG
 };
 
 // librosa.feature.rms (0.8.0): pad win / 2 on both sides, frame t = padded [t hop, t hop + win), sqrt(mean(x^2))
+// RG: the row pads at its own end; a frame past the row's frames returns at once.
+template <bool RG>
 __global__ __launch_bounds__(CV_NT) void cv_rms_kernel(const RmsArgs a) {
   __shared__ double red[CV_NW];
   const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const RmsJob jb = a.job[blockIdx.z];
   const int win = a.p.win, half = win / 2;
+  const int L = RG ? cv_row_samples(a.rows, b, a.L, win) : a.L;
+  if (RG && t > L / a.p.hop) return;
   const float* wrow = jb.wav + (long long)b * a.L;
   double acc[1] = {0.0};
   for (int m = tid; m < win; m += CV_NT) {
     const long long s = (long long)t * a.p.hop + m - half;
     double x;
-    if (a.constant_pad) x = (s >= 0 && s < a.L) ? (double)wrow[s] : 0.0;
-    else x = (double)wrow[reflect_index(s, a.L)];
+    if (a.constant_pad) x = (s >= 0 && s < L) ? (double)wrow[s] : 0.0;
+    else x = (double)wrow[reflect_index(s, L)];
     acc[0] += x * x;
   }
   cv_block_sum<1>(acc, red, tid);
@@ -280,6 +332,8 @@ struct FinArgs {
   const float* taps;   // [ksize] or null: no smoothing
   int ksize, Te, mel_len;
   float db_min, db_max;
+  const int* rows;     // RG
+  int L, win, hop;
 };
 
 // the amplitude the dB step (or nothing) is applied to: frame i of the curve zero-padded to mel_len
@@ -307,16 +361,26 @@ __device__ __forceinline__ float cv_value(int mode, float amp, float floor_db) {
 // One block per 256 output frames of one row of one curve.  dB modes: 10 log10 is monotone in the amplitude, so
 // the row maximum of the dB curve is the dB of the largest amplitude.  Then the unsmoothed values of the tile and
 // its halo (replicate padding: indices clamped into the row) in LDS, the taps, clamp and normalisation.
+// RG: the row's own frames and mel_len (the row maximum, the zero padding and the edge clamp follow them); the
+// strides stay Te and mel_len, and the frames from the row's mel_len up to mel_len are written as 0.
+template <bool RG>
 __global__ __launch_bounds__(CV_NT) void cv_finish_kernel(const FinArgs a) {
   __shared__ float pts[CV_NT + CV_MAX_TAPS - 1];
   __shared__ float wmax[CV_NW];
   const int tid = threadIdx.x, row = blockIdx.y, tile0 = blockIdx.x * CV_NT;
   const FinJob jb = a.job[blockIdx.z];
   const long long row0 = (long long)row * a.Te;
+  int Te = a.Te, mel_len = a.mel_len;
+  if (RG) {
+    Te = cv_row_samples(a.rows, row, a.L, a.win) / a.hop + 1;
+    mel_len = cv_row_mel(a.rows, row, a.mel_len);
+    if (tile0 + tid >= mel_len && tile0 + tid < a.mel_len) jb.out[(long long)row * a.mel_len + tile0 + tid] = 0.f;
+    if (tile0 >= mel_len) return;   // the whole block, before any barrier
+  }
   float floor_db = 0.f;
   if (jb.mode == CV_DB || jb.mode == CV_T_DB) {
     float mx = 0.f;   // amplitudes are >= 0, and a NaN does not enter (fmaxf returns the other operand)
-    for (int i = tid; i < a.mel_len; i += CV_NT) mx = fmaxf(mx, fabsf(cv_amp(jb, row0, i, a.Te)));
+    for (int i = tid; i < mel_len; i += CV_NT) mx = fmaxf(mx, fabsf(cv_amp(jb, row0, i, Te)));
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off));
     if ((tid & 63) == 0) wmax[tid >> 6] = mx;
@@ -328,12 +392,12 @@ __global__ __launch_bounds__(CV_NT) void cv_finish_kernel(const FinArgs a) {
   }
   const int k = a.taps ? a.ksize : 1, left = (k - 1) / 2;
   for (int q = tid; q < CV_NT + k - 1; q += CV_NT) {
-    const int src = min(max(tile0 - left + q, 0), a.mel_len - 1);
-    pts[q] = cv_value(jb.mode, cv_amp(jb, row0, src, a.Te), floor_db);
+    const int src = min(max(tile0 - left + q, 0), mel_len - 1);
+    pts[q] = cv_value(jb.mode, cv_amp(jb, row0, src, Te), floor_db);
   }
   __syncthreads();
   const int i = tile0 + tid;
-  if (i >= a.mel_len) return;
+  if (i >= mel_len) return;
   float v = pts[tid];
   if (a.taps) {
     double s = 0.0;
@@ -413,9 +477,9 @@ int check_taps(const float* taps, int ksize) {
   return PD_OK;
 }
 
-// every argument is checked by the caller
+// every argument is checked by the caller; rows: a ragged batch's sizes, or null
 int run_kth(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid, int B, int L,
-            int T_f0, char* ws, hipStream_t st) {
+            int T_f0, const int* rows, char* ws, hipStream_t st) {
   const CvLayout lo = layout_of(h->p, B, L, T_f0);
   const int T = L / h->p.hop + 1;
   int2* bins = (int2*)(ws + lo.bins);
@@ -424,46 +488,58 @@ int run_kth(const pd_curves* h, const float* wav, const float* f0, int k, float*
   {
     F0Args a{};
     a.f0 = f0; a.prev = (int*)(ws + lo.prev); a.bins = bins; a.T_f0 = T_f0; a.Tn = std::max(T, T_f0); a.T = T;
-    a.kmul = (float)(k + 1); a.p = h->p;
+    a.kmul = (float)(k + 1); a.p = h->p; a.rows = rows; a.L = L;
     ProfScope ps("curves_f0", st);
-    hipLaunchKernelGGL(cv_f0_kernel, dim3(B), dim3(64), 0, st, a);
+    if (rows) hipLaunchKernelGGL(cv_f0_kernel<true>, dim3(B), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(cv_f0_kernel<false>, dim3(B), dim3(64), 0, st, a);
     PD_LAUNCH_CHECK();
   }
   {
     AnArgs a{};
     a.wav = wav; a.bins = bins; a.w = h->w; a.tw = h->table(); a.coef = coef; a.L = L; a.T = T; a.p = h->p;
+    a.rows = rows;
     ProfScope ps("curves_analysis", st);
-    hipLaunchKernelGGL(cv_analysis_kernel, dim3(T, B), dim3(CV_NT), lds, st, a);
+    if (rows) hipLaunchKernelGGL(cv_analysis_kernel<true>, dim3(T, B), dim3(CV_NT), lds, st, a);
+    else hipLaunchKernelGGL(cv_analysis_kernel<false>, dim3(T, B), dim3(CV_NT), lds, st, a);
     PD_LAUNCH_CHECK();
   }
   {
     SyArgs a{};
     a.coef = coef; a.bins = bins; a.w = h->w; a.tw = h->table(); a.wav = wav; a.y = y; a.resid = resid;
-    a.L = L; a.T = T; a.p = h->p;
+    a.L = L; a.T = T; a.p = h->p; a.rows = rows;
     ProfScope ps("curves_synth", st);
-    hipLaunchKernelGGL(cv_synth_kernel, dim3(cdiv(L, 256), B), dim3(256), lds, st, a);
+    if (rows) hipLaunchKernelGGL(cv_synth_kernel<true>, dim3(cdiv(L, 256), B), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(cv_synth_kernel<false>, dim3(cdiv(L, 256), B), dim3(256), lds, st, a);
     PD_LAUNCH_CHECK();
   }
   return PD_OK;
 }
 
-int run_rms(const pd_curves* h, const RmsJob* jobs, int njobs, int constant_pad, int B, int L, hipStream_t st) {
+int run_rms(const pd_curves* h, const RmsJob* jobs, int njobs, int constant_pad, int B, int L, const int* rows,
+            hipStream_t st) {
   RmsArgs a{};
   for (int j = 0; j < njobs; ++j) a.job[j] = jobs[j];
-  a.L = L; a.T = L / h->p.hop + 1; a.constant_pad = constant_pad; a.p = h->p;
+  a.L = L; a.T = L / h->p.hop + 1; a.constant_pad = constant_pad; a.p = h->p; a.rows = rows;
   ProfScope ps("curves_rms", st);
-  hipLaunchKernelGGL(cv_rms_kernel, dim3(a.T, B, njobs), dim3(CV_NT), 0, st, a);
+  if (rows) hipLaunchKernelGGL(cv_rms_kernel<true>, dim3(a.T, B, njobs), dim3(CV_NT), 0, st, a);
+  else hipLaunchKernelGGL(cv_rms_kernel<false>, dim3(a.T, B, njobs), dim3(CV_NT), 0, st, a);
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
 
+// sizes (with the plan and L they refer to): a ragged batch, or null
 int run_finish(const FinJob* jobs, int njobs, const float* taps, int ksize, int rows, int Te, int mel_len,
-               float db_min, float db_max, hipStream_t st) {
+               float db_min, float db_max, hipStream_t st, const int* sizes = nullptr, const CvPlan* p = nullptr,
+               int L = 0) {
   FinArgs a{};
   for (int j = 0; j < njobs; ++j) a.job[j] = jobs[j];
   a.taps = taps; a.ksize = ksize; a.Te = Te; a.mel_len = mel_len; a.db_min = db_min; a.db_max = db_max;
+  a.rows = sizes;
+  if (sizes) { a.L = L; a.win = p->win; a.hop = p->hop; }
   ProfScope ps("curves_finish", st);
-  hipLaunchKernelGGL(cv_finish_kernel, dim3(cdiv(mel_len, CV_NT), rows, njobs), dim3(CV_NT), 0, st, a);
+  const dim3 grid(cdiv(mel_len, CV_NT), rows, njobs);
+  if (sizes) hipLaunchKernelGGL(cv_finish_kernel<true>, grid, dim3(CV_NT), 0, st, a);
+  else hipLaunchKernelGGL(cv_finish_kernel<false>, grid, dim3(CV_NT), 0, st, a);
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -507,19 +583,24 @@ size_t pd_curves_workspace_size(const pd_curves* h, int B, int L, int T_f0) {
   return layout_of(h->p, B, L, T_f0).total;
 }
 
-int pd_curves_kth_harmonic(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid, int B,
-                           int L, int T_f0, void* workspace, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// pd_curves_kth_harmonic (rows = null) and pd_curves_kth_harmonic_ragged
+int kth_impl(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid, const int* rows,
+             int B, int L, int T_f0, void* workspace, size_t ws_bytes, void* stream) {
   PD_CHECK_ARG(h && wav && f0 && y, "null pointer");
   PD_TRY(check_batch(h, B, L));
   PD_CHECK_ARG(k >= 0 && k < (1 << 20), "k must lie in [0, 2^20), got " + std::to_string(k));
   PD_CHECK_ARG(T_f0 >= 1, "f0 must hold at least one frame, got " + std::to_string(T_f0));
   PD_TRY(check_workspace(h, B, L, T_f0, workspace, ws_bytes));
-  return run_kth(h, wav, f0, k, y, resid, B, L, T_f0, (char*)workspace, (hipStream_t)stream);
+  return run_kth(h, wav, f0, k, y, resid, B, L, T_f0, rows, (char*)workspace, (hipStream_t)stream);
 }
 
-int pd_curves_energy(const pd_curves* h, const float* wav, int pad_mode, int domain, int mel_len, const float* taps,
-                     int kernel_size, int norm, float db_min, float db_max, float* out, int B, int L, void* workspace,
-                     size_t ws_bytes, void* stream) {
+int energy_impl(const pd_curves* h, const float* wav, int pad_mode, int domain, int mel_len, const float* taps,
+                int kernel_size, int norm, float db_min, float db_max, float* out, const int* rows, int B, int L,
+                void* workspace, size_t ws_bytes, void* stream) {
   PD_CHECK_ARG(h && wav && out, "null pointer");
   PD_TRY(check_batch(h, B, L));
   PD_CHECK_ARG(pad_mode == PD_CURVES_PAD_REFLECT || pad_mode == PD_CURVES_PAD_CONSTANT,
@@ -534,9 +615,40 @@ int pd_curves_energy(const pd_curves* h, const float* wav, int pad_mode, int dom
   const int T = L / h->p.hop + 1;
   float* e = (float*)((char*)workspace + lo.rms);
   const RmsJob rj{wav, e};
-  PD_TRY(run_rms(h, &rj, 1, pad_mode == PD_CURVES_PAD_CONSTANT, B, L, st));
+  PD_TRY(run_rms(h, &rj, 1, pad_mode == PD_CURVES_PAD_CONSTANT, B, L, rows, st));
   const FinJob fj{e, nullptr, out, domain == PD_CURVES_DB ? CV_DB : CV_AMP, norm ? 1 : 0};
-  return run_finish(&fj, 1, taps, kernel_size, B, T, mel_len, db_min, db_max, st);
+  return run_finish(&fj, 1, taps, kernel_size, B, T, mel_len, db_min, db_max, st, rows, &h->p, L);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pd_curves_kth_harmonic(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid, int B,
+                           int L, int T_f0, void* workspace, size_t ws_bytes, void* stream) {
+  return kth_impl(h, wav, f0, k, y, resid, nullptr, B, L, T_f0, workspace, ws_bytes, stream);
+}
+
+int pd_curves_kth_harmonic_ragged(const pd_curves* h, const float* wav, const float* f0, int k, float* y, float* resid,
+                                  const int* rows, int B, int L, int T_f0, void* workspace, size_t ws_bytes,
+                                  void* stream) {
+  PD_CHECK_ARG(rows, "null pointer");
+  return kth_impl(h, wav, f0, k, y, resid, rows, B, L, T_f0, workspace, ws_bytes, stream);
+}
+
+int pd_curves_energy(const pd_curves* h, const float* wav, int pad_mode, int domain, int mel_len, const float* taps,
+                     int kernel_size, int norm, float db_min, float db_max, float* out, int B, int L, void* workspace,
+                     size_t ws_bytes, void* stream) {
+  return energy_impl(h, wav, pad_mode, domain, mel_len, taps, kernel_size, norm, db_min, db_max, out, nullptr, B, L,
+                     workspace, ws_bytes, stream);
+}
+
+int pd_curves_energy_ragged(const pd_curves* h, const float* wav, int pad_mode, int domain, int mel_len,
+                            const float* taps, int kernel_size, int norm, float db_min, float db_max, float* out,
+                            const int* rows, int B, int L, void* workspace, size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(rows, "null pointer");
+  return energy_impl(h, wav, pad_mode, domain, mel_len, taps, kernel_size, norm, db_min, db_max, out, rows, B, L,
+                     workspace, ws_bytes, stream);
 }
 
 int pd_curves_smooth(const float* x, const float* taps, int kernel_size, float* out, int rows, int T, void* stream) {
@@ -548,10 +660,14 @@ int pd_curves_smooth(const float* x, const float* taps, int kernel_size, float* 
   return run_finish(&fj, 1, taps, kernel_size, rows, T, T, 0.f, 0.f, (hipStream_t)stream);
 }
 
-int pd_curves_forward(const pd_curves* h, const float* sp, const float* ap, const float* f0, int pad_mode,
-                      int tension_domain, int mel_len, const float* taps, int kernel_size, int norm, float db_min,
-                      float db_max, float* voicing, float* breath, float* tension, float* base, int B, int L, int T_f0,
-                      void* workspace, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+int forward_impl(const pd_curves* h, const float* sp, const float* ap, const float* f0, int pad_mode,
+                 int tension_domain, int mel_len, const float* taps, int kernel_size, int norm, float db_min,
+                 float db_max, float* voicing, float* breath, float* tension, float* base, const int* rows, int B, int L,
+                 int T_f0, void* workspace, size_t ws_bytes, void* stream) {
   PD_CHECK_ARG(h && sp && f0 && tension, "null pointer");
   PD_CHECK_ARG(!breath || ap, "breath needs the aperiodic part");
   PD_TRY(check_batch(h, B, L));
@@ -568,17 +684,38 @@ int pd_curves_forward(const pd_curves* h, const float* sp, const float* ap, cons
   const CvLayout lo = layout_of(h->p, B, L, T_f0);
   const int T = L / h->p.hop + 1;
   float* y = base ? base : (float*)(ws + lo.base);
-  PD_TRY(run_kth(h, sp, f0, 0, y, nullptr, B, L, T_f0, ws, st));
+  PD_TRY(run_kth(h, sp, f0, 0, y, nullptr, B, L, T_f0, rows, ws, st));
   float* e = (float*)(ws + lo.rms);
   const size_t per = (size_t)B * T;
   RmsJob rj[CV_MAX_JOBS] = {{sp, e}, {y, e + per}, {ap, e + 2 * per}};
-  PD_TRY(run_rms(h, rj, breath ? 3 : 2, pad_mode == PD_CURVES_PAD_CONSTANT, B, L, st));
+  PD_TRY(run_rms(h, rj, breath ? 3 : 2, pad_mode == PD_CURVES_PAD_CONSTANT, B, L, rows, st));
   FinJob fj[CV_MAX_JOBS];
   int nj = 0;
   fj[nj++] = FinJob{e, e + per, tension, CV_T_RATIO + tension_domain, 0};
   if (voicing) fj[nj++] = FinJob{e, nullptr, voicing, CV_DB, norm ? 1 : 0};
   if (breath) fj[nj++] = FinJob{e + 2 * per, nullptr, breath, CV_DB, norm ? 1 : 0};
-  return run_finish(fj, nj, taps, kernel_size, B, T, mel_len, db_min, db_max, st);
+  return run_finish(fj, nj, taps, kernel_size, B, T, mel_len, db_min, db_max, st, rows, &h->p, L);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pd_curves_forward(const pd_curves* h, const float* sp, const float* ap, const float* f0, int pad_mode,
+                      int tension_domain, int mel_len, const float* taps, int kernel_size, int norm, float db_min,
+                      float db_max, float* voicing, float* breath, float* tension, float* base, int B, int L, int T_f0,
+                      void* workspace, size_t ws_bytes, void* stream) {
+  return forward_impl(h, sp, ap, f0, pad_mode, tension_domain, mel_len, taps, kernel_size, norm, db_min, db_max,
+                      voicing, breath, tension, base, nullptr, B, L, T_f0, workspace, ws_bytes, stream);
+}
+
+int pd_curves_forward_ragged(const pd_curves* h, const float* sp, const float* ap, const float* f0, int pad_mode,
+                             int tension_domain, int mel_len, const float* taps, int kernel_size, int norm,
+                             float db_min, float db_max, float* voicing, float* breath, float* tension, float* base,
+                             const int* rows, int B, int L, int T_f0, void* workspace, size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(rows, "null pointer");
+  return forward_impl(h, sp, ap, f0, pad_mode, tension_domain, mel_len, taps, kernel_size, norm, db_min, db_max,
+                      voicing, breath, tension, base, rows, B, L, T_f0, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

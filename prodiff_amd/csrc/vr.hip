@@ -30,6 +30,12 @@
 //
 // Every output element is one f32 operation sequence in a fixed order that does not depend on B, on the batch row
 // or on the tile position.
+//
+// Ragged batches (pd_vr_*_ragged): the conv, LSTM, STFT and iSTFT kernels have a second template instance (RG) that
+// reads a row's own samples or frames from a device int32 array (VrRag) and uses the row's heights, lead and length
+// wherever the equal-length instance uses the launch's; strides and grids stay those of the longest row.  The
+// pointwise kernels (input interleave, mean over the bins, linear layers, bounded mask) run over all frames: what
+// they write past a row's frames is never read.  The equal-length instances compile to what they were.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -121,6 +127,26 @@ struct VrSrc {
   int vec;        // every pixel's channel 0 is 16-byte aligned
 };
 
+// A ragged batch's per-row sizes: v = device int32, one value per group of `div` consecutive rows; null in the
+// equal-length calls.  hop > 0: v holds samples (clamped into [1, L]), a row's frames and lead follow from them as
+// pd_vr_frames and pd_vr_lead give them; hop == 0: v holds frames (rounded down to a multiple of 32 inside [32, T]).
+struct VrRag {
+  const int* v;
+  int L, hop, nf, T, div;
+};
+
+__device__ __forceinline__ int vr_rag_len(const VrRag& g, int row) { return min(max(g.v[row / g.div], 1), g.L); }
+
+__device__ __forceinline__ int vr_rag_frames(const VrRag& g, int row) {
+  if (g.hop == 0) return max(min(g.v[row / g.div], g.T) & ~31, 32);
+  return min(32 * ((vr_rag_len(g, row) / g.hop + 1) / 32 + 1), g.T);
+}
+
+// lead of a row of Lb samples in Tb frames (pd_vr_lead)
+__device__ __forceinline__ int vr_rag_lead(const VrRag& g, int Lb, int Tb) {
+  return g.nf / 2 + (int)(((long long)(Tb - 1) * g.hop - Lb) / 2 / g.hop * g.hop);
+}
+
 struct VrConvArgs {
   VrSrc s[2];
   int nsrc;
@@ -134,6 +160,8 @@ struct VrConvArgs {
   float* out;
   long long obs;
   int oys, oxs, cout;
+  VrRag rg;            // RG: image b is (frames(b) >> lvl) rows tall inside its Hi-row allocation
+  int lvl;
 };
 
 // channels cb .. cb + 7 of one stored pixel, zero from channel s.c on
@@ -156,12 +184,20 @@ __device__ __forceinline__ void vr_lerp_index(float scale, int i, int n_in, int&
 }
 
 // TAPS 1 or 9; UP: source 0 is read through the gather; NT: 32-channel output tiles per wave (the pixel's values
-// are fetched once for all of them)
-template <int TAPS, bool UP, int NT>
+// are fetched once for all of them); RG: a ragged batch, every pixel at or past the row's own height lies outside
+// the image (read as the border's zero, never written), and a tile wholly past it returns at once
+template <int TAPS, bool UP, int NT, bool RG>
 __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int b = blockIdx.z, ct0 = blockIdx.y * NT;
-  const int npix = a.H * a.W;
+  int Hi = a.Hi, H = a.H;
+  float sy = a.sy;
+  if (RG) {
+    Hi = __builtin_amdgcn_readfirstlane(vr_rag_frames(a.rg, b) >> a.lvl);
+    H = Hi / a.stride;
+    sy = Hi > 1 ? __fdiv_rn((float)(Hi / 2 - 1), (float)(Hi - 1)) : 0.f;
+  }
+  const int npix = H * a.W;
   const int p0 = blockIdx.x * 128 + wave * 32;
   if (p0 >= npix) return;   // wave-uniform
   const int p = min(p0 + r, npix - 1);   // lanes past the image repeat its last pixel and are never written
@@ -199,12 +235,12 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
 #pragma unroll
           for (int i = 0; i < NT; ++i) load8(wrow[i] + wo + tap * 512, wf[i]);
           const int iy = y * a.stride + (TAPS == 9 ? tr - 1 : 0) * a.dy, ix = x * a.stride + (TAPS == 9 ? tc - 1 : 0) * a.dx;
-          const bool ok = iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi;
-          const int cy = min(max(iy, 0), a.Hi - 1), cx = min(max(ix, 0), a.Wi - 1);
+          const bool ok = iy >= 0 && iy < Hi && ix >= 0 && ix < a.Wi;
+          const int cy = min(max(iy, 0), Hi - 1), cx = min(max(ix, 0), a.Wi - 1);
           if (up) {
             int y0, y1, x0, x1;
             float ly0, ly1, lx0, lx1;
-            vr_lerp_index(a.sy, cy, a.Hi >> 1, y0, y1, ly0, ly1);
+            vr_lerp_index(sy, cy, Hi >> 1, y0, y1, ly0, ly1);
             vr_lerp_index(a.sx, cx, a.Wi >> 1, x0, x1, lx0, lx1);
             float v00[8], v01[8], v10[8], v11[8];   // v[bin][frame]
             vr_pixel8(s, img + (long long)y0 * s.ys + (long long)x0 * s.xs, cb, v00);
@@ -323,8 +359,11 @@ __global__ __launch_bounds__(256) void vr_linear_kernel(const float* __restrict_
 // grid (2 directions, B), 256 threads.  Thread j < 4 Hh owns gate row j (order i, f, g, o) with its W_hh row in
 // registers, zero from Hh on (h in LDS is zero there too, so the chain over 64 equals the chain over Hh).
 // xp [B][T][8 Hh] = W_ih x + b_ih + b_hh, the forward direction's gates first; out [B][T][2 Hh].
+// RG: row b runs over its own frames(b) >> 1 frames (the loop has that many trips, the reverse direction starts at
+// its last one from zero state); the row stride stays T.
+template <bool RG>
 __global__ __launch_bounds__(256) void vr_lstm_kernel(const float* __restrict__ xp, const float* __restrict__ whh,
-                                                      float* __restrict__ out, int T, int Hh) {
+                                                      float* __restrict__ out, int T, int Hh, const VrRag rg) {
   __shared__ __attribute__((aligned(16))) float hs[VR_MAX_HID];
   __shared__ float gs[4 * VR_MAX_HID];
   const int j = threadIdx.x, dir = blockIdx.x, b = blockIdx.y;
@@ -334,9 +373,10 @@ __global__ __launch_bounds__(256) void vr_lstm_kernel(const float* __restrict__ 
   for (int k = 0; k < VR_MAX_HID; ++k) w[k] = (j < G && k < Hh) ? whh[((long long)dir * G + j) * Hh + k] : 0.f;
   if (j < VR_MAX_HID) hs[j] = 0.f;
   float c = 0.f;
+  const int Tb = RG ? __builtin_amdgcn_readfirstlane(vr_rag_frames(rg, b) >> 1) : T;
   __syncthreads();
-  for (int step = 0; step < T; ++step) {
-    const int t = dir ? T - 1 - step : step;
+  for (int step = 0; step < Tb; ++step) {
+    const int t = dir ? Tb - 1 - step : step;
     const long long row = (long long)b * T + t;
     float acc = 0.f;
 #pragma unroll
@@ -370,18 +410,28 @@ struct VrStftArgs {
   float* re;          // [rows][T][nb]
   float* im;
   int L, T, lead, nf, hop, nb, nbp;
+  VrRag rg;
 };
 
 // grid (frame tiles of 32, groups of four 32-bin tiles, rows); frame t covers samples [t hop - lead, .. + n_fft),
 // zero outside [0, L).  A = table (lane: bin, k half), B = the frame's samples (lane: frame, k half).
+// RG: row b's own samples, frames and lead; the row strides stay L and T, the frames past the row's are not written.
+template <bool RG>
 __global__ __launch_bounds__(256) void vr_stft_kernel(const VrStftArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kh = lane >> 5, j = lane & 31;
   const int col0 = (blockIdx.y * 4 + wave) * 32;
   if (col0 >= a.nbp) return;
   const int t = blockIdx.x * 32 + j;
   const long long row = blockIdx.z;
+  int Lb = a.L, Tb = a.T, lead = a.lead;
+  if (RG) {
+    Lb = __builtin_amdgcn_readfirstlane(vr_rag_len(a.rg, (int)row));
+    Tb = __builtin_amdgcn_readfirstlane(vr_rag_frames(a.rg, (int)row));
+    lead = vr_rag_lead(a.rg, Lb, Tb);
+    if ((int)blockIdx.x * 32 >= Tb) return;
+  }
   const float* wr = a.wav + row * a.L;
-  const long long s0 = (long long)t * a.hop - a.lead + kh;
+  const long long s0 = (long long)t * a.hop - lead + kh;
   const float* pc = a.fc + (long long)kh * a.nbp + col0 + j;
   const float* ps = a.fs + (long long)kh * a.nbp + col0 + j;
   f32x16 re, im, re_hi, im_hi, re_lo, im_lo;
@@ -395,8 +445,8 @@ __global__ __launch_bounds__(256) void vr_stft_kernel(const VrStftArgs a) {
       c[u] = pc[o];
       sn[u] = ps[o];
       const long long si = s0 + n0 + 2 * u;
-      const float v = wr[min(max(si, 0ll), (long long)a.L - 1)];
-      y[u] = (si >= 0 && si < a.L) ? v : 0.f;
+      const float v = wr[min(max(si, 0ll), (long long)Lb - 1)];
+      y[u] = (si >= 0 && si < Lb) ? v : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -406,7 +456,7 @@ __global__ __launch_bounds__(256) void vr_stft_kernel(const VrStftArgs a) {
     mfma_fold(re, re_hi, re_lo);
     mfma_fold(im, im_hi, im_lo);
   }
-  if (t >= a.T) return;
+  if (t >= Tb) return;
   // register g of lane (kh, j): bin col0 + 8 (g / 4) + 4 kh + g % 4 of frame j
   float* ore = a.re + (row * a.T + t) * a.nb;
   float* oim = a.im + (row * a.T + t) * a.nb;
@@ -432,28 +482,49 @@ struct VrIstftArgs {
   float* y;           // [rows][L_out]
   float* resid;       // [rows][L_out] or null: wav - y
   int T, nf, hop, R, nb, nbk, lead, L_out, seg0, nseg;
+  VrRag rg;
 };
 
 // grid (groups of four 32-segment tiles, 32-sample tiles of the hop, rows).  Segment j of the overlap-add (samples
 // [j hop, (j + 1) hop)) is sum_{q < R} frame (j - q) [q hop + r].  A = the masked spectrum (lane: segment, k half),
 // B = the table (lane: sample r, k half); K runs over q, then the bins in chunks of 16 (cos and sin parts of a chunk
 // into the same chain).
+// RG: row b's own frames, lead and length decide its segments; the row strides stay T and L_out, the grid covers the
+// segments of any length up to L_out, and the samples from the row's length up to L_out are written as 0.
+template <bool RG>
 __global__ __launch_bounds__(256) void vr_istft_kernel(const VrIstftArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kh = lane >> 5, j = lane & 31;
   const int st0 = (blockIdx.x * 4 + wave) * 32;
-  if (st0 >= a.nseg) return;
-  const int seg = a.seg0 + st0 + j;        // A row of this lane
   const int r0 = blockIdx.y * 32;
-  const int rb = min(r0 + j, a.hop - 1);   // B column of this lane (columns past the hop are never written)
   const long long row = blockIdx.z;
+  int Tb = a.T, lead = a.lead, Lb = a.L_out, seg0 = a.seg0, nseg = a.nseg;
+  if (RG) {
+    Lb = __builtin_amdgcn_readfirstlane(vr_rag_len(a.rg, (int)row));
+    Tb = __builtin_amdgcn_readfirstlane(vr_rag_frames(a.rg, (int)row));
+    lead = vr_rag_lead(a.rg, Lb, Tb);
+    seg0 = lead / a.hop;
+    nseg = (int)(((long long)lead + Lb - 1) / a.hop) - seg0 + 1;
+  }
+  if (st0 >= nseg) {
+    if (RG && r0 + j < a.hop)   // the segments past the row's last one: zeros up to the row stride
+      for (int sl = st0 + kh; sl < st0 + 32; sl += 2) {
+        const long long i = (long long)(seg0 + sl) * a.hop + r0 + j - lead;
+        if (i < Lb || i >= a.L_out) continue;
+        a.y[row * a.L_out + i] = 0.f;
+        if (a.resid) a.resid[row * a.L_out + i] = 0.f;
+      }
+    return;
+  }
+  const int seg = seg0 + st0 + j;          // A row of this lane
+  const int rb = min(r0 + j, a.hop - 1);   // B column of this lane (columns past the hop are never written)
   const long long sbase = row * a.T * a.nb;
   f32x16 acc, hi, lo;
 #pragma unroll
   for (int g = 0; g < 16; ++g) { acc[g] = hi[g] = lo[g] = 0.f; }
   for (int q = 0; q < a.R; ++q) {
     const int t = seg - q;
-    const bool tok = t >= 0 && t < a.T;
-    const long long fo = sbase + (long long)min(max(t, 0), a.T - 1) * a.nb;
+    const bool tok = t >= 0 && t < Tb;
+    const long long fo = sbase + (long long)min(max(t, 0), Tb - 1) * a.nb;
     const float* pc = a.ic + q * a.hop + rb;
     const float* ps = a.is + q * a.hop + rb;
     for (int k0 = 0; k0 < a.nbk; k0 += 16) {
@@ -489,15 +560,20 @@ __global__ __launch_bounds__(256) void vr_istft_kernel(const VrIstftArgs a) {
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const int sl = st0 + mfma_row(g, kh);
-    if (sl >= a.nseg) continue;
-    const int sg = a.seg0 + sl;
-    const long long i = (long long)sg * a.hop + rr - a.lead;
-    if (i < 0 || i >= a.L_out) continue;
+    if (!RG && sl >= nseg) continue;
+    const int sg = seg0 + sl;
+    const long long i = (long long)sg * a.hop + rr - lead;
+    if (RG && i >= Lb && i < a.L_out) {
+      a.y[row * a.L_out + i] = 0.f;
+      if (a.resid) a.resid[row * a.L_out + i] = 0.f;
+    }
+    if (RG && sl >= nseg) continue;
+    if (i < 0 || i >= Lb) continue;
     float env = 0.f;
     for (int q = a.R - 1; q >= 0; --q) {   // frames in ascending order, as the reference's fold adds them
       const int t = sg - q;
       const float w = a.win[q * a.hop + rr];
-      if (t >= 0 && t < a.T) env += w * w;
+      if (t >= 0 && t < Tb) env += w * w;
     }
     const float v = (hi[g] + lo[g]) / env;
     const long long o = row * a.L_out + i;
@@ -601,10 +677,12 @@ struct OutView {
 
 OutView dense_out(float* p, int H, int W, int c) { return OutView{p, (long long)H * W * c, W * c, c}; }
 
-// Hi x Wi: the conv's input image (twice the stored one for a gathered source)
+// Hi x Wi: the conv's input image (twice the stored one for a gathered source); rg.v: a ragged batch, Hi = rg.T >> lvl
 int launch_conv(const Conv& cw, const VrSrc& s0, const VrSrc* s1, int B, int Hi, int Wi, int stride, int dy, int dx,
-                int act, const OutView& o, hipStream_t st, const char* tag) {
+                int act, const OutView& o, const VrRag& rg, hipStream_t st, const char* tag) {
   VrConvArgs a{};
+  a.rg = rg;
+  if (rg.v) a.lvl = __builtin_ctz((unsigned)(rg.T / Hi));
   a.s[0] = s0;
   a.nsrc = 1;
   if (s1) { a.s[1] = *s1; a.nsrc = 2; }
@@ -635,7 +713,8 @@ int launch_conv(const Conv& cw, const VrSrc& s0, const VrSrc* s1, int B, int Hi,
   ProfScope ps(tag, st);
   dispatch([&](auto NT) {
     dispatch_rows<DispatchRow<1, false>, DispatchRow<9, true>, DispatchRow<9, false>>([&](auto TAPS, auto UP) {
-      hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT()>), grid, dim3(256), 0, st, a);
+      if (rg.v) hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT(), true>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT(), false>), grid, dim3(256), 0, st, a);
     }, cw.taps != 9 ? 1 : 9, cw.taps == 9 && up);
   }, one_of<1, 2, 3, 4>(nt));
   PD_LAUNCH_CHECK();
@@ -654,7 +733,7 @@ int launch_linear(const float* x, int xs, const float* wt, int ldn, const float*
 
 // One BaseNet (and a band net's 1x1 tail) on the band [f0, f0 + Fb) of X; the result goes to `dst`.
 int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, int T, int f0, int Fb,
-            const OutView& dst, hipStream_t st) {
+            const OutView& dst, const VrRag& rg, hipStream_t st) {
   const int n = nt.n, F = h.F, cx = h.cx;
   int Hl[5], Wl[5];
   for (int l = 0; l < 5; ++l) { Hl[l] = T >> l; Wl[l] = Fb >> l; }
@@ -663,13 +742,13 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   float* tmp = ws + wp.tmp;
   float* e[5] = {e1, ws + wp.e[0], ws + wp.e[1], ws + wp.e[2], ws + wp.e[3]};
   const int ec[5] = {n, 2 * n, 4 * n, 6 * n, 8 * n};
-  PD_TRY(launch_conv(nt.enc1, xin, nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dense_out(e1, T, Fb, n), st, "vr_enc_l0"));
+  PD_TRY(launch_conv(nt.enc1, xin, nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dense_out(e1, T, Fb, n), rg, st, "vr_enc_l0"));
   static const char* const ENC_TAG[4] = {"vr_enc_l1", "vr_enc_l2", "vr_enc_l3", "vr_enc_l4"};
   for (int l = 1; l < 5; ++l) {
     PD_TRY(launch_conv(nt.enc[l - 1][0], dense_src(e[l - 1], Hl[l - 1], Wl[l - 1], ec[l - 1]), nullptr, B, Hl[l - 1],
-                       Wl[l - 1], 2, 1, 1, ACT_LRELU, dense_out(tmp, Hl[l], Wl[l], ec[l]), st, ENC_TAG[l - 1]));
+                       Wl[l - 1], 2, 1, 1, ACT_LRELU, dense_out(tmp, Hl[l], Wl[l], ec[l]), rg, st, ENC_TAG[l - 1]));
     PD_TRY(launch_conv(nt.enc[l - 1][1], dense_src(tmp, Hl[l], Wl[l], ec[l]), nullptr, B, Hl[l], Wl[l], 1, 1, 1,
-                       ACT_LRELU, dense_out(e[l], Hl[l], Wl[l], ec[l]), st, ENC_TAG[l - 1]));
+                       ACT_LRELU, dense_out(e[l], Hl[l], Wl[l], ec[l]), rg, st, ENC_TAG[l - 1]));
   }
   // ---- ASPP on the T/16 x Fb/16 map, its five branches written side by side into `cat`
   const int H4 = Hl[4], W4 = Wl[4], c8 = 8 * n;
@@ -685,33 +764,33 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   auto cat_out = [&](int br) { return OutView{cat + (size_t)br * c8, (long long)H4 * W4 * 5 * c8, W4 * 5 * c8, 5 * c8}; };
   const VrSrc e5 = dense_src(e[4], H4, W4, c8);
   PD_TRY(launch_conv(nt.aspp[0], make_src(pooled, (long long)H4 * c8, c8, 0, c8, false), nullptr, B, H4, W4, 1, 1, 1,
-                     ACT_RELU, cat_out(0), st, "vr_aspp"));
-  PD_TRY(launch_conv(nt.aspp[1], e5, nullptr, B, H4, W4, 1, 1, 1, ACT_RELU, cat_out(1), st, "vr_aspp"));
+                     ACT_RELU, cat_out(0), rg, st, "vr_aspp"));
+  PD_TRY(launch_conv(nt.aspp[1], e5, nullptr, B, H4, W4, 1, 1, 1, ACT_RELU, cat_out(1), rg, st, "vr_aspp"));
   static const int DIL[3][2] = {{4, 2}, {8, 4}, {12, 6}};   // (bins, frames)
   for (int i = 0; i < 3; ++i)
-    PD_TRY(launch_conv(nt.aspp[2 + i], e5, nullptr, B, H4, W4, 1, DIL[i][1], DIL[i][0], ACT_RELU, cat_out(2 + i), st,
+    PD_TRY(launch_conv(nt.aspp[2 + i], e5, nullptr, B, H4, W4, 1, DIL[i][1], DIL[i][0], ACT_RELU, cat_out(2 + i), rg, st,
                        "vr_aspp"));
   PD_TRY(launch_conv(nt.bott, dense_src(cat, H4, W4, 5 * c8), nullptr, B, H4, W4, 1, 1, 1, ACT_RELU,
-                     dense_out(asp, H4, W4, c8), st, "vr_aspp"));
+                     dense_out(asp, H4, W4, c8), rg, st, "vr_aspp"));
   // ---- decoders: bilinear x2 of the map below (read through the gather) cat the skip
   float* d4 = ws + wp.d4;
   float* d3 = ws + wp.d3;
   float* d2 = ws + wp.d2;
   {
     const VrSrc up = dense_src(asp, H4, W4, c8, true), sk = dense_src(e[3], Hl[3], Wl[3], ec[3]);
-    PD_TRY(launch_conv(nt.dec[0], up, &sk, B, Hl[3], Wl[3], 1, 1, 1, ACT_RELU, dense_out(d4, Hl[3], Wl[3], 6 * n), st,
+    PD_TRY(launch_conv(nt.dec[0], up, &sk, B, Hl[3], Wl[3], 1, 1, 1, ACT_RELU, dense_out(d4, Hl[3], Wl[3], 6 * n), rg, st,
                        "vr_dec_l3"));
   }
   {
     const VrSrc up = dense_src(d4, Hl[3], Wl[3], 6 * n, true), sk = dense_src(e[2], Hl[2], Wl[2], ec[2]);
-    PD_TRY(launch_conv(nt.dec[1], up, &sk, B, Hl[2], Wl[2], 1, 1, 1, ACT_RELU, dense_out(d3, Hl[2], Wl[2], 4 * n), st,
+    PD_TRY(launch_conv(nt.dec[1], up, &sk, B, Hl[2], Wl[2], 1, 1, 1, ACT_RELU, dense_out(d3, Hl[2], Wl[2], 4 * n), rg, st,
                        "vr_dec_l2"));
   }
   // dec2's 2 n channels and the LSTM's one, side by side, the pixel stride rounded up to whole 16-byte rows
   const int H1 = Hl[1], W1 = Wl[1], cd2 = 2 * n + 1, sd2 = round_up(cd2, 4);
   {
     const VrSrc up = dense_src(d3, Hl[2], Wl[2], 4 * n, true), sk = dense_src(e[1], H1, W1, ec[1]);
-    PD_TRY(launch_conv(nt.dec[2], up, &sk, B, H1, W1, 1, 1, 1, ACT_RELU, dense_out(d2, H1, W1, sd2), st, "vr_dec_l1"));
+    PD_TRY(launch_conv(nt.dec[2], up, &sk, B, H1, W1, 1, 1, 1, ACT_RELU, dense_out(d2, H1, W1, sd2), rg, st, "vr_dec_l1"));
   }
   // ---- LSTM module over the T/2 frames, input = the Fb/2 bins
   float* lconv = ws + wp.lconv;
@@ -719,12 +798,13 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   float* lo = ws + wp.lo;
   const int Hh = nt.hid, G = 4 * Hh;
   PD_TRY(launch_conv(nt.lconv, make_src(d2, (long long)H1 * W1 * sd2, W1 * sd2, sd2, 2 * n, false), nullptr, B, H1, W1,
-                     1, 1, 1, ACT_RELU, dense_out(lconv, H1, W1, 1), st, "vr_lstm_conv"));
+                     1, 1, 1, ACT_RELU, dense_out(lconv, H1, W1, 1), rg, st, "vr_lstm_conv"));
   PD_TRY(launch_linear(lconv, W1, nt.wih, 2 * G, nt.bl, xp, 2 * G, 1, (long long)B * H1, 2 * G, W1, false, st,
                        "vr_lstm_xproj"));
   {
     ProfScope ps("vr_lstm", st);
-    hipLaunchKernelGGL(vr_lstm_kernel, dim3(2, B), dim3(256), 0, st, xp, nt.whh, lo, H1, Hh);
+    if (rg.v) hipLaunchKernelGGL(vr_lstm_kernel<true>, dim3(2, B), dim3(256), 0, st, xp, nt.whh, lo, H1, Hh, rg);
+    else hipLaunchKernelGGL(vr_lstm_kernel<false>, dim3(2, B), dim3(256), 0, st, xp, nt.whh, lo, H1, Hh, rg);
     PD_LAUNCH_CHECK();
   }
   PD_TRY(launch_linear(lo, 2 * Hh, nt.wd, W1, nt.bd, d2 + 2 * n, (long long)W1 * sd2, sd2, (long long)B * H1, W1,
@@ -733,10 +813,10 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   {
     const VrSrc up = make_src(d2, (long long)H1 * W1 * sd2, W1 * sd2, sd2, cd2, true), sk = dense_src(e1, T, Fb, n);
     const OutView o = nt.has_tail ? dense_out(ws + wp.d1, T, Fb, n) : dst;
-    PD_TRY(launch_conv(nt.dec1, up, &sk, B, T, Fb, 1, 1, 1, ACT_RELU, o, st, "vr_dec_l0"));
+    PD_TRY(launch_conv(nt.dec1, up, &sk, B, T, Fb, 1, 1, 1, ACT_RELU, o, rg, st, "vr_dec_l0"));
   }
   if (nt.has_tail)
-    PD_TRY(launch_conv(nt.tail, dense_src(ws + wp.d1, T, Fb, n), nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dst, st,
+    PD_TRY(launch_conv(nt.tail, dense_src(ws + wp.d1, T, Fb, n), nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dst, rg, st,
                        "vr_tail"));
   return PD_OK;
 }
@@ -750,16 +830,24 @@ int check_ws(const pd_vr* h, int B, int T, void* workspace, size_t ws_bytes, WsP
   return PD_OK;
 }
 
-int run_stft(const pd_vr* h, const float* wav, float* re, float* im, int rows, int L, int lead, int T, hipStream_t st) {
-  VrStftArgs a{wav, h->fc, h->fs, re, im, L, T, lead, h->d.n_fft, h->d.hop_length, h->nb, h->nbp};
+// a ragged batch's sizes from samples (one value per `div` rows) or, with hop 0, from frames
+VrRag rag_of(const pd_vr* h, const int* v, int L, int T, int div, bool samples = true) {
+  return VrRag{v, L, samples ? h->d.hop_length : 0, h->d.n_fft, T, div};
+}
+
+int run_stft(const pd_vr* h, const float* wav, float* re, float* im, int rows, int L, int lead, int T, const VrRag& rg,
+             hipStream_t st) {
+  VrStftArgs a{wav, h->fc, h->fs, re, im, L, T, lead, h->d.n_fft, h->d.hop_length, h->nb, h->nbp, rg};
   ProfScope ps("vr_stft", st);
-  hipLaunchKernelGGL(vr_stft_kernel, dim3(cdiv(T, 32), cdiv(h->nbp, 128), rows), dim3(256), 0, st, a);
+  const dim3 grid(cdiv(T, 32), cdiv(h->nbp, 128), rows);
+  if (rg.v) hipLaunchKernelGGL(vr_stft_kernel<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(vr_stft_kernel<false>, grid, dim3(256), 0, st, a);
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
 
 int run_mask(const pd_vr* h, const float* sre, const float* sim, float* mre, float* mim, int B, int T, const WsPlan& wp,
-             float* ws, hipStream_t st) {
+             float* ws, const VrRag& rg, hipStream_t st) {
   const int F = h->F, cx = h->cx, nin = h->nin, q = h->d.nout / 4;
   {
     const long long total = (long long)B * T * F * nin;
@@ -772,13 +860,13 @@ int run_mask(const pd_vr* h, const float* sre, const float* sim, float* mre, flo
     return OutView{ws + wp.X + (size_t)f0 * cx + ch, (long long)T * F * cx, F * cx, cx};
   };
   const int Fb = F / 2;
-  PD_TRY(run_net(*h, h->nets[0], wp, ws, B, T, 0, Fb, x_out(0, nin), st));
-  PD_TRY(run_net(*h, h->nets[1], wp, ws, B, T, Fb, Fb, x_out(Fb, nin), st));
-  PD_TRY(run_net(*h, h->nets[2], wp, ws, B, T, 0, Fb, x_out(0, nin + q), st));
-  PD_TRY(run_net(*h, h->nets[3], wp, ws, B, T, Fb, Fb, x_out(Fb, nin + q), st));
-  PD_TRY(run_net(*h, h->nets[4], wp, ws, B, T, 0, F, dense_out(ws + wp.d1, T, F, h->d.nout), st));
+  PD_TRY(run_net(*h, h->nets[0], wp, ws, B, T, 0, Fb, x_out(0, nin), rg, st));
+  PD_TRY(run_net(*h, h->nets[1], wp, ws, B, T, Fb, Fb, x_out(Fb, nin), rg, st));
+  PD_TRY(run_net(*h, h->nets[2], wp, ws, B, T, 0, Fb, x_out(0, nin + q), rg, st));
+  PD_TRY(run_net(*h, h->nets[3], wp, ws, B, T, Fb, Fb, x_out(Fb, nin + q), rg, st));
+  PD_TRY(run_net(*h, h->nets[4], wp, ws, B, T, 0, F, dense_out(ws + wp.d1, T, F, h->d.nout), rg, st));
   PD_TRY(launch_conv(h->out, dense_src(ws + wp.d1, T, F, h->d.nout), nullptr, B, T, F, 1, 1, 1, ACT_NONE,
-                     dense_out(ws + wp.mout, T, F, nin), st, "vr_out"));
+                     dense_out(ws + wp.mout, T, F, nin), rg, st, "vr_out"));
   {
     const long long total = (long long)B * h->C * T * h->nb;
     ProfScope ps("vr_mask", st);
@@ -790,7 +878,7 @@ int run_mask(const pd_vr* h, const float* sre, const float* sim, float* mre, flo
 }
 
 int run_istft(const pd_vr* h, const float* sre, const float* sim, const float* mre, const float* mim, const float* wav,
-              float* y, float* resid, int rows, int T, int lead, int L_out, hipStream_t st) {
+              float* y, float* resid, int rows, int T, int lead, int L_out, const VrRag& rg, hipStream_t st) {
   const int hop = h->d.hop_length;
   VrIstftArgs a{};
   a.sre = sre; a.sim = sim; a.mre = mre; a.mim = mim; a.ic = h->ic; a.is = h->is; a.win = h->win;
@@ -799,8 +887,12 @@ int run_istft(const pd_vr* h, const float* sre, const float* sim, const float* m
   a.lead = lead; a.L_out = L_out;
   a.seg0 = lead / hop;
   a.nseg = (int)(((long long)lead + L_out - 1) / hop) - a.seg0 + 1;
+  a.rg = rg;
   ProfScope ps("vr_istft", st);
-  hipLaunchKernelGGL(vr_istft_kernel, dim3(cdiv(a.nseg, 128), cdiv(hop, 32), rows), dim3(256), 0, st, a);
+  if (rg.v)   // a row of Lb <= L_out samples has at most Lb / hop + 2 segments, counted from its own first one
+    hipLaunchKernelGGL(vr_istft_kernel<true>, dim3(cdiv(L_out / hop + 2, 128), cdiv(hop, 32), rows), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(vr_istft_kernel<false>, dim3(cdiv(a.nseg, 128), cdiv(hop, 32), rows), dim3(256), 0, st, a);
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -963,7 +1055,16 @@ int pd_vr_stft(const pd_vr* h, const float* wav, float* re, float* im, int rows,
   PD_CHECK_ARG(rows > 0 && rows <= 65535, "rows must lie in [1, 65535]");
   PD_CHECK_ARG(L > 0 && T > 0 && lead >= 0, "L and T must be positive, lead non-negative");
   PD_CHECK_ARG((long long)rows * T * h->nb < (1ll << 31), "rows * T too large for one call");
-  return run_stft(h, wav, re, im, rows, L, lead, T, (hipStream_t)stream);
+  return run_stft(h, wav, re, im, rows, L, lead, T, VrRag{}, (hipStream_t)stream);
+}
+
+int pd_vr_stft_ragged(const pd_vr* h, const float* wav, const int* lens, float* re, float* im, int rows, int L, int T,
+                      void* stream) {
+  PD_CHECK_ARG(h && wav && lens && re && im, "null pointer");
+  PD_CHECK_ARG(rows > 0 && rows <= 65535, "rows must lie in [1, 65535]");
+  PD_CHECK_ARG(L > 0 && T > 0 && T % 32 == 0, "L must be positive, T a positive multiple of 32");
+  PD_CHECK_ARG((long long)rows * T * h->nb < (1ll << 31), "rows * T too large for one call");
+  return run_stft(h, wav, re, im, rows, L, 0, T, rag_of(h, lens, L, T, 1), (hipStream_t)stream);
 }
 
 int pd_vr_mask(const pd_vr* h, const float* spec_re, const float* spec_im, float* mask_re, float* mask_im, int B, int T,
@@ -974,7 +1075,20 @@ int pd_vr_mask(const pd_vr* h, const float* spec_re, const float* spec_im, float
   PD_CHECK_ARG(sizes_ok(h, B, T), "B * T too large for one call");
   WsPlan wp;
   PD_TRY(check_ws(h, B, T, workspace, ws_bytes, &wp));
-  return run_mask(h, spec_re, spec_im, mask_re, mask_im, B, T, wp, static_cast<float*>(workspace), (hipStream_t)stream);
+  return run_mask(h, spec_re, spec_im, mask_re, mask_im, B, T, wp, static_cast<float*>(workspace), VrRag{},
+                  (hipStream_t)stream);
+}
+
+int pd_vr_mask_ragged(const pd_vr* h, const float* spec_re, const float* spec_im, const int* frames, float* mask_re,
+                      float* mask_im, int B, int T, void* workspace, size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(h && spec_re && spec_im && frames && mask_re && mask_im, "null pointer");
+  PD_CHECK_ARG(B > 0 && B <= 65535, "B must lie in [1, 65535]");
+  PD_CHECK_ARG(T > 0 && T % 32 == 0, "T must be a positive multiple of 32");
+  PD_CHECK_ARG(sizes_ok(h, B, T), "B * T too large for one call");
+  WsPlan wp;
+  PD_TRY(check_ws(h, B, T, workspace, ws_bytes, &wp));
+  return run_mask(h, spec_re, spec_im, mask_re, mask_im, B, T, wp, static_cast<float*>(workspace),
+                  rag_of(h, frames, 0, T, 1, false), (hipStream_t)stream);
 }
 
 int pd_vr_istft(const pd_vr* h, const float* spec_re, const float* spec_im, const float* mask_re, const float* mask_im,
@@ -986,7 +1100,21 @@ int pd_vr_istft(const pd_vr* h, const float* spec_re, const float* spec_im, cons
   PD_CHECK_ARG(T > 0 && L_out > 0, "T and L_out must be positive");
   PD_CHECK_ARG(lead >= h->d.n_fft / 2 && (long long)lead - h->d.n_fft / 2 + L_out <= (long long)(T - 1) * h->d.hop_length,
                "the kept samples must lie inside the inverse transform's output");
-  return run_istft(h, spec_re, spec_im, mask_re, mask_im, wav, y, resid, rows, T, lead, L_out, (hipStream_t)stream);
+  return run_istft(h, spec_re, spec_im, mask_re, mask_im, wav, y, resid, rows, T, lead, L_out, VrRag{},
+                   (hipStream_t)stream);
+}
+
+int pd_vr_istft_ragged(const pd_vr* h, const float* spec_re, const float* spec_im, const float* mask_re,
+                       const float* mask_im, const float* wav, const int* lens, float* y, float* resid, int rows, int T,
+                       int L, void* stream) {
+  PD_CHECK_ARG(h && spec_re && spec_im && lens && y, "null pointer");
+  PD_CHECK_ARG((mask_re == nullptr) == (mask_im == nullptr), "the mask needs both parts");
+  PD_CHECK_ARG(!resid || wav, "the residual needs the input waveform");
+  PD_CHECK_ARG(rows > 0 && rows <= 65535, "rows must lie in [1, 65535]");
+  PD_CHECK_ARG(L > 0 && T > 0 && T % 32 == 0 && T >= vr_frames(h->d, L),
+               "L must be positive, T a multiple of 32 that holds the frames of L samples");
+  return run_istft(h, spec_re, spec_im, mask_re, mask_im, wav, y, resid, rows, T, pd_vr_lead(h, L), L,
+                   rag_of(h, lens, L, T, 1), (hipStream_t)stream);
 }
 
 int pd_vr_separate(const pd_vr* h, const float* wav, float* harmonic, float* aperiodic, int B, int L, void* workspace,
@@ -1001,9 +1129,29 @@ int pd_vr_separate(const pd_vr* h, const float* wav, float* harmonic, float* ape
   PD_TRY(check_ws(h, B, T, workspace, ws_bytes, &wp));
   hipStream_t st = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
-  PD_TRY(run_stft(h, wav, ws + wp.sre, ws + wp.sim, rows, L, lead, T, st));
-  PD_TRY(run_mask(h, ws + wp.sre, ws + wp.sim, ws + wp.mre, ws + wp.mim, B, T, wp, ws, st));
-  return run_istft(h, ws + wp.sre, ws + wp.sim, ws + wp.mre, ws + wp.mim, wav, harmonic, aperiodic, rows, T, lead, L, st);
+  PD_TRY(run_stft(h, wav, ws + wp.sre, ws + wp.sim, rows, L, lead, T, VrRag{}, st));
+  PD_TRY(run_mask(h, ws + wp.sre, ws + wp.sim, ws + wp.mre, ws + wp.mim, B, T, wp, ws, VrRag{}, st));
+  return run_istft(h, ws + wp.sre, ws + wp.sim, ws + wp.mre, ws + wp.mim, wav, harmonic, aperiodic, rows, T, lead, L,
+                   VrRag{}, st);
+}
+
+int pd_vr_separate_ragged(const pd_vr* h, const float* wav, const int* lens, float* harmonic, float* aperiodic, int B,
+                          int L, void* workspace, size_t ws_bytes, void* stream) {
+  PD_CHECK_ARG(h && wav && lens && harmonic, "null pointer");
+  PD_CHECK_ARG(B > 0 && B * h->C <= 65535, "B * channels must lie in [1, 65535]");
+  PD_CHECK_ARG(L > 0, "L must be positive");
+  const long long Tl = vr_frames(h->d, L);
+  PD_CHECK_ARG(Tl <= 0x7fffffffll && sizes_ok(h, B, Tl), "B * L too large for one call");
+  const int T = (int)Tl, rows = B * h->C;
+  WsPlan wp;
+  PD_TRY(check_ws(h, B, T, workspace, ws_bytes, &wp));
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  const VrRag per_row = rag_of(h, lens, L, T, h->C), per_clip = rag_of(h, lens, L, T, 1);
+  PD_TRY(run_stft(h, wav, ws + wp.sre, ws + wp.sim, rows, L, 0, T, per_row, st));
+  PD_TRY(run_mask(h, ws + wp.sre, ws + wp.sim, ws + wp.mre, ws + wp.mim, B, T, wp, ws, per_clip, st));
+  return run_istft(h, ws + wp.sre, ws + wp.sim, ws + wp.mre, ws + wp.mim, wav, harmonic, aperiodic, rows, T,
+                   pd_vr_lead(h, L), L, per_row, st);
 }
 
 }  // extern "C"

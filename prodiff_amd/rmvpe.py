@@ -373,7 +373,9 @@ def stack_waveforms(waveforms, lens, device):
         if any(r.is_cuda for r in rows):
             audio = torch.zeros(len(rows), max(lens), device=device, dtype=torch.float32)
         else:
-            audio = torch.zeros(len(rows), max(lens), dtype=torch.float32).pin_memory()
+            audio = torch.zeros(len(rows), max(lens), dtype=torch.float32)
+            if torch.device(device).type == "cuda":
+                audio = audio.pin_memory()
         for b, r in enumerate(rows):
             audio[b, :lens[b]] = r
         return audio.to(device, non_blocking=True), lens

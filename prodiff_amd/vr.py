@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from . import _lib, synth
-from .rmvpe import _attach
+from .rmvpe import _attach, stack_waveforms
 
 MAX_LSTM_HIDDEN = 64      # per direction: what the recurrence kernel holds (pd_vr_dims.nout_lstm <= 128)
 
@@ -24,6 +24,16 @@ def padded_frames(n_samples, hop_length):
     T_pad = (T - 1) * hop_length - n_samples
     Tl_pad = T_pad // 2 // hop_length * hop_length
     return T, Tl_pad, T_pad
+
+
+def row_sizes(lens, n_fft, hop_length):
+    """The per-row sizes of a ragged batch from the rows' sample counts, on the host: a list of
+    (T_b, lead_b) = (pd_vr_frames, pd_vr_lead) per row, which the kernels restate from ``lens``."""
+    out = []
+    for n in lens:
+        T, Tl_pad, _ = padded_frames(int(n), hop_length)
+        out.append((T, n_fft // 2 + Tl_pad))
+    return out
 
 
 def check_dims(n_fft, hop_length, nout, nout_lstm):
@@ -111,17 +121,36 @@ class CascadedNet(nn.Module):
             raise ValueError(f"expected a [B, {self.channels}, L] waveform, got {tuple(x.shape)}")
         return x.float().contiguous()
 
-    def _stft(self, rows, lead, T):
-        """rows [R, L] -> (re, im) [R, T, n_fft/2 + 1]; frame t covers samples [t hop - lead, .. + n_fft)."""
+    def _lens(self, lens, B, L, dev, name="lens"):
+        """A ragged batch's sample counts, B host ints in [1, L] -> (the ints, a cached device int32 copy)."""
+        if torch.is_tensor(lens) and lens.is_cuda:
+            raise _lib.HipError(f"CascadedNet: `{name}` must be host integers (the per-row sizes are worked out on the "
+                                "host)")
+        host = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+        return host, _lib._device_rows(host, B, dev, name, 1, L)
+
+    def _stft(self, rows, lead, T, lens=None):
+        """rows [R, L] -> (re, im) [R, T, n_fft/2 + 1]; frame t covers samples [t hop - lead, .. + n_fft).
+        ``lens`` (R host ints): a ragged batch (pd_vr_stft_ragged) -- row r is its first lens[r] samples with its
+        own frame count and lead (``lead`` is not used), its frames past that count stay zero."""
         h = self.handle()
         R, L = rows.shape
+        if lens is not None:
+            _, ld = self._lens(lens, R, L, rows.device)
+            re = torch.zeros(R, T, self.output_bin, device=rows.device, dtype=torch.float32)
+            im = torch.zeros_like(re)
+            _lib.check(_lib.lib().pd_vr_stft_ragged(h, _lib.fptr(rows), _lib.iptr(ld), _lib.fptr(re), _lib.fptr(im), R, L,
+                                                    T, _lib.stream_ptr(rows.device)))
+            return re, im
         re = torch.empty(R, T, self.output_bin, device=rows.device, dtype=torch.float32)
         im = torch.empty_like(re)
         _lib.check(_lib.lib().pd_vr_stft(h, _lib.fptr(rows), _lib.fptr(re), _lib.fptr(im), R, L, lead, T,
                                          _lib.stream_ptr(rows.device)))
         return re, im
 
-    def _mask(self, re, im, B):
+    def _mask(self, re, im, B, frames=None):
+        """``frames`` (B host ints, positive multiples of 32 up to T): a ragged batch (pd_vr_mask_ragged); the
+        mask past a row's frames is unspecified."""
         h = self.handle()
         R, T, F = re.shape
         if R != B * self.channels or F != self.output_bin:
@@ -131,16 +160,34 @@ class CascadedNet(nn.Module):
         L = _lib.lib()
         mre, mim = torch.empty_like(re), torch.empty_like(im)
         ws, wsb = self._ws.get(L.pd_vr_workspace_size(h, B, (T - 32) * self.hop_length), re.device)
+        if frames is not None:
+            if torch.is_tensor(frames) and frames.is_cuda:
+                raise _lib.HipError("CascadedNet: `frames` must be host integers")
+            host = [int(v) for v in (frames.tolist() if torch.is_tensor(frames) else frames)]
+            if any(v % 32 != 0 for v in host):
+                raise _lib.HipError(f"frames must be positive multiples of 32, got {host}")
+            fd = _lib._device_rows(host, B, re.device, "frames", 32, T)
+            _lib.check(L.pd_vr_mask_ragged(h, _lib.fptr(re), _lib.fptr(im), _lib.iptr(fd), _lib.fptr(mre), _lib.fptr(mim),
+                                           B, T, ws, wsb, _lib.stream_ptr(re.device)))
+            return mre, mim
         _lib.check(L.pd_vr_mask(h, _lib.fptr(re), _lib.fptr(im), _lib.fptr(mre), _lib.fptr(mim), B, T, ws, wsb,
                                 _lib.stream_ptr(re.device)))
         return mre, mim
 
-    def _istft(self, re, im, mre, mim, lead, L_out, wav=None):
-        """-> y [R, L_out] (and wav - y when ``wav`` [R, L_out] is given, from the same epilogue)."""
+    def _istft(self, re, im, mre, mim, lead, L_out, wav=None, lens=None):
+        """-> y [R, L_out] (and wav - y when ``wav`` [R, L_out] is given, from the same epilogue).  ``lens``
+        (R host ints): a ragged batch (pd_vr_istft_ragged) -- row r's first lens[r] samples from its own frames and
+        lead (``lead`` is not used), zeros from there to L_out."""
         h = self.handle()
         R, T, _ = re.shape
         y = torch.empty(R, L_out, device=re.device, dtype=torch.float32)
         resid = torch.empty_like(y) if wav is not None else None
+        if lens is not None:
+            _, ld = self._lens(lens, R, L_out, re.device)
+            _lib.check(_lib.lib().pd_vr_istft_ragged(h, _lib.fptr(re), _lib.fptr(im), _lib.fptr(mre), _lib.fptr(mim),
+                                                     _lib.fptr(wav), _lib.iptr(ld), _lib.fptr(y), _lib.fptr(resid), R, T,
+                                                     L_out, _lib.stream_ptr(re.device)))
+            return (y, resid) if wav is not None else y
         _lib.check(_lib.lib().pd_vr_istft(h, _lib.fptr(re), _lib.fptr(im), _lib.fptr(mre), _lib.fptr(mim), _lib.fptr(wav),
                                           _lib.fptr(y), _lib.fptr(resid), R, T, lead, L_out, _lib.stream_ptr(re.device)))
         return (y, resid) if wav is not None else y
@@ -189,21 +236,28 @@ class CascadedNet(nn.Module):
         return self._istft(re, im, None, None, self.n_fft // 2, (T - 1) * self.hop_length).reshape(B, Cn, -1)
 
     @torch.no_grad()
-    def separate(self, wav):
-        """[B, C, L] -> (harmonic, aperiodic = wav - harmonic), both [B, C, L], in one pd_vr_separate call."""
+    def separate(self, wav, lens=None):
+        """[B, C, L] -> (harmonic, aperiodic = wav - harmonic), both [B, C, L], in one pd_vr_separate call.
+        ``lens`` (B host ints in [1, L]): a ragged batch (pd_vr_separate_ragged) -- row b's first lens[b] samples
+        equal, bit for bit, that clip run alone; what ``wav`` holds past them is not used, the outputs there are 0."""
         x = self._check_wav(wav)
         B, Cn, L = x.shape
         h = self.handle()
         lib = _lib.lib()
+        ld = None if lens is None else self._lens(lens, B, L, x.device)[1]
         y, ap = torch.empty_like(x), torch.empty_like(x)
         ws, wsb = self._ws.get(lib.pd_vr_workspace_size(h, B, L), x.device)
+        if ld is not None:
+            _lib.check(lib.pd_vr_separate_ragged(h, _lib.fptr(x), _lib.iptr(ld), _lib.fptr(y), _lib.fptr(ap), B, L, ws,
+                                                 wsb, _lib.stream_ptr(x.device)))
+            return y, ap
         _lib.check(lib.pd_vr_separate(h, _lib.fptr(x), _lib.fptr(y), _lib.fptr(ap), B, L, ws, wsb,
                                       _lib.stream_ptr(x.device)))
         return y, ap
 
-    def predict_from_audio(self, x):
-        """nets.py:175-197: [B, C, L] -> the harmonic part [B, C, L]."""
-        return self.separate(x)[0]
+    def predict_from_audio(self, x, lens=None):
+        """nets.py:175-197: [B, C, L] -> the harmonic part [B, C, L]; ``lens``: a ragged batch (``separate``)."""
+        return self.separate(x, lens)[0]
 
 
 def load_sep_model(model_path, device="cuda"):
@@ -224,7 +278,8 @@ SEP_MODEL = None
 def extract_harmonic_aperiodic(waveform, model_path=None, device="cuda"):
     """component/binarizer/binarizer_utils.py:99-113: a mono waveform (numpy [L]) -> (harmonic, aperiodic) numpy [L].  The model is
     loaded on the first call and kept at module level, as in the reference; ``model_path`` may also be a
-    ``CascadedNet``."""
+    ``CascadedNet``.  A list or tuple of mono waveforms of different lengths goes through one ragged
+    ``separate`` call and gives a list of (harmonic, aperiodic), each pair what its clip gives alone."""
     global SEP_MODEL
     if isinstance(model_path, CascadedNet):
         model = model_path
@@ -233,6 +288,19 @@ def extract_harmonic_aperiodic(waveform, model_path=None, device="cuda"):
             SEP_MODEL = load_sep_model(model_path, device)
         model = SEP_MODEL
     dev = next(model.parameters()).device
+    if isinstance(waveform, (list, tuple)):
+        audio, lens = stack_waveforms(waveform, None, dev)
+        x = audio[:, None]
+        y, ap = model.separate(x if model.is_mono else x.repeat(1, 2, 1), lens)
+        out = []
+        for b, n in enumerate(lens):
+            if model.is_mono:
+                harmonic, aperiodic = y[b, 0, :n], ap[b, 0, :n]
+            else:
+                harmonic = y[b, :, :n].mean(dim=0)
+                aperiodic = audio[b, :n] - harmonic
+            out.append((harmonic.cpu().numpy(), aperiodic.cpu().numpy()))
+        return out
     wav = torch.from_numpy(np.asarray(waveform, dtype=np.float32)).to(dev)
     x = wav[None, None]
     if not model.is_mono:

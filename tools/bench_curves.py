@@ -8,6 +8,12 @@ reference interpolates with numpy on the host; that host trip is left out of its
 from pd_profile_*.  Fails without a GPU.  Prints one JSON line per batch size.
 
     python tools/bench_curves.py [--calls 20] [--rounds 3] [--warmup 3] [--batches 1,8] [--seconds 10]
+    python tools/bench_curves.py --ragged N [--calls 20]
+
+--ragged N times the fused ``VarianceCurves`` call on clips of the first N lengths of tests/golden/ds_lengths.json
+(frames times the hop, in samples) three ways: (a) one ragged call on the padded batch with ``lens`` and
+``f0_lens``, (b) one call per clip (the only way without ragged batches), (c) one equal-length call on the clips
+padded to the longest (its results are not those of the clips alone).  (a) is checked bit-equal to (b) first.
 """
 import argparse
 import json
@@ -97,8 +103,56 @@ def torch_curves(sp, ap, f0i, window, taps, mel_len):
     return voicing, breath, tension
 
 
+def bench_ragged(a):
+    dev = torch.device("cuda:0")
+    with open(os.path.join(ROOT, "tests", "golden", "ds_lengths.json")) as f:
+        ds = json.load(f)
+    sr, hop = int(ds["sr"]), int(ds["hop"])
+    frames = [int(v) for v in ds["frames"][:a.ragged]]
+    if len(frames) < a.ragged:
+        raise SystemExit(f"ds_lengths.json holds {len(frames)} lengths")
+    lens = [n * hop for n in frames]
+    mels = [CV.num_frames(n, HOP) for n in lens]
+    vc = prodiff_amd.VarianceCurves(SR, WIN, HOP)
+    rng = np.random.default_rng(0)
+    f0s = [CC._contour(m, 200.0 + 5.0 * b, rng, SR, HOP) for b, m in enumerate(mels)]
+    for f in f0s:
+        f[5:9] = 0
+    sps = [torch.from_numpy(CC._stack(CC.interp_f0(f.copy()), n, SR, HOP, rng)).to(dev) for f, n in zip(f0s, lens)]
+    aps = [torch.from_numpy((0.05 * rng.standard_normal(n)).astype(np.float32)).to(dev) for n in lens]
+    f0s = [torch.from_numpy(f).to(dev) for f in f0s]
+    sp, ap, f0 = (torch.zeros(len(lens), max(w), device=dev) for w in (lens, lens, mels))
+    for b in range(len(lens)):
+        sp[b, :lens[b]], ap[b, :lens[b]], f0[b, :mels[b]] = sps[b], aps[b], f0s[b]
+
+    def ragged():
+        return vc.core.forward(sp, ap, f0, mels, vc.smooth, lens=lens, f0_lens=mels)[:3]
+
+    def one_by_one():
+        return [vc.core.forward(s, p, f, m, vc.smooth)[:3] for s, p, f, m in zip(sps, aps, f0s, mels)]
+
+    def padded_call():
+        return vc.core.forward(sp, ap, f0, max(mels), vc.smooth)[:3]
+
+    with torch.no_grad():
+        out = ragged()
+        same = all(torch.equal(got[b, :m], want) for b, (m, r) in enumerate(zip(mels, one_by_one()))
+                   for got, want in zip(out, r))
+        line = {"bench": "curves_ragged", "N": len(lens), "seconds": [round(n / sr, 2) for n in lens], "calls": a.calls,
+                "device": torch.cuda.get_device_name(0), "lib": _lib.lib().pd_build_config().decode(),
+                "ragged_equals_single_calls": bool(same)}
+        for key, fn in (("ragged", ragged), ("single_calls", one_by_one), ("padded", padded_call)):
+            for _ in range(a.warmup):
+                fn()
+            torch.cuda.synchronize()
+            line[key + "_ms"] = stats(time_calls(fn, a.calls))
+    print(json.dumps(line), flush=True)
+    vc.close()
+
+
 def main():
     ap_ = argparse.ArgumentParser()
+    ap_.add_argument("--ragged", type=int, default=0, metavar="N")
     ap_.add_argument("--calls", type=int, default=20)
     ap_.add_argument("--rounds", type=int, default=3)
     ap_.add_argument("--warmup", type=int, default=3)
@@ -107,6 +161,8 @@ def main():
     a = ap_.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_curves: no GPU found")
+    if a.ragged:
+        return bench_ragged(a)
     dev = torch.device("cuda:0")
     L = int(round(a.seconds * SR))
     T = CV.num_frames(L, HOP)

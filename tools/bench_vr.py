@@ -7,6 +7,12 @@ written with torch ops (torch.stft, F.conv2d, F.batch_norm, F.interpolate, nn.LS
 the same GPU.  Prints one JSON line per batch size.
 
     python tools/bench_vr.py [--calls 20] [--warmup 3] [--batches 1,8] [--seconds 10] [--no-torch]
+    python tools/bench_vr.py --ragged N [--calls 20]
+
+--ragged N times ``CascadedNet.separate`` on clips of the first N lengths of tests/golden/ds_lengths.json (frames
+times the hop, in samples) three ways: (a) one ragged call on the padded batch with ``lens``, (b) one call per clip
+(the only way without ragged batches), (c) one equal-length call on the clips padded to the longest (its results
+are not those of the clips alone).  (a) is checked bit-equal to (b) first.
 
 The conv floor: 2 x output pixels x taps C_in C_out FLOP per conv on the f32 MFMA (157.3 TFLOP/s dense).
 """
@@ -119,8 +125,52 @@ def torch_separate(P, lstms, a, wav):
     return y[:, Tl_pad:Tl_pad + L].reshape(B, C, L)
 
 
+def bench_ragged(a):
+    dev = torch.device("cuda:0")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "tests", "golden", "ds_lengths.json")) as f:
+        ds = json.load(f)
+    sr, hop = int(ds["sr"]), int(ds["hop"])
+    frames = [int(v) for v in ds["frames"][:a.ragged]]
+    if len(frames) < a.ragged:
+        raise SystemExit(f"ds_lengths.json holds {len(frames)} lengths")
+    lens = [n * hop for n in frames]
+    net = prodiff_amd.CascadedNet(**FULL)
+    shapes = synth.vr_param_shapes(FULL["n_fft"], FULL["nout"], FULL["nout_lstm"], FULL["is_mono"])
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_vr_params(shapes, a.seed).items()})
+    net.to(dev)
+    g = torch.Generator().manual_seed(0)
+    clips = [((torch.rand(n, generator=g) * 2 - 1) * 0.3).to(dev)[None, None] for n in lens]
+    padded = torch.zeros(len(clips), 1, max(lens), device=dev)
+    for b, c in enumerate(clips):
+        padded[b, :, :c.shape[-1]] = c[0]
+
+    def ragged():
+        return net.separate(padded, lens)
+
+    def one_by_one():
+        return [net.separate(c) for c in clips]
+
+    def padded_call():
+        return net.separate(padded)
+
+    y, ap_ = ragged()
+    same = all(torch.equal(y[b, :, :n], r[0][0]) and torch.equal(ap_[b, :, :n], r[1][0])
+               for b, (n, r) in enumerate(zip(lens, one_by_one())))
+    line = {"bench": "vr_ragged", "N": len(lens), "seconds": [round(n / sr, 2) for n in lens],
+            "frames": [padded_frames(n, FULL["hop_length"])[0] for n in lens], "calls": a.calls,
+            "device": torch.cuda.get_device_name(0), "lib": _lib.lib().pd_build_config().decode(),
+            "ragged_equals_single_calls": bool(same)}
+    for key, fn in (("ragged", ragged), ("single_calls", one_by_one), ("padded", padded_call)):
+        med, best, p90 = time_calls(fn, a.calls, a.warmup)
+        line[key + "_ms"] = {"median": round(med, 3), "min": round(best, 3), "p90": round(p90, 3)}
+    print(json.dumps(line), flush=True)
+    net.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", type=int, default=0, metavar="N")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batches", default="1,8")
@@ -128,6 +178,8 @@ def main():
     ap.add_argument("--seed", type=int, default=54)
     ap.add_argument("--no-torch", action="store_true")
     a = ap.parse_args()
+    if a.ragged:
+        return bench_ragged(a)
     dev = torch.device("cuda:0")
     Lw = int(round(a.seconds * 44100))
     shapes = synth.vr_param_shapes(FULL["n_fft"], FULL["nout"], FULL["nout_lstm"], FULL["is_mono"])
