@@ -95,10 +95,10 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
 void pd_wavenet_destroy(pd_wavenet* h);
 /* Kernel-variant option of a handle; set before its first call.  PD_WN_OPT_LAYER selects the
  * bf16 residual-layer implementation: 0 the fused kernel with 32-frame blocks, 3 the fused
- * kernel with 64-frame blocks, 1 two launches per layer (GATE: 128 frames x 64 gated channels
- * per block, activation window staged once; RESSKIP: 64 frames x 128 outputs), 2 (default)
- * 64-frame fused blocks when they still give every CU a block (B*T >= 16384 frames) else 32.
- * DESIGN.md §4 has the measurements. */
+ * kernel with 64-frame blocks, 2 (default) 64-frame fused blocks when they still give every CU a
+ * block (B*T >= 16384 frames) else 32.  DESIGN.md §4 has the measurements.
+ * 1: reserved (r02's two launches per layer, GATE + RESSKIP kernels, removed: measured slower,
+ * DESIGN.md §4) -- PD_ERR_ARG. */
 #define PD_WN_OPT_LAYER 0
 /* PD_WN_OPT_KSPLIT (fp32 path): the residual-layer GEMMs split their K range over several blocks
  * until the grid holds 512 (default) or 256 blocks; 0 = never split. */
@@ -144,7 +144,7 @@ int pd_wavenet_forward(const pd_wavenet* h, const float* spec, const float* step
  * equal a run of that utterance alone (B = 1, T = lens[b]), the reference's one-segment-at-a-time
  * inference (handler/infer/handler.py:373-388).  Outputs in the padding are unspecified.  With the
  * on-device draws below, the draws of an utterance's frames are the same padded or alone.  A few
- * A/B kernel variants do not take lens (PD_WN_OPT_LAYER 1, FD_OPT_LVC_TS 0, FD_OPT_KP_SIDE, FD_OPT_KP_CHUNK)
+ * A/B kernel variants do not take lens (FD_OPT_LVC_TS 0, FD_OPT_KP_CHUNK)
  * and return PD_ERR_UNSUPPORTED. */
 /* Random draws (every sampler below).  When the caller passes no explicit draws they come
  * from an on-device Philox4x32-10 generator keyed by (seed, utterance id, element index
@@ -241,12 +241,15 @@ size_t fd_workspace_size(const fd_model* m, int B, int Tc, int S);
 /* Kernel-variant options of a handle (bf16 LVC-block tiling and fusions).  The defaults are
  * the measured production configuration; the tests select each variant.
  * Set them before the handle's first forward/sample call; not thread-safe against calls. */
-#define FD_OPT_LVC_TS 0       /* whole-block LVC tile, hop >= 32: 384 (default), 256, 128; 0 = per-layer launches */
-#define FD_OPT_LVC_TS_SUB 1   /* whole-block LVC tile of the hop < 32 block: 256 (default), 128, 384 */
+#define FD_OPT_LVC_TS 0       /* whole-block LVC tile, hop >= 32: 384 (default), 256, 128 (the hop < 32 block: 256);
+                               * 0 = per-layer launches */
+/* 1: reserved (FD_OPT_LVC_TS_SUB, the hop < 32 block's 128 / 384 tiles, removed: measured slower, r03 A/B at
+ * fastdiff.hip's fd_model) */
 #define FD_OPT_LVC_FUSE 2     /* 1: upsample / first conv / sampler update fused into the LVC blocks */
 #define FD_OPT_LVC_PF 3       /* 1: next-layer kernel fragments prefetched into registers (tile 384) */
 #define FD_OPT_LVC_SUB 4      /* 1: the hop < 32 block on the whole-block kernel too */
-#define FD_OPT_KP_SIDE 5      /* 1: kernel-predictor GEMMs of fd_sample on a low-priority side stream */
+/* 5: reserved (FD_OPT_KP_SIDE, fd_sample's kernel-predictor GEMMs on a low-priority side stream, removed:
+ * measured slower, r01 ab_v16b 7.41 vs 7.33 ms/step) */
 /* 6: reserved (r02's streaming LVC kernel, removed in r03: measured slower) */
 #define FD_OPT_KP_CHUNK 7     /* n > 0: kernel predictor + LVC block per chunk of n utterances (default 0 = whole batch) */
 /* 8, 9: reserved (r03's skewed persistent LVC kernel, removed: measured slower) */

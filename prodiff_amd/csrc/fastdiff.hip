@@ -52,22 +52,16 @@ struct fd_model {
   int ratios[4];
   int hops[4];
   int dtype;
-  // Whole-block LVC tile per block kind (measured, r01_ab4): 384 output samples with the
-  // next-layer kernel prefetch (8 waves, 1 block/CU, 256 VGPRs) for hop >= 32; 128 for the
-  // hop-8 block, whose tiles span several frames (no prefetch).  lvc_ts = 0 selects one
+  // Whole-block LVC tile per block kind: 384 output samples with the next-layer kernel prefetch
+  // (8 waves, 1 block/CU, 256 VGPRs) for hop >= 32 (measured, r01_ab4); 256 for the hop-8 block,
+  // whose tiles span several frames (no prefetch; r03 A/B with plain K stores 105 us vs 112 at 128
+  // and 121 at 384: those two are no longer built).  lvc_ts = 0 selects one
   // fused launch per layer.  Every field below is an fd_set_option (FD_OPT_*) with these
   // measured defaults; the tests use the options to cover each variant.
   int lvc_ts = 384;
-  int lvc_ts_sub = 256;        // hop < 32 (hop-8) block tile: r03 A/B with plain K stores 105 vs 112 us (128), 121 (384)
   bool lvc_fuse = true;        // upsample / first conv / final update fused into the LVC block (FD_OPT_LVC_FUSE)
   bool lvc_pf = true;          // next-layer kernel fragments prefetched into registers (FD_OPT_LVC_PF)
   bool lvc_sub = true;         // hop < 32 blocks (hop 8) on the whole-block kernel too (FD_OPT_LVC_SUB)
-  // fd_sample (bf16): the kernel-predictor GEMMs run on a second, low-priority stream into a
-  // ring of one K buffer per block, so step j+1's kernels for block n are written while
-  // step j's later blocks run (FD_OPT_KP_SIDE).  Created on first use.  Off by default:
-  // the two streams share the CUs, so each kernel slows down by about the time the overlap
-  // saves (r01 ab_v16b: 7.41 vs 7.33 ms/step).
-  bool kp_side = false;
   int kp_chunk = 0;   // FD_OPT_KP_CHUNK: utterances per kernel-predictor -> LVC chunk (0 = whole batch)
   int lvc_tpw = 2;    // FD_OPT_LVC_TPW: 32-row tiles per wave of the 384-sample hop >= 32 blocks (2 or 1)
   int lvc_prio = 0;   // FD_OPT_LVC_PRIO: 1 = s_setprio(1) for the second half of an LVC block's waves
@@ -75,8 +69,6 @@ struct fd_model {
   int lvc_carry = 1;  // FD_OPT_LVC_CARRY: the persistent blocks walk runs of tiles and carry the left halo
   int lvc_ps_grid = 0;   // FD_OPT_LVC_PS_GRID: cap of the persistent grid (0 = one block per CU)
 
-  mutable hipStream_t side = nullptr;
-  mutable hipEvent_t ev_hidden = nullptr, ev_kp[4] = {}, ev_lvc[4] = {};
   WeightPool weights;          // every float* below points into it; bf16() is set for PD_DTYPE_BF16
   DevBuf kps;                  // the blocks' pre-scaled kernel-predictor weights (kks_w, kks_b)
   // step MLP
@@ -99,18 +91,6 @@ struct fd_model {
     float *c0_w, *c0_b, *c1_w, *c1_b;   // [32][96]
     float *c2_w, *c2_b;                 // [32][96 + 32] : conv.2 taps ++ residual_dense
   } dn[4];
-
-  ~fd_model() {   // the side stream and its events exist once a sampler call has used them
-    if (side) {
-      (void)hipStreamSynchronize(side);
-      (void)hipStreamDestroy(side);
-    }
-    if (ev_hidden) (void)hipEventDestroy(ev_hidden);
-    for (int n = 0; n < 4; ++n) {
-      if (ev_kp[n]) (void)hipEventDestroy(ev_kp[n]);
-      if (ev_lvc[n]) (void)hipEventDestroy(ev_lvc[n]);
-    }
-  }
 };
 
 namespace {
@@ -2208,34 +2188,21 @@ __global__ __launch_bounds__(256) void kp_hidden_bf16_kernel(const KPArgs A) {
 // the work dealt as equal runs of 32-frame tiles (C3's 128-frame items fall 10 or 11 per block): 85-87
 // vs 84-85 us; the same as two 4-wave blocks per CU, each with its own barrier phase: 86-87 us.
 constexpr int KP_F = 128, KP_NG = 512, KP_LDH = 200;   // 400-B LDS rows: conflict-free b128 reads
-// Output transpose tile.  KP_SWZ 0 (default): 32 frames x (64 + 8 pad) bf16 rows (144 B: 16-B aligned
-// for the b128 reads; 68 measured 15% slower).  KP_SWZ 1 (r05 A/B): unpadded 128-B rows with an XOR
-// swizzle -- at 256 VGPRs the per-slot addresses spill (51 registers) unless KP_STAGGER is off: 8-B slot s
-// of frame row r lives at slot s ^ kp_swz(r), kp_swz(r) = 2 (r & 7) + ((r >> 3) & 1).  The epilogue's
-// ds_write_b64 (16 lanes = 16 frame rows at one slot) then hits 16 distinct slots -- the 144-B padded
-// rows of r02-r04 put rows r and r + 8 on one bank pair (2-way, the SQ pass's 1.62 conflict cycles per
-// LDS instruction) -- and the store side's ds_read_b128 (16-B chunk c of row r at chunk c ^ (r & 7),
-// halves swapped when (r >> 3) & 1) covers all 64 banks in every lane group.
-#ifndef KP_SWZ
-#define KP_SWZ 0
-#endif
-constexpr int KP_LDO = KP_SWZ ? 64 : 72;
-__device__ __forceinline__ int kp_swz(int r) { return KP_SWZ ? 2 * (r & 7) + ((r >> 3) & 1) : 0; }
+// Output transpose tile: 32 frames x (64 + 8 pad) bf16 rows (144 B: 16-B aligned for the b128 reads; 68
+// measured 15% slower).  Rows r and r + 8 share a bank pair (2-way, the SQ pass's 1.62 conflict cycles per
+// LDS instruction); r05's conflict-free alternative, unpadded 128-B rows with an XOR swizzle, measured no
+// faster and was removed, as was running waves 4..7 one frame tile behind on their epilogues (off 5.68 vs on
+// 5.72-5.76 ms/step, kp 103 vs 107 us: profiles/r05_ab/kp_stagger_swz_ab.txt).
+constexpr int KP_LDO = 72;
 constexpr int KP_NGROUPS = NLY * KPERLAYER / KP_NG;    // 48
 constexpr int KP_THREADS = 512;
-#ifndef KP_STAGGER
-#define KP_STAGGER 0   // r05 same-box ABAB: off 5.68 vs on 5.72-5.76 ms/step, kp 103 vs 107 us (profiles/r05_ab/kp_stagger_swz_ab.txt)
-#endif
-#ifndef KP_AUX
-#define KP_AUX 0   // plain K stores: the lines stay on-die for the LVC block that reads them next (r03 A/B: non-temporal (2) made kp ~4% and the next LVC launch ~4% slower)
-#endif
 __global__ __launch_bounds__(KP_THREADS, 1) void kp_kernel_bf16_kernel(const __bf16* __restrict__ hin,
                                                                        const __bf16* __restrict__ W,
                                                                        const float* __restrict__ bias,
                                                                        __bf16* __restrict__ Kf, int Tc, int rows,
                                                                        int nfg) {
   __shared__ __attribute__((aligned(16))) __bf16 Hs[2][KP_F * KP_LDH];
-  __shared__ __attribute__((aligned(16))) __bf16 Ot[8][32 * KP_LDO];   // swizzled (kp_swz)
+  __shared__ __attribute__((aligned(16))) __bf16 Ot[8][32 * KP_LDO];
   __shared__ __attribute__((aligned(16))) float Bq[8][64];   // wave-private: its rows' biases
   const int tid = threadIdx.x, lane = tid & 63, r32 = lane & 31, h = lane >> 5;
   // wave-uniform, and provably so: the K-store descriptor is built from it (a descriptor hipcc
@@ -2335,13 +2302,12 @@ __global__ __launch_bounds__(KP_THREADS, 1) void kp_kernel_bf16_kernel(const __b
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[12 + kk], hb, acc[1], 0, 0, 0);
       }
     };
-    const int swz = kp_swz(r32);
     auto epi = [&](int ft, const f32x16 (&acc)[2]) {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int g = 0; g < 4; ++g)   // 8-B slot 8j + 2g + h of frame row r32 (swizzled: KP_SWZ)
-          *reinterpret_cast<bf16x4*>(&ot[r32 * KP_LDO + 4 * (KP_SWZ ? (8 * j + 2 * g + h) ^ swz : 8 * j + 2 * g + h)]) =
+        for (int g = 0; g < 4; ++g)   // 8-B slot 8j + 2g + h of frame row r32
+          *reinterpret_cast<bf16x4*>(&ot[r32 * KP_LDO + 4 * (8 * j + 2 * g + h)]) =
               bf16x4{(__bf16)acc[j][4 * g], (__bf16)acc[j][4 * g + 1], (__bf16)acc[j][4 * g + 2], (__bf16)acc[j][4 * g + 3]};
       __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS writes landed (wave-private tile)
       __builtin_amdgcn_wave_barrier();
@@ -2349,36 +2315,20 @@ __global__ __launch_bounds__(KP_THREADS, 1) void kp_kernel_bf16_kernel(const __b
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int fl = i * 8 + (lane >> 3), ch = (lane & 7) * 8;
-        // chunk (lane & 7) of row fl sits at chunk (lane & 7) ^ (fl & 7), its halves swapped when
-        // (fl >> 3) & 1 = i & 1 (compile-time here)
-        uint4 v = *reinterpret_cast<const uint4*>(&ot[fl * KP_LDO + 8 * (KP_SWZ ? (lane & 7) ^ (lane >> 3) : lane & 7)]);
-        if (KP_SWZ && (i & 1)) v = make_uint4(v.z, v.w, v.x, v.y);
-        // 340 MB per launch, read back by the next launch
+        const uint4 v = *reinterpret_cast<const uint4*>(&ot[fl * KP_LDO + 8 * (lane & 7)]);
+        // 340 MB per launch, read back by the next launch: plain stores, so the lines stay on-die for the LVC
+        // block that reads them (r03 A/B: non-temporal made kp ~4% and the next LVC launch ~4% slower)
         __builtin_amdgcn_raw_buffer_store_b128(u32x4_{v.x, v.y, v.z, v.w}, kout,
-                                               ((f0 + fl) * KPERLAYER + n0 + ch) * 2, 0, KP_AUX);
+                                               ((f0 + fl) * KPERLAYER + n0 + ch) * 2, 0, 0);
       }
       __builtin_amdgcn_wave_barrier();      // the next frame tile rewrites ot
     };
-    // (unrolled: hipcc counts the stores in vmcnt.)  Waves 4..7 -- each one's SIMD partner is
-    // wave - 4 -- run one frame tile behind on their epilogues (KP_STAGGER): a tile's
-    // conversion, LDS transpose and stores then issue beside the partner's MFMAs instead of in
-    // the same phase (MI355X_MICROARCH.md "Two waves per SIMD", item 9).
-    f32x16 acc0[2], acc1[2];
-    if (!KP_STAGGER || wave < 4) {
+    // (unrolled: hipcc counts the stores in vmcnt.)
+    f32x16 acc0[2];
 #pragma unroll
-      for (int ft = 0; ft < KP_F / 32; ++ft) {
-        mma(ft, acc0);
-        epi(ft, acc0);
-      }
-    } else {
-      mma(0, acc0);
-#pragma unroll
-      for (int ft = 1; ft < KP_F / 32; ++ft) {
-        if (ft & 1) { mma(ft, acc1); epi(ft - 1, acc0); }
-        else { mma(ft, acc0); epi(ft - 1, acc1); }
-      }
-      if ((KP_F / 32 - 1) & 1) epi(KP_F / 32 - 1, acc1);
-      else epi(KP_F / 32 - 1, acc0);
+    for (int ft = 0; ft < KP_F / 32; ++ft) {
+      mma(ft, acc0);
+      epi(ft, acc0);
     }
     // the next item's frames into the other buffer, whose readers (the previous item) are
     // past the last barrier; the barrier makes them visible
@@ -2512,13 +2462,6 @@ __global__ void pack_final_kernel(float* dst, const float* src) {
 bool fd_block_fused(const fd_model* m, int n) {
   return m->weights.bf16() && m->lvc_ts > 0 && (m->hops[n] % 32 == 0 || (32 % m->hops[n] == 0 && m->lvc_sub));
 }
-// Kernel predictor on the side stream (fd_sample): every block on the whole-block kernel.
-bool fd_kp_side(const fd_model* m) {
-  if (!m->kp_side || !m->weights.bf16()) return false;
-  for (int n = 0; n < m->nblocks; ++n)
-    if (!fd_block_fused(m, n)) return false;
-  return true;
-}
 
 struct FdWs {
   size_t steps, e128, e512a, e512, nz;  // step MLP (nvec = S*B)
@@ -2556,8 +2499,8 @@ FdWs fd_layout(const fd_model* m, int B, int Tc, int S) {
   // bf16 path: kernel-predictor hidden outputs of every (step, block), one batched launch
   w.hall = take((size_t)S * m->nblocks * B * Tc * HK);
   w.bfall = take((size_t)S * m->nblocks * B * Tc * 2 * CI * NLY);
-  // fp32: one layer; bf16: all 4 layers (one block's worth per block with the side stream)
-  w.Kf = take((size_t)B * Tc * KPERLAYER * 2 * (fd_kp_side(m) ? m->nblocks : 1));
+  // fp32: one layer; bf16: all 4 layers
+  w.Kf = take((size_t)B * Tc * KPERLAYER * 2);
   w.condT = take((size_t)B * Tc * CC);
   w.total = off * sizeof(float);
   return w;
@@ -2660,7 +2603,6 @@ struct FdCall {
   const float* xa;       // audio [B][L]
   bool aud;              // a0 = first_conv(audio) is recomputed by its consumers (fd_final_fused), never stored
   const FdFinal* fin;    // the sampler update for the last block to apply, or null
-  bool side;             // the kernel predictor runs on the side stream (fd_sample)
 };
 
 // One LVC block's place in the network: x [B][Tin][32] -> [B][Tout = Tin r][32], written to xn; ad: audio_down
@@ -2698,11 +2640,11 @@ int launch_lvc_ps(const fd_model* m, const LvcBlockArgs& la, bool fin, long long
 }
 
 // One whole-block LVC launch over B utterances of Tout rows: the persistent kernel, one tile per wave
-// (FD_OPT_LVC_TPW 1) or the TS-row tiles, with the block's fusions -- ups: the upsample, aud: a = first_conv
-// (audio) recomputed (the last block), fin: the final conv and the sampler update.
+// (FD_OPT_LVC_TPW 1) or the TS-row tiles (hop < 32: 256 rows), with the block's fusions -- ups: the
+// upsample, aud: a = first_conv(audio) recomputed (the last block), fin: the final conv and the sampler update.
 int launch_lvc_block(const fd_model* m, const LvcBlockArgs& la, bool ups, bool aud, bool fin, long long Tout, int B,
                      hipStream_t st) {
-  const int hop = la.hop, ts = hop < 32 ? m->lvc_ts_sub : m->lvc_ts;
+  const int hop = la.hop, ts = m->lvc_ts;
   const bool pf = m->lvc_pf && hop % 64 == 0;   // a 64-row tile pair shares one frame
   const bool ps_fin = fin && la.r == 4 && hop % 256 == 0;
   const bool ps_ups = ups && !fin && !aud && la.a && la.r == 8 && hop % 64 == 0;
@@ -2721,17 +2663,22 @@ int launch_lvc_block(const fd_model* m, const LvcBlockArgs& la, bool ups, bool a
   if (sub && (aud || fin)) { set_error("lvc_block: audio/final fusion needs hop >= 32"); return PD_ERR_ARG; }
   if (!ups && (aud || fin)) { set_error("lvc_block: audio/final fusion needs the fused upsample"); return PD_ERR_ARG; }
   if (fin && !aud) { set_error("lvc_block: final fusion needs the audio fusion"); return PD_ERR_ARG; }
-  // two tiles per wave: the (UPS, AUD, FIN, PF, SUB) instantiated for every tile size (a tile size that is
-  // neither 256 nor 384 runs as 128).  The register prefetch (PF) exists beside the fused upsample without the
-  // audio fusion or with both fusions; the checks above leave no other combination.
+  // two tiles per wave: the (UPS, AUD, FIN, PF, SUB) instantiated -- the hop < 32 (SUB) rows at 256-row tiles, the
+  // others for every tile size (a tile size that is neither 256 nor 384 runs as 128).  The register prefetch (PF)
+  // exists beside the fused upsample without the audio fusion or with both fusions; the checks above leave no
+  // other combination.
   const bool pfk = pf && !sub && ups && aud == fin;
-  dispatch([&](auto TS) {
-    dispatch_rows<DispatchRow<false, false, false, false, true>, DispatchRow<true, false, false, false, true>,
-                  DispatchRow<false, false, false, false, false>, DispatchRow<true, false, false, false, false>,
-                  DispatchRow<true, false, false, true, false>, DispatchRow<true, true, false, false, false>,
-                  DispatchRow<true, true, true, false, false>, DispatchRow<true, true, true, true, false>>(
-        [&](auto... cs) { go(TS, cs..., Const<2>{}); }, ups, aud, fin, pfk, sub);
-  }, one_of<128, 256, 384>(ts == 256 || ts == 384 ? ts : 128));
+  if (sub) {
+    dispatch_rows<DispatchRow<false, false, false, false, true>, DispatchRow<true, false, false, false, true>>(
+        [&](auto... cs) { go(Const<256>{}, cs..., Const<2>{}); }, ups, aud, fin, pfk, sub);
+  } else {
+    dispatch([&](auto TS) {
+      dispatch_rows<DispatchRow<false, false, false, false, false>, DispatchRow<true, false, false, false, false>,
+                    DispatchRow<true, false, false, true, false>, DispatchRow<true, true, false, false, false>,
+                    DispatchRow<true, true, true, false, false>, DispatchRow<true, true, true, true, false>>(
+          [&](auto... cs) { go(TS, cs..., Const<2>{}); }, ups, aud, fin, pfk, sub);
+    }, one_of<128, 256, 384>(ts == 256 || ts == 384 ? ts : 128));
+  }
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -2854,27 +2801,20 @@ int fd_block_whole(const FdCall& c, const FdBlockIo& b, const __bf16* hkb, float
   const int B = c.B, Tc = c.Tc, n = b.n;
   const bool last = n == m->nblocks - 1;
   const bool ups = m->lvc_fuse && b.r >= 4;
-  const bool fuse_fin = ups && last && c.fin != nullptr, side = c.side, aud = last && c.aud;
+  const bool fuse_fin = ups && last && c.fin != nullptr, aud = last && c.aud;
   if (!ups) PD_TRY(fd_upsample(c, b));   // separate upsample
   __bf16* Kb = reinterpret_cast<__bf16*>(c.ws + c.W.Kf);
   // FD_OPT_KP_CHUNK: kernel predictor + LVC block per chunk of utterances, so a chunk's
   // kernel tensor can still be on-die (Infinity Cache) when the LVC block reads it
-  const int cb = (!side && m->kp_chunk > 0 && m->kp_chunk < B) ? m->kp_chunk : B;
+  const int cb = (m->kp_chunk > 0 && m->kp_chunk < B) ? m->kp_chunk : B;
   for (int b0 = 0; b0 < B; b0 += cb) {
     const int nbk = B - b0 < cb ? B - b0 : cb;
-    __bf16* Kc = Kb;
-    if (side) {   // written on the side stream (fd_sample)
-      Kc += (size_t)n * nbk * Tc * NLY * KPERLAYER;
-      PD_HIP(hipStreamWaitEvent(c.st, m->ev_kp[n], 0));
-    } else {
-      PD_TRY(kp_kernels_all(K, hkb + (size_t)b0 * Tc * HK, Kc, nbk, Tc, c.st, true));
-    }
-    const LvcBlockArgs la = lvc_block_args(c, b, Kc, b0, nbk, ups, aud, fuse_fin ? c.fin : nullptr);
+    PD_TRY(kp_kernels_all(K, hkb + (size_t)b0 * Tc * HK, Kb, nbk, Tc, c.st, true));
+    const LvcBlockArgs la = lvc_block_args(c, b, Kb, b0, nbk, ups, aud, fuse_fin ? c.fin : nullptr);
     ProfScope ps(fuse_fin ? "fd_lvc_block_final" : b.hop < 32 ? "fd_lvc_block_sub" : ups ? "fd_lvc_block_ups"
                                                                                      : "fd_lvc_block", c.st);
     PD_TRY(launch_lvc_block(m, la, ups, aud, fuse_fin, b.Tout, nbk, c.st));
   }
-  if (side) PD_HIP(hipEventRecord(m->ev_lvc[n], c.st));   // ring slot n free again
   *xo = fuse_fin ? nullptr : ups ? b.xn : c.ws + c.W.y;
   return PD_OK;
 }
@@ -2942,14 +2882,14 @@ int fd_block_layers(const FdCall& c, const FdBlockIo& b, const float* hk, const 
 // the sampler update itself and sets *xout = nullptr.
 int fd_net(const fd_model* m, float* ws, const FdWs& W, const float* xa, const float* condT,
            const float* nz, int step, int B, int Tc, float** xout, hipStream_t st,
-           const FdFinal* fin = nullptr, bool side = false, const int* lens = nullptr) {
+           const FdFinal* fin = nullptr, const int* lens = nullptr) {
   const int nb = m->nblocks;
   const bool bf = m->weights.bf16() != nullptr;
   if (lens && bf && m->lvc_ts == 0) {
     set_error("FD_OPT_LVC_TS 0 (per-layer LVC launches) does not take ragged batches (lens)");
     return PD_ERR_UNSUPPORTED;
   }
-  const FdCall c{m, ws, W, B, Tc, lens, st, xa, fd_final_fused(m), fin, side};
+  const FdCall c{m, ws, W, B, Tc, lens, st, xa, fd_final_fused(m), fin};
   const float* downs[4];
   const float* x = nullptr;   // [B][Tc][32]
   PD_TRY(fd_downsample(c, downs, &x));
@@ -3134,14 +3074,9 @@ int fd_set_option(fd_model* m, int option, int value) {
       m->lvc_ts = value;
       m->lvc_pf = value >= 384;   // the register prefetch is tuned for the 384 tile
       return PD_OK;
-    case FD_OPT_LVC_TS_SUB:
-      PD_CHECK_ARG(value == 128 || value == 256 || value == 384, "FD_OPT_LVC_TS_SUB in {128,256,384}");
-      m->lvc_ts_sub = value;
-      return PD_OK;
     case FD_OPT_LVC_FUSE: m->lvc_fuse = value != 0; return PD_OK;
     case FD_OPT_LVC_PF: m->lvc_pf = value != 0; return PD_OK;
     case FD_OPT_LVC_SUB: m->lvc_sub = value != 0; return PD_OK;
-    case FD_OPT_KP_SIDE: m->kp_side = value != 0; return PD_OK;
     case FD_OPT_KP_CHUNK:
       PD_CHECK_ARG(value >= 0, "FD_OPT_KP_CHUNK >= 0");
       m->kp_chunk = value;
@@ -3231,18 +3166,7 @@ int fd_sample_coefs(const fd_model* m, const float* mel, const float* ce_, const
   } else {
     PD_TRY(fill_normal_utt(cur, B, L, seed, 0xFFFF0001u, utt_ids, st));
   }
-  const bool side = fd_kp_side(m);
-  if (side && !m->side) {
-    int lo = 0, hi = 0;
-    PD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));   // lo = least urgent
-    PD_HIP(hipStreamCreateWithPriority(&m->side, hipStreamNonBlocking, lo));
-    PD_HIP(hipEventCreateWithFlags(&m->ev_hidden, hipEventDisableTiming));
-    for (int b = 0; b < m->nblocks; ++b) {
-      PD_HIP(hipEventCreateWithFlags(&m->ev_kp[b], hipEventDisableTiming));
-      PD_HIP(hipEventCreateWithFlags(&m->ev_lvc[b], hipEventDisableTiming));
-    }
-  }
-  const int nb = m->nblocks, rows = B * Tc;
+  const int nb = m->nblocks;
   for (int j0 = 0; j0 < N; j0 += CH) {
     const int nc = N - j0 < CH ? N - j0 : CH;
     // the chunk's step embeddings at once
@@ -3251,29 +3175,15 @@ int fd_sample_coefs(const fd_model* m, const float* mel, const float* ce_, const
     PD_TRY(fill_steps(ws + W.steps, sv.data(), nc, B, st));
     PD_TRY(fd_step_mlp(m, ws, W, nc * B, st));
     if (m->weights.bf16()) PD_TRY(fd_kp_hidden_all(m, ws, W, mel, ws + W.nz, nc, B, Tc, st, lens));
-    if (side) {
-      PD_HIP(hipEventRecord(m->ev_hidden, st));
-      PD_HIP(hipStreamWaitEvent(m->side, m->ev_hidden, 0));
-    }
     for (int jl = 0; jl < nc; ++jl) {
       const int j = j0 + jl;
-      if (side) {
-        // step j's kernels for every block; slot b is rewritten once step j-1's block b has run
-        for (int b = 0; b < nb; ++b) {
-          if (j > 0) PD_HIP(hipStreamWaitEvent(m->side, m->ev_lvc[b], 0));
-          const __bf16* hkb = reinterpret_cast<const __bf16*>(ws + W.hall) + ((size_t)jl * nb + b) * rows * HK;
-          __bf16* Kb = reinterpret_cast<__bf16*>(ws + W.Kf) + (size_t)b * rows * NLY * KPERLAYER;
-          PD_TRY(kp_kernels_all(m->blk[b], hkb, Kb, B, Tc, m->side, true));
-          PD_HIP(hipEventRecord(m->ev_kp[b], m->side));
-        }
-      }
       float* x = nullptr;
       // x = (x - ce eps) / den + sg z  (pass j's coefficients, fd_sample / util.py:222-231)
       const float ce = ce_[j], den = den_[j], sg = sg_[j];
       const FdFinal fin{other, noise ? noise + (size_t)j * B * L : (const float*)nullptr, ce, den, sg, seed,
                         0x10000u + draw0 + j, utt_ids};
       PD_TRY(fd_net(m, ws, W, cur, mel, ws + W.nz + (size_t)jl * B * nb * CC, jl, B, Tc, &x, st,
-                    fused ? &fin : nullptr, side, lens));
+                    fused ? &fin : nullptr, lens));
       if (x == nullptr) {   // updated inside the last LVC block
         std::swap(cur, other);
         continue;
@@ -3328,15 +3238,6 @@ const char* fastdiff_build_flags() {
 #endif
 #if DB_WPE != 5
          " DB_WPE"
-#endif
-#if KP_STAGGER != 0
-         " KP_STAGGER"
-#endif
-#if KP_AUX != 0
-         " KP_AUX"
-#endif
-#if KP_SWZ != 0
-         " KP_SWZ"
 #endif
       ;
 }

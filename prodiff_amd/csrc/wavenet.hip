@@ -28,9 +28,8 @@ struct pd_wavenet {
   DevBuf frag;
   __bf16* W1f = nullptr;   // [L][2C/32 tiles][K/16 steps][64 lanes][8]
   __bf16* W2f = nullptr;
-  __bf16* W1p = nullptr;   // [L][C/16 pair tiles][K/16][64][8] (wn_gate_bf16_kernel)
   // bf16 residual layer (PD_WN_OPT_LAYER): 0 = fused kernel, 32 frames per block; 3 = fused, 64
-  // frames per block; 1 = GATE + RESSKIP kernels; 2 = auto between 0 and 3 by grid size
+  // frames per block; 2 = auto between 0 and 3 by grid size
   int layer_mode = 2;
   int ksplit_blocks = 512;   // PD_WN_OPT_KSPLIT: fp32 layer GEMMs split K up to this many blocks
   int l2_prefetch = 1;       // PD_WN_OPT_L2PF: fused layer l pulls layer l + 1's weights into L2
@@ -1044,318 +1043,7 @@ __global__ __launch_bounds__(512) void wn_f32_tail_kernel(const WnF32TailArgs P)
   }
 }
 
-// ------------------------------------------------------------------ two-kernel residual layer (bf16)
-// The same layer as wn_layer_bf16_kernel as two launches (wavenet.py:60-72), PD_WN_OPT_LAYER = 1:
-//   GATE     g = sigmoid(W1_g . a + b_g) * tanh(W1_f . a + b_f),  a = [xa(t-d); xa(t); xa(t+d); cond(t)]
-//   RESSKIP  o = W2 . g + b2;  x = (x + o[:C]) / sqrt2 (and xa' = bf16(x + dp of the next layer));
-//            skip (+)= o[C:]
-// Why it exists: the fused kernel holds 32 frames per block and streams all 1.3 MB of a layer's
-// weights through every block, so the L2 -> CU port (~60 GB/s per CU measured) bounds it at
-// ~22 us per layer at B*T = 6888.  A GATE block holds 128 frames x 64 gated channels: its
-// activation window (the frames' x rows with a dilation halo, and their cond rows) is staged in
-// LDS once for all K = 3C + H (the three taps are row-shifted reads of one window), and each
-// weight byte is read once per block: ~390 KB per block instead of 1.3 MB per 32 frames.
-// Why it is not the default: each launch pays its own load round trip and drain (~5 us at any
-// batch on MI355X), so the pair measured 12.6 + 16.6 us vs 22.2 us fused at B = 8 and 42 + 44 vs
-// ~87 us at B = 32.
-// The activations are bf16 copies kept beside the fp32 state: xa = bf16(x + dp_l) (written by
-// the previous RESSKIP epilogue, which knows dp_{l+1}) and condb = bf16(cond); x and skip stay
-// fp32 -- the same roundings as the fused kernel's LDS staging.
-//
-// GATE weight tiles pair the halves: pair tile p holds rows 16p..16p+15 of the gate half, then
-// the same 16 channels of the filter half, so in the transposed 32x32 C layout (lane = frame,
-// registers = weight rows (r&3) + 8(r>>2) + 4h) register r < 8 holds a gate channel and
-// register r + 8 its filter channel: the gate needs no data movement.
-constexpr int WG2_ROWS = 128;   // GATE frames per block
-constexpr int WG2_LD = 264;     // bf16 per LDS row: 512 B + 16 B (conflict-free b128 fragment reads)
-constexpr int WN_RS_RQ = 2;     // RESSKIP frame tiles (32 frames each) per block
-
-// XCD-aware block order for (row group, column) grids: the hardware deals consecutive block ids
-// round-robin over the 8 XCDs; remap so each XCD walks a contiguous run of logical blocks, column
-// fastest, and the column blocks of one row group -- which read the same activation rows -- share
-// one XCD's L2.
-__device__ __forceinline__ void wn_xcd_block(int& bx, int& by) {
-  const int total = gridDim.x * gridDim.y, id = blockIdx.y * gridDim.x + blockIdx.x;
-  const int xcd = id & 7, slot = id >> 3, per = total >> 3, rem = total & 7;
-  const int logical = xcd < rem ? xcd * (per + 1) + slot : rem * (per + 1) + (xcd - rem) * per + slot;
-  bx = logical / gridDim.y;
-  by = logical - bx * gridDim.y;
-}
-
-// dst[((p*KS + ks)*64 + lane)*8 + j] = bf16(src[row(p, lane%32) * ld + ks*16 + (lane/32)*8 + j]),
-// row(p, i) = i < 16 ? 16p + i : C + 16p + i - 16
-__global__ void pack_frag_pair_kernel(__bf16* dst, const float* src, int C, int K, int ld) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)2 * C * K) return;
-  const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
-  const long long rest = i >> 9;
-  const int KS = K / 16, ks = (int)(rest % KS), p = (int)(rest / KS);
-  const int r = lane & 31, row = r < 16 ? 16 * p + r : C + 16 * p + r - 16;
-  dst[i] = (__bf16)src[(long long)row * ld + ks * 16 + (lane >> 5) * 8 + j];
-}
-
-struct WnGateArgs {
-  const __bf16* xa;      // [rows][C] bf16(x + dp_l)
-  const __bf16* condb;   // [rows][H] bf16(cond)
-  const __bf16* Wp;      // [C/16 pair tiles][K1/16][64][8]
-  const float* b1;       // [2C] (dilated-conv + conditioner biases)
-  __bf16* g;             // [rows][C] gated output
-  int rows, T, dil;
-};
-
-// B fragment (frames 32q + n, k-step ks) of the GATE input: ks < 48 the x window at tap ks / 16,
-// else the cond rows.  EDGE: taps outside the frame's utterance read as zero (select: staged rows
-// of the neighbouring utterance, or clamped rows, are never multiplied in).
-template <int DW, bool EDGE>
-__device__ __forceinline__ bf16x8 wn_gate_bfrag(const __bf16* Xs, const __bf16* Cs, int ks, int q, int n, int h,
-                                                int d, const bool (&inv0)[4], const bool (&inv2)[4]) {
-  if (ks < 48) {
-    const int tap = ks >> 4;
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(&Xs[(32 * q + n + DW + (tap - 1) * d) * WG2_LD + (ks & 15) * 16 + 8 * h]);
-    if (EDGE && tap != 1) {
-      const bf16x8 z = {};
-      v = (tap == 0 ? inv0[q] : inv2[q]) ? z : v;
-    }
-    return v;
-  }
-  return *reinterpret_cast<const bf16x8*>(&Cs[(32 * q + n) * WG2_LD + (ks - 48) * 16 + 8 * h]);
-}
-
-// K loop of one GATE wave over k-steps [K0, K0 + 32): 4 frame tiles (128 frames) x one pair tile.
-// The next k-step's B fragments are read from LDS before this step's MFMAs, and the weight ring
-// refills WD steps ahead (sched_barrier keeps both where they are: the scheduler sinks loads to
-// their first use).
-template <int DW, int WD, int K0, bool EDGE>
-__device__ __forceinline__ void wn_gate_kloop(f32x16 (&acc)[4], bf16x8 (&rw)[WD], const bf16x8* wp,
-                                              const __bf16* Xs, const __bf16* Cs, int n, int h, int d,
-                                              const bool (&inv0)[4], const bool (&inv2)[4]) {
-  constexpr int NK = 32;
-  bf16x8 b[2][4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) b[0][q] = wn_gate_bfrag<DW, EDGE>(Xs, Cs, K0, q, n, h, d, inv0, inv2);
-#pragma unroll
-  for (int i = 0; i < NK; ++i) {
-    const bf16x8 w = rw[i % WD];
-    if (i + WD < NK) rw[i % WD] = wp[(K0 + i + WD) * 64];
-    if (i + 1 < NK) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) b[(i + 1) & 1][q] = wn_gate_bfrag<DW, EDGE>(Xs, Cs, K0 + i + 1, q, n, h, d, inv0, inv2);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, b[i & 1][q], acc[q], 0, 0, 0);
-  }
-}
-
-// GATE block (bx, by): frames [128 bx, +128), gated channels [64 by, +64) = pair tiles 4 by + w.
-// 8 waves: wave w < 4 runs k-steps [0, 32) of pair tile 4 by + w (taps t-d, t), wave w + 4 the
-// k-steps [32, 64) (tap t+d and cond) of the same tile, so a SIMD hosts two waves and each weight
-// byte is still read once per block; the halves meet through LDS at the end and each wave of
-// the pair finalises two of the four frame tiles.  Requires C = H = 256 and dil <= DW.
-template <int DW>
-__global__ __launch_bounds__(512, 1) void wn_gate_bf16_kernel(const WnGateArgs P) {
-  constexpr int C = 256, KS = 64, XR = WG2_ROWS + 2 * DW, WD = 12;
-  __shared__ __attribute__((aligned(16))) __bf16 Xs[XR * WG2_LD];          // frames R0 - DW + i
-  __shared__ __attribute__((aligned(16))) __bf16 Cs[WG2_ROWS * WG2_LD];    // frames R0 + i
-  static_assert(XR * WG2_LD * 2 >= 4 * 2 * 2 * 16 * 64 * 4, "partial-sum exchange reuses the x window");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, h = lane >> 5;
-  int bx, by;
-  wn_xcd_block(bx, by);
-  const int R0 = bx * WG2_ROWS, d = P.dil, rows = P.rows;
-  const int pw = wave & 3, half = wave >> 2, p = by * 4 + pw;
-  const bf16x8* wp = reinterpret_cast<const bf16x8*>(P.Wp) + (long long)p * KS * 64 + lane;
-  // staging: 32 16-B pieces per row; unconditional loads at clamped rows, masked at the store
-  constexpr int NX = XR * 32, IX = (NX + 511) / 512, IC = WG2_ROWS * 32 / 512;
-  uint4 xv[IX], cv[IC];
-#pragma unroll
-  for (int it = 0; it < IX; ++it) {
-    const int i = tid + 512 * it, r = min(max(R0 - DW + (i >> 5), 0), rows - 1);
-    xv[it] = *reinterpret_cast<const uint4*>(P.xa + (long long)r * C + (i & 31) * 8);
-  }
-#pragma unroll
-  for (int it = 0; it < IC; ++it) {
-    const int i = tid + 512 * it, r = min(R0 + (i >> 5), rows - 1);
-    cv[it] = *reinterpret_cast<const uint4*>(P.condb + (long long)r * C + (i & 31) * 8);
-  }
-  bf16x8 rw[WD];
-  const int k0 = half * 32;
-#pragma unroll
-  for (int i = 0; i < WD; ++i) rw[i] = wp[(k0 + i) * 64];
-#pragma unroll
-  for (int it = 0; it < IX; ++it) {
-    const int i = tid + 512 * it;
-    if (i < NX) *reinterpret_cast<uint4*>(&Xs[(i >> 5) * WG2_LD + (i & 31) * 8]) = xv[it];
-  }
-#pragma unroll
-  for (int it = 0; it < IC; ++it) {
-    const int i = tid + 512 * it;
-    *reinterpret_cast<uint4*>(&Cs[(i >> 5) * WG2_LD + (i & 31) * 8]) = cv[it];
-  }
-  // taps outside the frame's utterance (zero padding of the dilated conv)
-  bool inv0[4], inv2[4], any = false;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int R = min(R0 + 32 * q + n, rows - 1), b = R / P.T, t = R - b * P.T;
-    inv0[q] = t - d < 0;
-    inv2[q] = t + d >= P.T;
-    any |= inv0[q] | inv2[q];
-  }
-  const bool edge = __ballot(any) != 0;
-  __syncthreads();
-  f32x16 acc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-  if (half == 0) {
-    if (edge) wn_gate_kloop<DW, WD, 0, true>(acc, rw, wp, Xs, Cs, n, h, d, inv0, inv2);
-    else wn_gate_kloop<DW, WD, 0, false>(acc, rw, wp, Xs, Cs, n, h, d, inv0, inv2);
-  } else {
-    if (edge) wn_gate_kloop<DW, WD, 32, true>(acc, rw, wp, Xs, Cs, n, h, d, inv0, inv2);
-    else wn_gate_kloop<DW, WD, 32, false>(acc, rw, wp, Xs, Cs, n, h, d, inv0, inv2);
-  }
-  // exchange: wave (pw, half) finalises frame tiles 2 half, 2 half + 1 and hands the other two
-  // tiles' partial sums to its partner (x window space, every wave is past its reads).  Tile
-  // indices stay compile-time (a run-time index would put acc in scratch).
-  __syncthreads();
-  float* ex = reinterpret_cast<float*>(Xs);     // [pw][half][2 tiles][16 regs][64 lanes]
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if ((q >> 1) != half) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ex[(((pw * 2 + half) * 2 + (q & 1)) * 16 + r) * 64 + lane] = acc[q][r];
-    }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if ((q >> 1) == half) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[q][r] += ex[(((pw * 2 + (1 - half)) * 2 + (q & 1)) * 16 + r) * 64 + lane];
-    }
-  // epilogue: register r < 8 = gate channel 16p + (r&3) + 8(r>>2) + 4h, r + 8 = its filter channel
-  float bg[8], bf[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const int c = 16 * p + (r & 3) + 8 * (r >> 2) + 4 * h;
-    bg[r] = P.b1[c];
-    bf[r] = P.b1[C + c];
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int R = R0 + 32 * q + n;
-    if ((q >> 1) == half && R < rows) {
-#pragma unroll
-      for (int gq = 0; gq < 2; ++gq) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * gq + e;
-          o[e] = (__bf16)gate_fast(acc[q][r] + bg[r], acc[q][r + 8] + bf[r]);
-        }
-        *reinterpret_cast<bf16x4*>(P.g + (long long)R * C + 16 * p + 8 * gq + 4 * h) = o;
-      }
-    }
-  }
-}
-
-struct WnResSkipArgs {
-  const __bf16* g;       // [rows][C] gated activations
-  const __bf16* W2f;     // [2C/32][C/16][64][8] (fragment order; tiles 0..C/32-1 residual, then skip)
-  const float* b2;       // [2C]
-  float* x;              // [rows][C] fp32 residual state, updated in place
-  float* skip;           // [rows][C] fp32
-  __bf16* xa_next;       // [rows][C] bf16(x + dp_{l+1}) or null (last layer)
-  const float* dp_next;  // dp_{l+1}[b * dp_ld + c]
-  int dp_ld, first, nt0, rows, T;
-};
-
-// RESSKIP block (bx, by): frames [32 RQ bx, +32 RQ), output tile nt = nt0 + 4 by + wave (32
-// channels; nt < C/32: residual, else skip).  The block's g rows live in LDS (A operand, frames on
-// the accumulator rows), a wave's 16 weight fragments (its whole K) sit in registers (B operand,
-// channels on the lanes), so the epilogue's fp32 x / skip accesses are 128-B row segments.
-// The epilogue operands are loaded before the MFMAs.
-template <int RQ>
-__global__ __launch_bounds__(256, 2) void wn_resskip_bf16_kernel(const WnResSkipArgs P) {
-  constexpr int C = 256, KS = C / 16, BR = 32 * RQ;
-  __shared__ __attribute__((aligned(16))) __bf16 Gs[BR * WG2_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, h = lane >> 5;
-  int bx, by;
-  wn_xcd_block(bx, by);
-  const int R0 = bx * BR, rows = P.rows, T = P.T;
-  const int nt = P.nt0 + by * 4 + wave;
-  constexpr int IG = BR * 32 / 256;
-  uint4 gv[IG];
-#pragma unroll
-  for (int it = 0; it < IG; ++it) {
-    const int i = tid + 256 * it, r = min(R0 + (i >> 5), rows - 1);
-    gv[it] = *reinterpret_cast<const uint4*>(P.g + (long long)r * C + (i & 31) * 8);
-  }
-  const bf16x8* wp = reinterpret_cast<const bf16x8*>(P.W2f) + (long long)nt * KS * 64 + lane;
-  bf16x8 w[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) w[ks] = wp[ks * 64];
-#pragma unroll
-  for (int it = 0; it < IG; ++it) {
-    const int i = tid + 256 * it;
-    *reinterpret_cast<uint4*>(&Gs[(i >> 5) * WG2_LD + (i & 31) * 8]) = gv[it];
-  }
-  // lane (n, h) of frame tile q holds channel c = 32 (nt mod C/32) + n of frames
-  // R0 + 32q + (r&3) + 8(r>>2) + 4h, r < 16
-  const bool res = nt < C / 32;
-  const int c = (res ? nt : nt - C / 32) * 32 + n;
-  float* io = res ? P.x : P.skip;
-  const bool rd = res || !P.first;
-  float xo[RQ][16];
-#pragma unroll
-  for (int q = 0; q < RQ; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int R = min(R0 + 32 * q + (r & 3) + 8 * (r >> 2) + 4 * h, rows - 1);
-      xo[q][r] = rd ? io[(long long)R * C + c] : 0.f;
-    }
-  const float bias = P.b2[(res ? 0 : C) + c];
-  __syncthreads();
-  f32x16 acc[RQ];
-#pragma unroll
-  for (int q = 0; q < RQ; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    bf16x8 a[RQ];
-#pragma unroll
-    for (int q = 0; q < RQ; ++q)
-      a[q] = *reinterpret_cast<const bf16x8*>(&Gs[(32 * q + n) * WG2_LD + ks * 16 + 8 * h]);
-#pragma unroll
-    for (int q = 0; q < RQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[q], w[ks], acc[q], 0, 0, 0);
-  }
-  const float rs2 = 0.70710678118654752440f;
-#pragma unroll
-  for (int q = 0; q < RQ; ++q) {
-    // utterance of each row: one division per 32-row tile (T >= 32: at most one boundary inside)
-    const int Rq = R0 + 32 * q, bq = Rq / T, Rb = (bq + 1) * T;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int R = Rq + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (R < rows) {
-        const long long o = (long long)R * C + c;
-        const float v = acc[q][r] + bias;
-        if (res) {
-          const float xn = (xo[q][r] + v) * rs2;
-          io[o] = xn;
-          if (P.xa_next) {
-            const int b = T >= 32 ? bq + (R >= Rb ? 1 : 0) : R / T;
-            P.xa_next[o] = (__bf16)(xn + P.dp_next[(long long)b * P.dp_ld + c]);
-          }
-        } else {
-          io[o] = xo[q][r] + v;
-        }
-      }
-    }
-  }
-}
-
-// xa = bf16(x + dp[b]) (layer 0's GATE input) and, when cond is given, condb = bf16(cond)
+// condb = bf16(cond) for the stack kernel; with x given also xa = bf16(x + dp[b]) (no caller passes one)
 __global__ void wn_xa_kernel(const float* __restrict__ x, const float* __restrict__ dp, int dp_ld,
                              __bf16* __restrict__ xa, const float* __restrict__ cond, __bf16* __restrict__ condb,
                              int rows, int T, int C, int H) {
@@ -1375,7 +1063,7 @@ __global__ void wn_xa_kernel(const float* __restrict__ x, const float* __restric
 }
 
 struct WsLayout {
-  size_t x, x2, g, skip, hs, xin, condT, outT, steps, emb, h1, d, dproj, xa, condb, part, total;
+  size_t x, x2, g, skip, hs, xin, condT, outT, steps, emb, h1, d, dproj, condb, part, total;
 };
 
 // fp32 residual-layer GEMMs (128 x 64 paired tiles): split K over up to 8 blocks when the
@@ -1412,7 +1100,6 @@ WsLayout ws_layout(const pd_wavenet* h, int B, int T, int S) {
   w.h1 = take((size_t)S * B * 4 * h->C);
   w.d = take((size_t)S * B * h->C);
   w.dproj = take((size_t)S * B * h->L * h->C);
-  w.xa = take(BT * h->C / 2 + 8);                 // bf16 [B*T][C] (two-GEMM layer path)
   w.condb = take(BT * h->H / 2 + 8);              // bf16 [B*T][H]
   size_t part = 0;
   if (!h->W1f) {
@@ -1477,53 +1164,6 @@ struct WnCall {
   hipStream_t st;
   int rows() const { return B * T; }
 };
-
-// bf16 layer implementation (PD_WN_OPT_LAYER 1): GATE + RESSKIP launches per residual layer
-// (wn_gate_bf16_kernel, wn_resskip_bf16_kernel).  Not the default: at B*T = 1722 .. 27552 frames it measured
-// equal to or slower than the fused kernel.
-int wn_layers_two(const WnCall& c) {
-  const pd_wavenet* h = c.h;
-  const int H = h->H, C = h->C, Ly = h->L, rows = c.rows(), T = c.T;
-  float* x = c.ws + c.Lw.x;
-  __bf16* xa = reinterpret_cast<__bf16*>(c.ws + c.Lw.xa);
-  __bf16* condb = reinterpret_cast<__bf16*>(c.ws + c.Lw.condb);
-  __bf16* gb = reinterpret_cast<__bf16*>(c.ws + c.Lw.g);
-  {
-    ProfScope ps("wn_xa", c.st);
-    const long long n4 = ((long long)rows * (C > H ? C : H) + 3) / 4;
-    hipLaunchKernelGGL(wn_xa_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, c.st, x, c.dproj, Ly * C, xa, c.cond, condb,
-                       rows, T, C, H);
-    PD_LAUNCH_CHECK();
-  }
-  const int K1 = 3 * C + H;
-  for (int l = 0; l < Ly; ++l) {
-    WnGateArgs G{};
-    G.xa = xa; G.condb = condb; G.Wp = h->W1p + (size_t)l * 2 * C * K1; G.b1 = h->bl1 + (size_t)l * 2 * C;
-    G.g = gb; G.rows = rows; G.T = T; G.dil = 1 << (l % h->cyc);
-    {
-      ProfScope ps("wn_gate2", c.st);
-      dispatch([&](auto DW) {
-        hipLaunchKernelGGL(wn_gate_bf16_kernel<DW()>, dim3(cdiv(rows, WG2_ROWS), C / 64), dim3(512), 0, c.st, G);
-      }, one_of<1, 16>(h->cyc == 1 ? 1 : 16));
-      PD_LAUNCH_CHECK();
-    }
-    const bool last = l == Ly - 1;
-    WnResSkipArgs P{};
-    P.g = gb; P.W2f = h->W2f + (size_t)l * 2 * C * C; P.b2 = h->bl2 + (size_t)l * 2 * C;
-    P.x = x; P.skip = c.ws + c.Lw.skip; P.first = l == 0;
-    P.xa_next = last ? nullptr : xa; P.dp_next = last ? nullptr : c.dproj + (size_t)(l + 1) * C; P.dp_ld = Ly * C;
-    // the last layer's residual half feeds nothing (wavenet.py:115-119 keeps only skip)
-    P.nt0 = last ? C / 32 : 0;
-    P.rows = rows; P.T = T;
-    {
-      ProfScope ps("wn_resskip2", c.st);
-      hipLaunchKernelGGL(wn_resskip_bf16_kernel<WN_RS_RQ>, dim3(cdiv(rows, 32 * WN_RS_RQ), (last ? C : 2 * C) / 128),
-                         dim3(256), 0, c.st, P);
-      PD_LAUNCH_CHECK();
-    }
-  }
-  return PD_OK;
-}
 
 // The net's largest dilation, 2^(min(cyc, L) - 1) (pd_wavenet_create keeps the exponent below 31)
 int wn_max_dil(const pd_wavenet* h) { return 1 << (std::min(h->cyc, h->L) - 1); }
@@ -1780,13 +1420,7 @@ int wavenet_core(const pd_wavenet* h, float* ws, const WsLayout& Lw, const float
     a.act = ACT_RELU;
     PD_TRY((launch_small_gemm<EPI_STORE, U_WN_INPROJ>(a, st, "wn_inproj")));
   }
-  const bool two = h->W1p && h->cyc <= 5 && h->layer_mode == 1;   // dilations up to 16: the GATE kernel's halo
-  if (two && lens) {
-    set_error("PD_WN_OPT_LAYER 1 (two-kernel layers) does not take ragged batches (lens)");
-    return PD_ERR_UNSUPPORTED;
-  }
-  if (two) PD_TRY(wn_layers_two(c));
-  else if (stack) PD_TRY(wn_layers_stack(c, grp, ngrp, fuse));
+  if (stack) PD_TRY(wn_layers_stack(c, grp, ngrp, fuse));
   else if (h->W1f) PD_TRY(wn_layers_fused(c));
   else PD_TRY(wn_layers_f32(c));
   if (fuse_tail) {   // skip head, output projection and posterior ran in the last stack launch
@@ -1872,11 +1506,10 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
     PD_TRY(wp.mirror_bf16(st));
     if (C == WNF_C && 3 * C + H == 1024) {   // H == 256: the fused kernel is built for K1 = 1024
       const int K1 = 3 * C + H;
-      const size_t per = (size_t)4 * C * K1 + (size_t)2 * C * C;
+      const size_t per = (size_t)2 * C * K1 + (size_t)2 * C * C;
       PD_TRY(h->frag.alloc((size_t)L * per * sizeof(__bf16), "the WaveNet fragment-order weights"));
       h->W1f = static_cast<__bf16*>(h->frag.get());
       h->W2f = h->W1f + (size_t)L * 2 * C * K1;
-      h->W1p = h->W2f + (size_t)L * 2 * C * C;
       for (int l = 0; l < L; ++l) {
         const long long n1 = (long long)2 * C * K1, n2 = (long long)2 * C * C;
         hipLaunchKernelGGL(pack_frag_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, h->W1f + l * n1,
@@ -1884,9 +1517,6 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
         PD_LAUNCH_CHECK();
         hipLaunchKernelGGL(pack_frag_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, st, h->W2f + l * n2,
                            h->Wl2 + (size_t)l * 2 * C * C, 2 * C, C, C);
-        PD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pack_frag_pair_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, h->W1p + l * n1,
-                           h->Wl1 + (size_t)l * 2 * C * h->ldw1, C, K1, h->ldw1);
         PD_LAUNCH_CHECK();
       }
     }
@@ -1898,7 +1528,7 @@ int pd_wavenet_create(const pd_wavenet_dims* dims, const float* const* params, i
 int pd_wavenet_set_option(pd_wavenet* h, int option, int value) {
   PD_CHECK_ARG(h, "null pointer");
   if (option == PD_WN_OPT_LAYER) {
-    PD_CHECK_ARG(value >= 0 && value <= 3, "PD_WN_OPT_LAYER is 0, 1, 2 or 3");
+    PD_CHECK_ARG(value == 0 || value == 2 || value == 3, "PD_WN_OPT_LAYER is 0, 2 or 3");
     h->layer_mode = value;
     return PD_OK;
   }

@@ -142,7 +142,7 @@ class FastDiff(nn.Module):
 
     def set_options(self, **opts):
         """Kernel-variant options (fd_set_option, include/prodiff_hip.h FD_OPT_*): lvc_ts,
-        lvc_ts_sub, lvc_fuse, lvc_pf, lvc_sub, kp_side, kp_chunk, lvc_tpw, lvc_prio, lvc_ps, lvc_carry,
+        lvc_fuse, lvc_pf, lvc_sub, kp_chunk, lvc_tpw, lvc_prio, lvc_ps, lvc_carry,
         lvc_ps_grid (_lib.FD_OPTIONS).  Unset ones keep the measured defaults."""
         self._native.set_options(opts)
         return self

@@ -441,6 +441,21 @@ def test_unknown_options_and_dtypes_are_refused():
                 m.set_options(nope=1)
             assert m.set_options() is m
     assert [hasattr(m, "set_options") for _, m, _ in _four_modules()] == [True, True, True, False]
+    # the variants that lost their A/B runs are gone: their names are unknown, and the C setters answer their ids
+    # as any unknown id and their values as any bad value.  No handle can be created without a device, so a zeroed
+    # buffer, larger than either handle struct, stands in for one: the setters check the handle only for null and
+    # refuse an id or value before they read or write it, so the buffer is never used as an object (were a
+    # setter to accept one of these, it would return 0 and the assertion below would fail)
+    _, fd, _ = _four_modules()[1]
+    for k in ("kp_side", "lvc_ts_sub"):
+        with pytest.raises(ValueError, match=f"option '{k}'"):
+            fd.set_options(**{k: 1})
+    L, h = _lib.lib(), _lib.C.create_string_buffer(1 << 16)
+    for fn, option, values, text in ((L.fd_set_option, 1, (128, 256, 384), "unknown option 1"),
+                                     (L.fd_set_option, 5, (0, 1), "unknown option 5"),
+                                     (L.pd_wavenet_set_option, _lib.WN_OPTIONS["layer"], (1,), "PD_WN_OPT_LAYER")):
+        for v in values:
+            assert fn(h, option, v) == 1 and text in L.pd_last_error().decode(), (text, v)
 
 
 def test_cpu_parameters_fail_loudly_in_handle():

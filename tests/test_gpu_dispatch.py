@@ -9,7 +9,7 @@ what notices.  The fixture is recorded with the library of the commit BEFORE a c
     PRODIFF_HIP_LIB=tools/bin/lib_<rev>.so python -m tests.test_gpu_dispatch [out.json]
 
 What the table cannot see: options that choose between kernels launched under one tag leave their row equal to
-the default's.  Those are FD_OPT_LVC_PS, LVC_TPW, LVC_PF, LVC_PRIO and the tile sizes LVC_TS 128 / 256 and LVC_TS_SUB
+the default's.  Those are FD_OPT_LVC_PS, LVC_TPW, LVC_PF, LVC_PRIO and the tile sizes LVC_TS 128 / 256
 (all fd_lvc_block_*), NSF_OPT_RB16 1 against 2, NSF_OPT_C256 and NSF_OPT_NC_MFMA (nsf_rb16, nsf_res,
 nsf_noise_conv), PD_WN_OPT_STACK_RO and stack sizes of 10 and more (wn_stack), and the fp32 WaveNet layers as
 kernels or GEMMs (wn_gate / wn_resskip; only the sampler's wn_f32_tail tells them apart).  For those the
@@ -36,11 +36,11 @@ FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "di
 
 # every non-default value tests/test_gpu_bf16.py and tests/test_gpu_nsf.py set (and PD_WN_OPT_F32_LAYER of
 # tests/test_gpu_parity.py), after the defaults
-FD_OPTS = [{}, dict(lvc_ts_sub=128), dict(lvc_ts_sub=384), dict(lvc_ts=0), dict(lvc_ts=128), dict(lvc_ts=256),
+FD_OPTS = [{}, dict(lvc_ts=0), dict(lvc_ts=128), dict(lvc_ts=256),
            dict(lvc_fuse=0, lvc_sub=0, lvc_ts=128), dict(lvc_fuse=0, lvc_sub=0, lvc_ts=256),
            dict(lvc_fuse=0, lvc_sub=0, lvc_ts=384), dict(kp_chunk=1), dict(kp_chunk=2), dict(lvc_pf=0),
            dict(lvc_pf=0, lvc_tpw=1), dict(lvc_pf=1, lvc_tpw=1), dict(lvc_pf=1, lvc_prio=1), dict(lvc_ps=0)]
-WN_OPTS = [{}, dict(layer=3), dict(layer=0), dict(layer=1), dict(layer=0, stack=0), dict(stack=1), dict(stack=4),
+WN_OPTS = [{}, dict(layer=3), dict(layer=0), dict(layer=0, stack=0), dict(stack=1), dict(stack=4),
            dict(stack=7), dict(stack=10), dict(stack=16), dict(stack=10, stack_ro=16), dict(stack=10, stack_ro=23),
            dict(stack=10, stack_ro=32), dict(stack=10, stack_ro=41), dict(stack=10, stack_ro=44), dict(stack_fuse=0)]
 WN_F32_OPTS = [{}, dict(f32_layer=0), dict(f32_layer=2)]
@@ -88,10 +88,10 @@ def fastdiff_tables():
 
 def wavenet_tables():
     """The ProDiff denoiser (20 layers, 256 channels): a 2-step ragged sample at T = 70 and a forward at T = 70
-    and T = 37 per option set; PD_WN_OPT_LAYER 1 takes no lens, so that set samples the dense batch.  Dilation
+    and T = 37 per option set.  Dilation
     cycle 5 at the defaults reaches the stack kernel's dilated instantiations."""
     out = {}
-    for cyc, dtype, sets in ((1, "fp32", WN_F32_OPTS), (1, "bf16", WN_OPTS), (5, "bf16", [{}, dict(layer=1)])):
+    for cyc, dtype, sets in ((1, "fp32", WN_F32_OPTS), (1, "bf16", WN_OPTS), (5, "bf16", [{}])):
         torch.manual_seed(41)
         sd = GaussianDiffusion(80, WaveNet(80, 256, 20, 256, cyc), timesteps=4, time_scale=1000,
                                max_beta=0.7).state_dict()
@@ -103,9 +103,8 @@ def wavenet_tables():
             g.load_state_dict(sd)
             g = g.to(DEV).set_compute_dtype(dtype)
             g.denoise_fn.set_options(**opts)
-            lens = None if opts.get("layer") == 1 else [70, 41]
             net = f"wavenet_cyc{cyc}"
-            out[_name(net, dtype, "sample", **opts)] = _tags(lambda: g.sample(cond, infer_step=2, seed=7, lens=lens))
+            out[_name(net, dtype, "sample", **opts)] = _tags(lambda: g.sample(cond, infer_step=2, seed=7, lens=[70, 41]))
             for T in (70, 37):
                 out[_name(net, dtype, f"forward_T{T}", **opts)] = _tags(
                     lambda: g.denoise_fn(spec[..., :T].contiguous(), steps, cond[:, :T].transpose(1, 2).contiguous()))

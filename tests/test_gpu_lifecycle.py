@@ -39,7 +39,7 @@ class Case:
 
 
 class WaveNetCase(Case):
-    dtype, option = "bf16", {"layer": 1}
+    dtype, option = "bf16", {"layer": 0}
 
     def make(self):
         m = WaveNet(80, 256, 2, 256, 1)

@@ -135,16 +135,6 @@ def test_long_stack_bitexact(name, opts, stacked):
     np.testing.assert_array_equal(out, one)
 
 
-def test_two_kernel_option_falls_back_at_cycle_6():
-    """PD_WN_OPT_LAYER 1 (GATE + RESSKIP kernels, a 16-row halo) at dilation 32 runs the one-layer kernel:
-    the same launches as PD_WN_OPT_LAYER 0, bit for bit."""
-    out, tags = forward(wavenet("cyc6", "bf16", layer=1), "cyc6")
-    check_tags(tags, ({"wn_layer"}, {"wn_gate2", "wn_resskip2", "wn_stack"}), "cyc6 bf16 layer=1")
-    one, _ = forward(wavenet("cyc6", "bf16", layer=0, stack=0), "cyc6")
-    np.testing.assert_array_equal(out, one)
-    assert_bf16_close(out, WC.forward_ref("cyc6"), "cyc6 forward layer=1")
-
-
 def prodiff(name, dtype, **opts):
     gd = GaussianDiffusion(WC.CASES[name]["dims"][0], wavenet(name, dtype, **opts), timesteps=WC.PRODIFF_TIMESTEPS,
                            time_scale=1000, max_beta=WC.PRODIFF_MAX_BETA)
