@@ -828,7 +828,8 @@ int pd_f0_align_ragged(const float* f0, float* f0_out, unsigned char* uv_out, co
 /* ================================================================ harmonic-noise separation
  * pd_vr -- CascadedNet of modules/vr (nets.py, layers.py) with is_complex = True, its zero-padded STFT and its
  * iSTFT: what extract_harmonic_aperiodic runs on a vocoder output (handler/infer/handler.py:349-358) and on every
- * training utterance (component/binarizer/svs.py:113).  Inference only, fp32 only.
+ * training utterance (component/binarizer/svs.py:113).  Inference only; fp32, with the convs on the bf16 MFMA as
+ * an option of the handle (PD_VR_OPT_CONV_DTYPE below).
  *   frames:  n_frames = L / hop + 1, T = 32 (n_frames / 32 + 1), T_pad = (T - 1) hop - L, Tl_pad = (T_pad / 2 / hop) hop
  *            zeros on the left and the rest on the right; torch.stft(n_fft, hop, periodic Hann(n_fft), center = True,
  *            pad_mode = 'constant') of that has exactly T frames.  Frame t covers samples [t hop - lead, t hop - lead +
@@ -882,6 +883,17 @@ int pd_vr_num_params(const pd_vr_dims* dims);
 int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, void* stream, pd_vr** out);
 /* The caller must ensure that no call on the handle is still in flight. */
 void pd_vr_destroy(pd_vr* h);
+/* PD_VR_OPT_CONV_DTYPE = PD_DTYPE_F32 (the default) or PD_DTYPE_BF16: with bf16 every conv but the last (`out`)
+ * rounds its input values to bf16 (nearest even; after the bilinear gather and the border's zeros, which stay f32)
+ * and multiplies them with a bf16 copy of its folded weights on v_mfma_f32_32x32x16_bf16, accumulating in f32.
+ * Bias, activation and every stored map stay f32, as do the STFT, the iSTFT, the LSTM and its two Linear layers,
+ * the frequency mean, `out` and the bounded mask; workspace sizes do not change and an output row still depends
+ * neither on the batch size nor on its position.  The first switch to bf16 builds the copy on `stream` inside the
+ * handle's weight pool (pd_live_device_bytes counts it, pd_vr_destroy returns it); later switches only flip the
+ * mode.  The caller must not switch while a call on the handle is in flight.  A null handle, an unknown option or
+ * any other value returns PD_ERR_ARG. */
+#define PD_VR_OPT_CONV_DTYPE 0
+int pd_vr_set_option(pd_vr* h, int option, int value, void* stream);
 /* T and lead (above) for a row of n_samples. */
 int pd_vr_frames(const pd_vr* h, int n_samples);
 int pd_vr_lead(const pd_vr* h, int n_samples);

@@ -19,6 +19,7 @@ FD_OPTIONS = {"lvc_ts": 0, "lvc_fuse": 2, "lvc_pf": 3, "lvc_sub": 4, "kp_chunk":
                "lvc_tpw": 10, "lvc_prio": 11, "lvc_ps": 14, "lvc_carry": 15, "lvc_ps_grid": 16}
 NSF_OPTIONS = {"small_max": 0, "wconv": 1, "pair": 2, "pair16": 3, "ups_nc": 4, "rb16": 5, "rb32": 6, "rb64": 7, "c256": 8, "nc_mfma": 9}
 WN_OPTIONS = {"layer": 0, "ksplit": 1, "l2pf": 2, "stack": 3, "stack_ro": 4, "stack_fuse": 6, "f32_layer": 7}
+PD_VR_OPT_CONV_DTYPE = 0   # pd_vr_set_option
 
 
 class HipError(RuntimeError):
@@ -206,6 +207,7 @@ _SIGS = {
     "pd_vr_num_params": (C.c_int, [C.POINTER(pd_vr_dims)]),
     "pd_vr_create": (C.c_int, [C.POINTER(pd_vr_dims), C.POINTER(_VP), C.c_int, _VP, C.POINTER(_VP)]),
     "pd_vr_destroy": (None, [_VP]),
+    "pd_vr_set_option": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pd_vr_frames": (C.c_int, [_VP, C.c_int]),
     "pd_vr_lead": (C.c_int, [_VP, C.c_int]),
     "pd_vr_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),

@@ -1,5 +1,6 @@
 // Harmonic-noise separation (include/prodiff_hip.h, "harmonic-noise separation"): CascadedNet of modules/vr
-// (nets.py, layers.py) with its zero-padded STFT front end and its iSTFT back end.  fp32 only.
+// (nets.py, layers.py) with its zero-padded STFT front end and its iSTFT back end.  fp32; every conv but the last
+// can take its operands in bf16 (pd_vr_set_option, the BF instance of vr_conv_kernel), all else staying fp32.
 //
 // Activations are channels-last images [B][T][F][C] (T = frames, F = bins).  One tensor X [B][T][F][nin + 3 nout/4]
 // holds the network input (channels 0 .. nin), aux1 (the next nout/4) and aux2 (the last nout/2): a band net reads
@@ -52,6 +53,8 @@ namespace {
 constexpr int VR_CK = 16;           // channels per K chunk
 constexpr int VR_MAX_HID = 64;      // LSTM hidden units per direction the recurrence kernel holds in registers
 constexpr int VR_MAX_NFFT = 16384;
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ------------------------------------------------------------------ create-time kernels
 // The convs are packed by pack_conv_tiles (kernels.h) with TAPS_SWAPPED: src is Conv2d's [Cout][c0 + c1][freq][time],
@@ -154,7 +157,7 @@ struct VrConvArgs {
   int H, W;            // output image
   int stride, dy, dx;  // dilation in frames and in bins
   float sy, sx;        // (Hi/2 - 1) / (Hi - 1), (Wi/2 - 1) / (Wi - 1): the gather's source scales
-  const float* wp;     // packed [ctiles][nchunk][taps][32][16]
+  const void* wp;      // packed [ctiles][nchunk][taps][32][16]: float, or (BF) the tiles' bf16 copy
   const float* bias;   // [ctiles * 32]
   int act;             // ACT_NONE, ACT_RELU or ACT_LRELU (slope 0.01)
   float* out;
@@ -185,8 +188,11 @@ __device__ __forceinline__ void vr_lerp_index(float scale, int i, int n_in, int&
 
 // TAPS 1 or 9; UP: source 0 is read through the gather; NT: 32-channel output tiles per wave (the pixel's values
 // are fetched once for all of them); RG: a ragged batch, every pixel at or past the row's own height lies outside
-// the image (read as the border's zero, never written), and a tile wholly past it returns at once
-template <int TAPS, bool UP, int NT, bool RG>
+// the image (read as the border's zero, never written), and a tile wholly past it returns at once; BF: the lane's
+// eight values, fetched, interpolated and border-zeroed in f32 exactly as without it, are rounded once to bf16
+// (nearest even) and meet the bf16 copy of the weights in one v_mfma_f32_32x32x16_bf16 per tap, chunk and tile
+// (element j of lane (r, h) is k = 8 h + j of both operands: the eight f32 steps' pairing), accumulated in f32
+template <int TAPS, bool UP, int NT, bool RG, bool BF>
 __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int b = blockIdx.z, ct0 = blockIdx.y * NT;
@@ -205,10 +211,11 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
   int nchunk = 0;
   for (int s = 0; s < a.nsrc; ++s) nchunk += (a.s[s].c + VR_CK - 1) / VR_CK;
   const int ctl = (a.cout + 31) / 32 - 1;   // tiles past the last one repeat it and are never written
-  const float* wrow[NT];
+  using TW = std::conditional_t<BF, __bf16, float>;
+  const TW* wrow[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i)
-    wrow[i] = a.wp + ((long long)min(ct0 + i, ctl) * nchunk * TAPS * 32 + r) * 16 + h * 8;
+    wrow[i] = static_cast<const TW*>(a.wp) + ((long long)min(ct0 + i, ctl) * nchunk * TAPS * 32 + r) * 16 + h * 8;
 
   f32x16 acc[NT];
 #pragma unroll
@@ -231,9 +238,13 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
 #pragma unroll
         for (int tc = 0; tc < TR; ++tc) {
           const int tap = tr * TR + tc;
-          float wf[NT][8], af[8];
+          float wf[BF ? 1 : NT][8], af[8];
+          bf16x8 wb[BF ? NT : 1];
 #pragma unroll
-          for (int i = 0; i < NT; ++i) load8(wrow[i] + wo + tap * 512, wf[i]);
+          for (int i = 0; i < NT; ++i) {
+            if constexpr (BF) wb[i] = *reinterpret_cast<const bf16x8*>(wrow[i] + wo + tap * 512);
+            else load8(wrow[i] + wo + tap * 512, wf[i]);
+          }
           const int iy = y * a.stride + (TAPS == 9 ? tr - 1 : 0) * a.dy, ix = x * a.stride + (TAPS == 9 ? tc - 1 : 0) * a.dx;
           const bool ok = iy >= 0 && iy < Hi && ix >= 0 && ix < a.Wi;
           const int cy = min(max(iy, 0), Hi - 1), cx = min(max(ix, 0), a.Wi - 1);
@@ -261,10 +272,19 @@ __global__ __launch_bounds__(256) void vr_conv_kernel(const VrConvArgs a) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) af[i] = 0.f;
           }
+          if constexpr (BF) {
+            bf16x8 ab;
 #pragma unroll
-          for (int kk = 0; kk < 8; ++kk)
+            for (int i = 0; i < 8; ++i) ab[i] = (__bf16)af[i];
 #pragma unroll
-            for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], wf[i][kk], acc[i], 0, 0, 0);
+            for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, wb[i], acc[i], 0, 0, 0);
+          } else {
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+              for (int i = 0; i < NT; ++i)
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], wf[i][kk], acc[i], 0, 0, 0);
+          }
         }
       }
     }
@@ -585,6 +605,7 @@ __global__ __launch_bounds__(256) void vr_istft_kernel(const VrIstftArgs a) {
 // ------------------------------------------------------------------ host side
 struct Conv {
   float* w = nullptr;
+  const __bf16* wb = nullptr;   // w's bf16 copy, from the first switch to PD_DTYPE_BF16 on
   float* b = nullptr;
   int c0 = 0, c1 = 0, cout = 0, taps = 9;
 };
@@ -595,6 +616,19 @@ struct Net {
   bool has_tail = false;
   float *wih = nullptr, *bl = nullptr, *whh = nullptr, *wd = nullptr, *bd = nullptr;
 };
+
+template <class F>
+void each_conv(Net& nt, F&& f) {
+  f(nt.enc1);
+  for (auto& pair : nt.enc)
+    for (Conv& c : pair) f(c);
+  for (Conv& c : nt.aspp) f(c);
+  f(nt.bott);
+  for (Conv& c : nt.dec) f(c);
+  f(nt.lconv);
+  f(nt.dec1);
+  if (nt.has_tail) f(nt.tail);
+}
 
 bool dims_ok(const pd_vr_dims& d) {
   if (d.is_mono != 0 && d.is_mono != 1) return false;
@@ -617,6 +651,7 @@ struct pd_vr {
   Conv out;
   float *fc = nullptr, *fs = nullptr, *ic = nullptr, *is = nullptr, *win = nullptr;
   int C, nin, F, nb, nbp, nbk, cx;
+  bool bf = false;    // PD_VR_OPT_CONV_DTYPE: every conv but `out` on the bf16 MFMA
 };
 
 namespace {
@@ -678,8 +713,8 @@ struct OutView {
 OutView dense_out(float* p, int H, int W, int c) { return OutView{p, (long long)H * W * c, W * c, c}; }
 
 // Hi x Wi: the conv's input image (twice the stored one for a gathered source); rg.v: a ragged batch, Hi = rg.T >> lvl
-int launch_conv(const Conv& cw, const VrSrc& s0, const VrSrc* s1, int B, int Hi, int Wi, int stride, int dy, int dx,
-                int act, const OutView& o, const VrRag& rg, hipStream_t st, const char* tag) {
+int launch_conv(const Conv& cw, bool bf, const VrSrc& s0, const VrSrc* s1, int B, int Hi, int Wi, int stride, int dy,
+                int dx, int act, const OutView& o, const VrRag& rg, hipStream_t st, const char* tag) {
   VrConvArgs a{};
   a.rg = rg;
   if (rg.v) a.lvl = __builtin_ctz((unsigned)(rg.T / Hi));
@@ -694,7 +729,7 @@ int launch_conv(const Conv& cw, const VrSrc& s0, const VrSrc* s1, int B, int Hi,
   a.stride = stride; a.dy = dy; a.dx = dx;
   a.sy = Hi > 1 ? (float)(Hi / 2 - 1) / (float)(Hi - 1) : 0.f;
   a.sx = Wi > 1 ? (float)(Wi / 2 - 1) / (float)(Wi - 1) : 0.f;
-  a.wp = cw.w; a.bias = cw.b; a.act = act;
+  a.wp = bf ? static_cast<const void*>(cw.wb) : cw.w; a.bias = cw.b; a.act = act;
   a.out = o.p; a.obs = o.bs; a.oys = o.ys; a.oxs = o.xs; a.cout = cw.cout;
   // output tiles per wave: the fewest padded tiles among 4, 3 and 2, the larger count on a tie
   const int ct = ctiles(cw.cout);
@@ -710,13 +745,16 @@ int launch_conv(const Conv& cw, const VrSrc& s0, const VrSrc* s1, int B, int Hi,
     set_error("vr: only a 3x3 conv's first source is read through the gather");
     return PD_ERR_ARG;
   }
+  if (bf && !cw.wb) {
+    set_error("vr: the conv has no bf16 weights");
+    return PD_ERR_ARG;
+  }
   ProfScope ps(tag, st);
-  dispatch([&](auto NT) {
+  dispatch([&](auto NT, auto RG, auto BF) {
     dispatch_rows<DispatchRow<1, false>, DispatchRow<9, true>, DispatchRow<9, false>>([&](auto TAPS, auto UP) {
-      if (rg.v) hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT(), true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT(), false>), grid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((vr_conv_kernel<TAPS(), UP(), NT(), RG(), BF()>), grid, dim3(256), 0, st, a);
     }, cw.taps != 9 ? 1 : 9, cw.taps == 9 && up);
-  }, one_of<1, 2, 3, 4>(nt));
+  }, one_of<1, 2, 3, 4>(nt), bool_of(rg.v != nullptr), bool_of(bf));
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -742,13 +780,15 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   float* tmp = ws + wp.tmp;
   float* e[5] = {e1, ws + wp.e[0], ws + wp.e[1], ws + wp.e[2], ws + wp.e[3]};
   const int ec[5] = {n, 2 * n, 4 * n, 6 * n, 8 * n};
-  PD_TRY(launch_conv(nt.enc1, xin, nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dense_out(e1, T, Fb, n), rg, st, "vr_enc_l0"));
+  // every conv of a net takes the handle's operand dtype (PD_VR_OPT_CONV_DTYPE)
+  auto conv = [&](const Conv& cw, auto&&... rest) { return launch_conv(cw, h.bf, rest...); };
+  PD_TRY(conv(nt.enc1, xin, nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dense_out(e1, T, Fb, n), rg, st, "vr_enc_l0"));
   static const char* const ENC_TAG[4] = {"vr_enc_l1", "vr_enc_l2", "vr_enc_l3", "vr_enc_l4"};
   for (int l = 1; l < 5; ++l) {
-    PD_TRY(launch_conv(nt.enc[l - 1][0], dense_src(e[l - 1], Hl[l - 1], Wl[l - 1], ec[l - 1]), nullptr, B, Hl[l - 1],
-                       Wl[l - 1], 2, 1, 1, ACT_LRELU, dense_out(tmp, Hl[l], Wl[l], ec[l]), rg, st, ENC_TAG[l - 1]));
-    PD_TRY(launch_conv(nt.enc[l - 1][1], dense_src(tmp, Hl[l], Wl[l], ec[l]), nullptr, B, Hl[l], Wl[l], 1, 1, 1,
-                       ACT_LRELU, dense_out(e[l], Hl[l], Wl[l], ec[l]), rg, st, ENC_TAG[l - 1]));
+    PD_TRY(conv(nt.enc[l - 1][0], dense_src(e[l - 1], Hl[l - 1], Wl[l - 1], ec[l - 1]), nullptr, B, Hl[l - 1],
+                Wl[l - 1], 2, 1, 1, ACT_LRELU, dense_out(tmp, Hl[l], Wl[l], ec[l]), rg, st, ENC_TAG[l - 1]));
+    PD_TRY(conv(nt.enc[l - 1][1], dense_src(tmp, Hl[l], Wl[l], ec[l]), nullptr, B, Hl[l], Wl[l], 1, 1, 1,
+                ACT_LRELU, dense_out(e[l], Hl[l], Wl[l], ec[l]), rg, st, ENC_TAG[l - 1]));
   }
   // ---- ASPP on the T/16 x Fb/16 map, its five branches written side by side into `cat`
   const int H4 = Hl[4], W4 = Wl[4], c8 = 8 * n;
@@ -763,42 +803,42 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   }
   auto cat_out = [&](int br) { return OutView{cat + (size_t)br * c8, (long long)H4 * W4 * 5 * c8, W4 * 5 * c8, 5 * c8}; };
   const VrSrc e5 = dense_src(e[4], H4, W4, c8);
-  PD_TRY(launch_conv(nt.aspp[0], make_src(pooled, (long long)H4 * c8, c8, 0, c8, false), nullptr, B, H4, W4, 1, 1, 1,
-                     ACT_RELU, cat_out(0), rg, st, "vr_aspp"));
-  PD_TRY(launch_conv(nt.aspp[1], e5, nullptr, B, H4, W4, 1, 1, 1, ACT_RELU, cat_out(1), rg, st, "vr_aspp"));
+  PD_TRY(conv(nt.aspp[0], make_src(pooled, (long long)H4 * c8, c8, 0, c8, false), nullptr, B, H4, W4, 1, 1, 1,
+              ACT_RELU, cat_out(0), rg, st, "vr_aspp"));
+  PD_TRY(conv(nt.aspp[1], e5, nullptr, B, H4, W4, 1, 1, 1, ACT_RELU, cat_out(1), rg, st, "vr_aspp"));
   static const int DIL[3][2] = {{4, 2}, {8, 4}, {12, 6}};   // (bins, frames)
   for (int i = 0; i < 3; ++i)
-    PD_TRY(launch_conv(nt.aspp[2 + i], e5, nullptr, B, H4, W4, 1, DIL[i][1], DIL[i][0], ACT_RELU, cat_out(2 + i), rg, st,
-                       "vr_aspp"));
-  PD_TRY(launch_conv(nt.bott, dense_src(cat, H4, W4, 5 * c8), nullptr, B, H4, W4, 1, 1, 1, ACT_RELU,
-                     dense_out(asp, H4, W4, c8), rg, st, "vr_aspp"));
+    PD_TRY(conv(nt.aspp[2 + i], e5, nullptr, B, H4, W4, 1, DIL[i][1], DIL[i][0], ACT_RELU, cat_out(2 + i), rg, st,
+                "vr_aspp"));
+  PD_TRY(conv(nt.bott, dense_src(cat, H4, W4, 5 * c8), nullptr, B, H4, W4, 1, 1, 1, ACT_RELU,
+              dense_out(asp, H4, W4, c8), rg, st, "vr_aspp"));
   // ---- decoders: bilinear x2 of the map below (read through the gather) cat the skip
   float* d4 = ws + wp.d4;
   float* d3 = ws + wp.d3;
   float* d2 = ws + wp.d2;
   {
     const VrSrc up = dense_src(asp, H4, W4, c8, true), sk = dense_src(e[3], Hl[3], Wl[3], ec[3]);
-    PD_TRY(launch_conv(nt.dec[0], up, &sk, B, Hl[3], Wl[3], 1, 1, 1, ACT_RELU, dense_out(d4, Hl[3], Wl[3], 6 * n), rg, st,
-                       "vr_dec_l3"));
+    PD_TRY(conv(nt.dec[0], up, &sk, B, Hl[3], Wl[3], 1, 1, 1, ACT_RELU, dense_out(d4, Hl[3], Wl[3], 6 * n), rg, st,
+                "vr_dec_l3"));
   }
   {
     const VrSrc up = dense_src(d4, Hl[3], Wl[3], 6 * n, true), sk = dense_src(e[2], Hl[2], Wl[2], ec[2]);
-    PD_TRY(launch_conv(nt.dec[1], up, &sk, B, Hl[2], Wl[2], 1, 1, 1, ACT_RELU, dense_out(d3, Hl[2], Wl[2], 4 * n), rg, st,
-                       "vr_dec_l2"));
+    PD_TRY(conv(nt.dec[1], up, &sk, B, Hl[2], Wl[2], 1, 1, 1, ACT_RELU, dense_out(d3, Hl[2], Wl[2], 4 * n), rg, st,
+                "vr_dec_l2"));
   }
   // dec2's 2 n channels and the LSTM's one, side by side, the pixel stride rounded up to whole 16-byte rows
   const int H1 = Hl[1], W1 = Wl[1], cd2 = 2 * n + 1, sd2 = round_up(cd2, 4);
   {
     const VrSrc up = dense_src(d3, Hl[2], Wl[2], 4 * n, true), sk = dense_src(e[1], H1, W1, ec[1]);
-    PD_TRY(launch_conv(nt.dec[2], up, &sk, B, H1, W1, 1, 1, 1, ACT_RELU, dense_out(d2, H1, W1, sd2), rg, st, "vr_dec_l1"));
+    PD_TRY(conv(nt.dec[2], up, &sk, B, H1, W1, 1, 1, 1, ACT_RELU, dense_out(d2, H1, W1, sd2), rg, st, "vr_dec_l1"));
   }
   // ---- LSTM module over the T/2 frames, input = the Fb/2 bins
   float* lconv = ws + wp.lconv;
   float* xp = ws + wp.xp;
   float* lo = ws + wp.lo;
   const int Hh = nt.hid, G = 4 * Hh;
-  PD_TRY(launch_conv(nt.lconv, make_src(d2, (long long)H1 * W1 * sd2, W1 * sd2, sd2, 2 * n, false), nullptr, B, H1, W1,
-                     1, 1, 1, ACT_RELU, dense_out(lconv, H1, W1, 1), rg, st, "vr_lstm_conv"));
+  PD_TRY(conv(nt.lconv, make_src(d2, (long long)H1 * W1 * sd2, W1 * sd2, sd2, 2 * n, false), nullptr, B, H1, W1,
+              1, 1, 1, ACT_RELU, dense_out(lconv, H1, W1, 1), rg, st, "vr_lstm_conv"));
   PD_TRY(launch_linear(lconv, W1, nt.wih, 2 * G, nt.bl, xp, 2 * G, 1, (long long)B * H1, 2 * G, W1, false, st,
                        "vr_lstm_xproj"));
   {
@@ -813,11 +853,11 @@ int run_net(const pd_vr& h, const Net& nt, const WsPlan& wp, float* ws, int B, i
   {
     const VrSrc up = make_src(d2, (long long)H1 * W1 * sd2, W1 * sd2, sd2, cd2, true), sk = dense_src(e1, T, Fb, n);
     const OutView o = nt.has_tail ? dense_out(ws + wp.d1, T, Fb, n) : dst;
-    PD_TRY(launch_conv(nt.dec1, up, &sk, B, T, Fb, 1, 1, 1, ACT_RELU, o, rg, st, "vr_dec_l0"));
+    PD_TRY(conv(nt.dec1, up, &sk, B, T, Fb, 1, 1, 1, ACT_RELU, o, rg, st, "vr_dec_l0"));
   }
   if (nt.has_tail)
-    PD_TRY(launch_conv(nt.tail, dense_src(ws + wp.d1, T, Fb, n), nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dst, rg, st,
-                       "vr_tail"));
+    PD_TRY(conv(nt.tail, dense_src(ws + wp.d1, T, Fb, n), nullptr, B, T, Fb, 1, 1, 1, ACT_RELU, dst, rg, st,
+                "vr_tail"));
   return PD_OK;
 }
 
@@ -865,7 +905,7 @@ int run_mask(const pd_vr* h, const float* sre, const float* sim, float* mre, flo
   PD_TRY(run_net(*h, h->nets[2], wp, ws, B, T, 0, Fb, x_out(0, nin + q), rg, st));
   PD_TRY(run_net(*h, h->nets[3], wp, ws, B, T, Fb, Fb, x_out(Fb, nin + q), rg, st));
   PD_TRY(run_net(*h, h->nets[4], wp, ws, B, T, 0, F, dense_out(ws + wp.d1, T, F, h->d.nout), rg, st));
-  PD_TRY(launch_conv(h->out, dense_src(ws + wp.d1, T, F, h->d.nout), nullptr, B, T, F, 1, 1, 1, ACT_NONE,
+  PD_TRY(launch_conv(h->out, false, dense_src(ws + wp.d1, T, F, h->d.nout), nullptr, B, T, F, 1, 1, 1, ACT_NONE,
                      dense_out(ws + wp.mout, T, F, nin), rg, st, "vr_out"));
   {
     const long long total = (long long)B * h->C * T * h->nb;
@@ -1031,6 +1071,23 @@ int pd_vr_create(const pd_vr_dims* dims, const float* const* params, int dtype, 
 }
 
 void pd_vr_destroy(pd_vr* h) { delete h; }
+
+int pd_vr_set_option(pd_vr* h, int option, int value, void* stream) {
+  PD_CHECK_ARG(h, "null handle");
+  PD_CHECK_ARG(option == PD_VR_OPT_CONV_DTYPE, "unknown pd_vr option");
+  PD_CHECK_ARG(value == PD_DTYPE_F32 || value == PD_DTYPE_BF16, "PD_VR_OPT_CONV_DTYPE takes PD_DTYPE_F32 or PD_DTYPE_BF16");
+  if (value == PD_DTYPE_BF16 && !h->out.wb) {
+    // the first switch: the pool's bf16 mirror (the conv tiles rounded once more, to nearest even), made on the stream
+    if (!h->weights.bf16()) PD_TRY(h->weights.mirror_bf16((hipStream_t)stream));
+    bool ok = true;
+    auto point = [&](Conv& cw) { cw.wb = lookup_bf16(cw.w); ok = ok && cw.wb; };
+    for (Net& nt : h->nets) each_conv(nt, point);
+    point(h->out);   // not read (`out` stays fp32): marks the mirror as standing
+    if (!ok) { set_error("vr: a conv lies outside the bf16 mirror"); return PD_ERR_HIP; }
+  }
+  h->bf = value == PD_DTYPE_BF16;
+  return PD_OK;
+}
 
 int pd_vr_frames(const pd_vr* h, int n_samples) {
   if (!h || n_samples < 0) return 0;

@@ -454,7 +454,8 @@ class VarianceCurves:
         """A mono waveform [L] or [B, L] (numpy or CUDA tensor) and its f0 -> the curves, through
         ``sep_model.separate`` (a mono CascadedNet) on the current stream.  mel_len: the frame count by default.
         A ragged batch (a list of clips with a list of f0, or padded tensors with ``lens`` and ``f0_lens``) runs
-        one ragged ``separate`` and one ragged curves call and gives lists of per-row curves."""
+        one ragged ``separate`` and one ragged curves call and gives lists of per-row curves.  The separation runs
+        in ``sep_model``'s compute dtype (``CascadedNet.set_compute_dtype``); the curves themselves stay fp32."""
         dev = next(sep_model.parameters()).device
         if _is_ragged(waveform, lens, f0_lens):
             as_np, wav, ns = _stack(waveform, lens, dev)
@@ -487,7 +488,8 @@ def isolate_parts(wav, f0, sep_model, hop_size, win_size, samplerate, base_harmo
     """handler/infer/handler.py:349-358: a vocoder output -> (sp, ap), or with ``base_harmonic``
     (sp - base, ap, base), the subtraction from the synthesis kernel's epilogue.  A ragged batch (a list of
     segments with a list of f0, or padded tensors with ``lens`` and ``f0_lens``) gives lists, each row cut to its
-    own samples, from one ragged ``separate`` and one ragged ``kth_harmonic`` call."""
+    own samples, from one ragged ``separate`` and one ragged ``kth_harmonic`` call.  The separation runs in
+    ``sep_model``'s compute dtype (``CascadedNet.set_compute_dtype``)."""
     dev = next(sep_model.parameters()).device
     if _is_ragged(wav, lens, f0_lens):
         as_np, x, ns = _stack(wav, lens, dev)

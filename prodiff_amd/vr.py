@@ -1,6 +1,7 @@
 """Harmonic-noise separation on the GPU: the reference's modules/vr (``CascadedNet``, ``load_sep_model``) and
 component/binarizer/binarizer_utils.py ``extract_harmonic_aperiodic`` on pd_vr (include/prodiff_hip.h, "harmonic-noise
-separation").  Inference only, fp32 only.
+separation").  Inference only.  fp32 is the default; ``set_compute_dtype("bf16")`` runs every conv but the last
+on the bf16 MFMA (PD_VR_OPT_CONV_DTYPE), all else staying fp32.
 """
 from __future__ import annotations
 
@@ -94,6 +95,16 @@ class CascadedNet(nn.Module):
         self.register_buffer("window", torch.hann_window(n_fft), persistent=False)
         self._native = _lib.NativeHandle("CascadedNet", "pd_vr_create", "pd_vr_destroy", num_params="pd_vr_num_params")
         self._ws = _lib.Workspace()
+        self._compute_dtype = "fp32"
+        self._applied = None      # (handle, compute dtype) of the last pd_vr_set_option
+
+    def set_compute_dtype(self, dtype):
+        """"fp32" (default) or "bf16": the convs' operands (every conv but ``out``); activations, the LSTM, the
+        transforms and the mask stay fp32.  Takes effect at the next call; the handle is not rebuilt."""
+        if dtype not in ("fp32", "bf16"):
+            raise ValueError(f"CascadedNet: compute dtype must be 'fp32' or 'bf16', got {dtype!r}")
+        self._compute_dtype = dtype
+        return self
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         kept = {k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
@@ -109,11 +120,18 @@ class CascadedNet(nn.Module):
 
     def handle(self):
         ps = self.ordered_params()
-        return self._native.get(self._native.signature(ps),
-                                lambda: (self.dims(), [p.detach().float().contiguous() for p in ps]))
+        h = self._native.get(self._native.signature(ps),
+                             lambda: (self.dims(), [p.detach().float().contiguous() for p in ps]))
+        want = (h.value, self._compute_dtype)
+        if self._applied != want and (self._applied is not None or self._compute_dtype != "fp32"):
+            dt = _lib.PD_DTYPE_BF16 if self._compute_dtype == "bf16" else _lib.PD_DTYPE_F32
+            _lib.check(_lib.lib().pd_vr_set_option(h, _lib.PD_VR_OPT_CONV_DTYPE, dt, _lib.stream_ptr(ps[0].device)))
+        self._applied = want
+        return h
 
     def close(self):
         self._native.close()
+        self._applied = None
 
     # ---------------------------------------------------------------- the three stages on planar spectra
     def _check_wav(self, x):
@@ -260,8 +278,9 @@ class CascadedNet(nn.Module):
         return self.separate(x, lens)[0]
 
 
-def load_sep_model(model_path, device="cuda"):
-    """modules/vr/__init__.py:18-35: the model described by ``config.yaml`` beside the checkpoint."""
+def load_sep_model(model_path, device="cuda", *, compute_dtype="fp32"):
+    """modules/vr/__init__.py:18-35: the model described by ``config.yaml`` beside the checkpoint;
+    ``compute_dtype``: ``CascadedNet.set_compute_dtype``."""
     import yaml
     model_path = pathlib.Path(model_path)
     with open(model_path.with_name("config.yaml"), "r") as f:
@@ -269,7 +288,7 @@ def load_sep_model(model_path, device="cuda"):
     model = CascadedNet(args["n_fft"], args["hop_length"], args["n_out"], args["n_out_lstm"], True,
                         is_mono=args["is_mono"])
     model.load_state_dict(torch.load(model_path, map_location="cpu", weights_only=True))
-    return model.to(device).eval()
+    return model.to(device).eval().set_compute_dtype(compute_dtype)
 
 
 SEP_MODEL = None
@@ -279,7 +298,8 @@ def extract_harmonic_aperiodic(waveform, model_path=None, device="cuda"):
     """component/binarizer/binarizer_utils.py:99-113: a mono waveform (numpy [L]) -> (harmonic, aperiodic) numpy [L].  The model is
     loaded on the first call and kept at module level, as in the reference; ``model_path`` may also be a
     ``CascadedNet``.  A list or tuple of mono waveforms of different lengths goes through one ragged
-    ``separate`` call and gives a list of (harmonic, aperiodic), each pair what its clip gives alone."""
+    ``separate`` call and gives a list of (harmonic, aperiodic), each pair what its clip gives alone.  The model's
+    own compute dtype (``set_compute_dtype``) applies."""
     global SEP_MODEL
     if isinstance(model_path, CascadedNet):
         model = model_path
