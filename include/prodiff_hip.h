@@ -701,7 +701,7 @@ int pd_mel_create_centered(const pd_mel_dims* dims, const float* mel_basis, void
  *   ConvBlockRes(x) = ReLU(BN(conv3x3(ReLU(BN(conv3x3(x)))))) + s(x), s = identity, or a 1x1 conv with bias
  * when the channel count changes.  Every BatchNorm is the eval form (eps 1e-5); create folds each post-conv one
  * into its conv in double precision (w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps)), rounded
- * once.  fp32 only. */
+ * once.  fp32 by default; pd_rmvpe_set_option below moves the 3x3 convs' operands and the recurrent product to bf16. */
 typedef struct pd_rmvpe pd_rmvpe;
 
 typedef struct {
@@ -735,6 +735,26 @@ int pd_rmvpe_num_params(const pd_rmvpe_dims* dims);
 int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int dtype, void* stream, pd_rmvpe** out);
 /* The caller must ensure that no call on the handle is still in flight (synchronize its streams first). */
 void pd_rmvpe_destroy(pd_rmvpe* h);
+/* Two options of the handle, each PD_DTYPE_F32 (the default) or PD_DTYPE_BF16; pd_rmvpe_create itself takes
+ * PD_DTYPE_F32 only.
+ *   PD_RMVPE_OPT_CONV_DTYPE  bf16: every 3x3 conv with C_in a multiple of 16 (all but the first conv and `cnn`), its
+ *       1x1-shortcut accumulator, the transposed convs and the two-source cat form run on v_mfma_f32_32x32x16_bf16.
+ *       The input values are rounded once to bf16 (nearest even) after the in-image select, so border and stuffed
+ *       zeros stay zeros, and meet the bf16 copy of the folded weights (the f32 folded value as create rounds it,
+ *       rounded once more).  Accumulation, folded bias, ReLU, residual add and every stored map stay fp32.
+ *   PD_RMVPE_OPT_GRU_DTYPE   bf16: the recurrent product is bf16(h_{t-1}) bf16(W_hh)^T on v_mfma_f32_16x16x32_bf16,
+ *       summed in f32; b_hh, the gates and the blend h = (1 - z) n + z h_{t-1} use the unrounded fp32 h_{t-1}; the
+ *       output and the carried state are fp32.  Without a GRU (n_gru = 0) the option is accepted and has no effect.
+ * The first conv, `cnn`, the pools, the W_ih projection, the head and the sigmoid are fp32 in every mode.  The first
+ * switch of either option to bf16 allocates the bf16 mirror of the weight pool and fills it on `stream`
+ * (pd_live_device_bytes counts it, pd_rmvpe_destroy returns it); later switches only flip the mode and touch
+ * nothing.  Workspace sizes do not change.  With both options at PD_DTYPE_F32 every kernel launched is the one
+ * launched without this call.  The bit-exact promises of pd_rmvpe_forward and pd_rmvpe_forward_ragged (rows,
+ * batch position, ragged rows against their single runs) hold within one mode.  The caller must ensure that no
+ * call on the handle is in flight.  A null handle, an unknown option or any other value: PD_ERR_ARG, nothing changes. */
+#define PD_RMVPE_OPT_CONV_DTYPE 0
+#define PD_RMVPE_OPT_GRU_DTYPE 1
+int pd_rmvpe_set_option(pd_rmvpe* h, int option, int value, void* stream);
 size_t pd_rmvpe_workspace_size(const pd_rmvpe* h, int B, int T);
 /* mel [B][T][n_mels] time-major natural-log mel (what pd_mel_forward writes) -> hidden [B][T][n_class], the
  * salience in [0, 1]; feat [B][T][3 n_mels] (the cnn output, feature index c n_mels + f) or NULL.  T must be a

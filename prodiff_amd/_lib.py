@@ -20,6 +20,8 @@ FD_OPTIONS = {"lvc_ts": 0, "lvc_fuse": 2, "lvc_pf": 3, "lvc_sub": 4, "kp_chunk":
 NSF_OPTIONS = {"small_max": 0, "wconv": 1, "pair": 2, "pair16": 3, "ups_nc": 4, "rb16": 5, "rb32": 6, "rb64": 7, "c256": 8, "nc_mfma": 9}
 WN_OPTIONS = {"layer": 0, "ksplit": 1, "l2pf": 2, "stack": 3, "stack_ro": 4, "stack_fuse": 6, "f32_layer": 7}
 PD_VR_OPT_CONV_DTYPE = 0   # pd_vr_set_option
+PD_RMVPE_OPT_CONV_DTYPE = 0   # pd_rmvpe_set_option
+PD_RMVPE_OPT_GRU_DTYPE = 1
 
 
 class HipError(RuntimeError):
@@ -193,6 +195,7 @@ _SIGS = {
     "pd_rmvpe_destroy": (None, [_VP]),
     "pd_rmvpe_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "pd_rmvpe_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_rmvpe_set_option": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pd_rmvpe_forward_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "pd_rmvpe_decode": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_double, _VP]),
     "pd_rmvpe_viterbi_chunk": (C.c_int, []),

@@ -1,6 +1,7 @@
 // RMVPE pitch extractor (include/prodiff_hip.h, "pitch extraction"): E2E0 of modules/rmvpe/model.py -- the deep
 // U-Net of deepunet.py, the 3-channel output conv, the BiGRU of seq.py and the 360-class sigmoid head -- and
-// to_local_average_f0 of modules/rmvpe/utils.py.  fp32 only.
+// to_local_average_f0 of modules/rmvpe/utils.py.  fp32; pd_rmvpe_set_option moves the MFMA convs' operands
+// (conv3x3_kernel's BF instance) and the recurrent product (gru_bf16_kernel) to bf16, all else staying fp32.
 //
 // Activations are channels-last images [B][T][F][C] (T = frames, F = mel bins), so the time-major log-mel
 // that pd_mel_forward writes already is the one-channel input image.
@@ -99,10 +100,10 @@ struct ConvArgs {
   int c0, c1;
   int H, W;            // output image; the source is H x W, or H/2 x W/2 when stuffed
   int stuffed;
-  const float* wp;     // packed [ctiles][nchunk][9][32][16]
+  const void* wp;      // packed [ctiles][nchunk][9][32][16]: float, or (BF) the tiles' bf16 copy
   const float* bias;   // [ctiles * 32]
   int relu;
-  const float* wsp;    // SC: packed 1x1 [ctiles][nchunk][32][16]
+  const void* wsp;     // SC: packed 1x1 [ctiles][nchunk][32][16], float or (BF) bf16
   const float* bsc;    // SC: [ctiles * 32]
   float* sc_out;       // SC: [B][H][W][cout]
   const float* resid;  // [B][H][W][cout] or null, added after the ReLU
@@ -113,9 +114,16 @@ struct ConvArgs {
   int lvl;
 };
 
-template <bool SC>
+// BF: the staged values -- selected against the image border and the stuffed zeros in f32 exactly as without it --
+// are rounded once to bf16 (nearest even) as they go to LDS, 32 bytes per window pixel, and meet the bf16 copy of the
+// packed tiles (the pool's mirror) in one v_mfma_f32_32x32x16_bf16 per tap and chunk: lane (r, h) holds channels
+// 8 h .. 8 h + 7 of pixel r (A) and of output channel r (B), the 16 bytes the f32 form reads as two float4.
+// Accumulators, bias, ReLU, residual and every stored map are f32, and the D layout is the f32 form's.
+template <bool SC, bool BF = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
-  __shared__ __attribute__((aligned(16))) float xs[CV_MAXWIN * CV_LD];
+  using TS = std::conditional_t<BF, __bf16, float>;
+  constexpr int LD = BF ? CV_CK : CV_LD;
+  __shared__ __attribute__((aligned(16))) TS xs[CV_MAXWIN * LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int b = blockIdx.z, ct = blockIdx.y;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
@@ -129,10 +137,10 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
   const int Hsb = a.stuffed ? Hb >> 1 : Hb;
   // the A operand of this lane: pixel m of the tile, channels 8 h .. 8 h + 7 of the chunk
   const int m = wave * 32 + r, pr = m / a.tc, pc = m - pr * a.tc;
-  const float* abase = xs + (pr * wc + pc) * CV_LD + h * 8;
+  const TS* abase = xs + (pr * wc + pc) * LD + h * 8;
   const int nchunk = (a.c0 + a.c1) / CV_CK;
-  const float* wrow = a.wp + ((long long)ct * nchunk * 9 * 32 + r) * 16 + h * 8;
-  const float* wsrow = SC ? a.wsp + ((long long)ct * nchunk * 32 + r) * 16 + h * 8 : nullptr;
+  const TS* wrow = static_cast<const TS*>(a.wp) + ((long long)ct * nchunk * 9 * 32 + r) * 16 + h * 8;
+  const TS* wsrow = SC ? static_cast<const TS*>(a.wsp) + ((long long)ct * nchunk * 32 + r) * 16 + h * 8 : nullptr;
 
   f32x16 acc, acc2;
 #pragma unroll
@@ -144,11 +152,18 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
     const float* src = first ? a.src0 : a.src1;
     const int cs = first ? a.c0 : a.c1, coff = first ? cb : cb - a.c0;
     // the chunk's weights are requested first: their L2 latency passes under the staging of the window
-    const float* wch = wrow + (long long)chunk * 9 * 512;
-    float wf[9][8], sf[8];
+    const TS* wch = wrow + (long long)chunk * 9 * 512;
+    float wf[BF ? 1 : 9][8], sf[8];
+    bf16x8 wb[BF ? 9 : 1], sb;
+    if constexpr (BF) {
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) load8(wch + tap * 512, wf[tap]);
-    if (SC) load8(wsrow + (long long)chunk * 512, sf);
+      for (int tap = 0; tap < 9; ++tap) wb[tap] = *reinterpret_cast<const bf16x8*>(wch + tap * 512);
+      if (SC) sb = *reinterpret_cast<const bf16x8*>(wsrow + (long long)chunk * 512);
+    } else {
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) load8(wch + tap * 512, wf[tap]);
+      if (SC) load8(wsrow + (long long)chunk * 512, sf);
+    }
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();   // the previous chunk's reads are done
     for (int idx = tid; idx < winpix * 4; idx += 256) {
@@ -162,18 +177,29 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
       sx = min(max(sx, 0), Ws - 1);
       float4 v = *reinterpret_cast<const float4*>(src + (((long long)b * Hs + sy) * Ws + sx) * cs + coff + q * 4);
       if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(xs + p * CV_LD + q * 4) = v;
+      if constexpr (BF) {
+        const bf16x4 vb = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
+        *reinterpret_cast<bf16x4*>(xs + p * LD + q * 4) = vb;
+      } else {
+        *reinterpret_cast<float4*>(xs + p * LD + q * 4) = v;
+      }
     }
     __syncthreads();
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-      float af[8];
-      load8(abase + ((tap / 3) * wc + (tap % 3)) * CV_LD, af);
+      if constexpr (BF) {
+        const bf16x8 ab = *reinterpret_cast<const bf16x8*>(abase + ((tap / 3) * wc + (tap % 3)) * LD);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, wb[tap], acc, 0, 0, 0);
+        if (SC && tap == 4) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, sb, acc2, 0, 0, 0);
+      } else {
+        float af[8];
+        load8(abase + ((tap / 3) * wc + (tap % 3)) * LD, af);
 #pragma unroll
-      for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], wf[tap][kk], acc, 0, 0, 0);
-      if (SC && tap == 4) {
+        for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], wf[tap][kk], acc, 0, 0, 0);
+        if (SC && tap == 4) {
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], sf[kk], acc2, 0, 0, 0);
+          for (int kk = 0; kk < 8; ++kk) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], sf[kk], acc2, 0, 0, 0);
+        }
       }
     }
   }
@@ -421,6 +447,113 @@ __global__ __launch_bounds__(512) void gru_kernel(const GruArgs a) {
   }
 }
 
+// The recurrence with hp = bf16(h) bf16(W_hh)^T on v_mfma_f32_16x16x32_bf16 (PD_RMVPE_OPT_GRU_DTYPE): the grid, the
+// block's 16 batch rows, wave w's units 32 w .. 32 w + 31 of the three gates, the D layout and the ragged rule are
+// gru_kernel's.  Lane (r, g) supplies k = 8 g .. 8 g + 7 of a 32-deep chunk j: A is one 16-byte read of the bf16 copy
+// of h that LDS keeps beside the f32 one, B is unit r of the pack's 16-chunk 2 j + (g >> 1) at element 8 (g & 1) in
+// the pool's bf16 mirror.  A wave's 48 KiB of W_hh stay on chip over the whole time loop: gates r and z in 128
+// registers per lane, gate n in LDS as the lane's own sixteen 16-byte items ([wave][item][lane]: a wave's read is
+// 1 KiB of consecutive bytes).  Each of the six accumulators is one chain over j = 0 .. 7; b_hh, the gates and the
+// blend are f32 on the unrounded h, as in gru_kernel.
+constexpr int GRU_LDB = GRU_H + 8;   // bf16 per row of h's copy: 528 bytes, the 16 rows of a read 16 bytes apart mod 256
+constexpr size_t GRU_BF_LDS = (size_t)8 * 16 * 64 * 16 + GRU_ROWS * GRU_LD * sizeof(float) + GRU_ROWS * GRU_LDB * sizeof(__bf16);
+
+template <bool RAGGED>
+__global__ __launch_bounds__(512) void gru_bf16_kernel(const GruArgs a, const __bf16* __restrict__ whh) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gru_lds[];
+  bf16x8* wn = reinterpret_cast<bf16x8*>(gru_lds);                                  // [8][16][64]
+  float* hs = reinterpret_cast<float*>(gru_lds + (size_t)8 * 16 * 64 * 16);          // [16][GRU_LD]
+  __bf16* hb = reinterpret_cast<__bf16*>(hs + GRU_ROWS * GRU_LD);                    // [16][GRU_LDB]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
+  const int dir = blockIdx.x, b0 = blockIdx.y * GRU_ROWS, nb = min(GRU_ROWS, a.B - b0);
+  for (int i = tid; i < GRU_ROWS * GRU_LD; i += 512) hs[i] = 0.f;
+  for (int i = tid; i < GRU_ROWS * GRU_LDB; i += 512) hb[i] = (__bf16)0.f;
+  int steps = a.T, nfr[4] = {0, 0, 0, 0};
+  if (RAGGED) {
+    steps = 0;
+    for (int i = 0; i < nb; ++i) steps = max(steps, padded_frames(a.rf, b0 + i));
+    steps = __builtin_amdgcn_readfirstlane(steps);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) nfr[i] = 4 * g + i < nb ? padded_frames(a.rf, b0 + 4 * g + i) : 0;
+  }
+  const float* bh = a.bhh + dir * 3 * GRU_H;
+  float bhr[2], bhz[2], bhn[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int n = wave * 32 + s * 16 + r;
+    bhr[s] = bh[n]; bhz[s] = bh[GRU_H + n]; bhn[s] = bh[2 * GRU_H + n];
+  }
+  // packed W_hh [dir][gate * 8 + wave][16-chunk][32][16] in bf16: the lane's 16 bytes of tile (gate, s), chunk j
+  const __bf16* wdir = whh + (long long)dir * 24 * 16 * 512;
+  auto wptr = [&](int gate, int s, int j) {
+    return reinterpret_cast<const bf16x8*>(wdir + ((gate * 8 + wave) * 16 + 2 * j + (g >> 1)) * 512 + (s * 16 + r) * 16 +
+                                           8 * (g & 1));
+  };
+  bf16x8 wreg[4][8];   // gates r, z: [gate * 2 + s][j]
+#pragma unroll
+  for (int gs = 0; gs < 4; ++gs)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wreg[gs][j] = *wptr(gs >> 1, gs & 1, j);
+  bf16x8* wmine = wn + wave * 16 * 64 + lane;
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wmine[(s * 8 + j) * 64] = *wptr(2, s, j);
+  const __bf16* arow = hb + r * GRU_LDB + 8 * g;
+  __syncthreads();
+  for (int step = 0; step < steps; ++step) {
+    const int t = dir ? steps - 1 - step : step;
+    float xr[8], xz[8], xn[8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * g + i;
+        const float* px = a.xp + ((long long)(b0 + min(row, nb - 1)) * a.T + t) * (6 * GRU_H) + dir * 3 * GRU_H +
+                          wave * 32 + s * 16 + r;
+        xr[s * 4 + i] = px[0];
+        xz[s * 4 + i] = px[GRU_H];
+        xn[s * 4 + i] = px[2 * GRU_H];
+      }
+    f32x4 acc[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bf16x8 hv = *reinterpret_cast<const bf16x8*>(arow + j * 32);
+#pragma unroll
+      for (int gs = 0; gs < 4; ++gs) acc[gs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hv, wreg[gs][j], acc[gs], 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        acc[4 + s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hv, wmine[(s * 8 + j) * 64], acc[4 + s], 0, 0, 0);
+    }
+    float hnew[8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float hold = hs[(4 * g + i) * GRU_LD + wave * 32 + s * 16 + r];
+        const float rg = sigmoid_exp(xr[s * 4 + i] + (acc[s][i] + bhr[s]));
+        const float zg = sigmoid_exp(xz[s * 4 + i] + (acc[2 + s][i] + bhz[s]));
+        const float ng = tanh_exp(xn[s * 4 + i] + rg * (acc[4 + s][i] + bhn[s]));
+        hnew[s * 4 + i] = (1.f - zg) * ng + zg * hold;
+      }
+    __syncthreads();   // every wave has read h
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * g + i, n = wave * 32 + s * 16 + r;
+        if (RAGGED ? t < nfr[i] : row < nb) {
+          hs[row * GRU_LD + n] = hnew[s * 4 + i];
+          hb[row * GRU_LDB + n] = (__bf16)hnew[s * 4 + i];
+          a.out[((long long)(b0 + row) * a.T + t) * (2 * GRU_H) + dir * GRU_H + n] = hnew[s * 4 + i];
+        }
+      }
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(256) void sigmoid_kernel(const float* __restrict__ x, float* __restrict__ out, long long n) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = sigmoid_exp(x[i]);
@@ -464,6 +597,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
 // ------------------------------------------------------------------ host side
 struct ConvW {
   float* w = nullptr;    // packed main weights
+  const __bf16* wb = nullptr;   // w's bf16 copy, from the first switch of an option to PD_DTYPE_BF16 on
   float* b = nullptr;    // folded bias [ctiles * 32]
   int cin = 0, cout = 0;
 };
@@ -471,6 +605,7 @@ struct ConvW {
 struct Block {
   ConvW c1, c2;
   float* ws = nullptr;   // packed 1x1 shortcut (cin != cout)
+  const __bf16* wsb = nullptr;
   float* bs = nullptr;
   bool sc = false;
   int cin = 0, cout = 0;
@@ -492,7 +627,10 @@ bool dims_ok(const pd_rmvpe_dims& d) {
 
 struct pd_rmvpe {
   pd_rmvpe_dims d;
-  WeightPool weights;
+  // `weights` is the pool the bf16 mirror copies; `gemm_weights` holds what the GEMM engine reads (W_ih, the head and
+  // their biases) and is never mirrored: launch_gemm takes the bf16 copy of any weight inside a mirrored pool, and
+  // these two products stay fp32 in every mode.
+  WeightPool weights, gemm_weights;
   float* inbn = nullptr;                 // encoder.bn {scale, shift}
   float *w_in = nullptr, *b_in = nullptr, *ws_in = nullptr, *bs_in = nullptr;   // first conv [c0][9], shortcut [c0]
   std::vector<std::vector<Block>> enc, inter, dec;   // enc[0][0].c1 / its shortcut are the *_in tensors above
@@ -501,6 +639,9 @@ struct pd_rmvpe {
   float *w_ih = nullptr, *b_ih = nullptr, *w_hh = nullptr, *b_hh = nullptr;   // both directions
   float *w_fc = nullptr, *b_fc = nullptr;
   int fc_in = 0;
+  const __bf16* w_hh_b = nullptr;        // w_hh's bf16 copy
+  bool mirrored = false;                 // the mirror stands and every wb / wsb / w_hh_b points into it
+  bool bf_conv = false, bf_gru = false;  // PD_RMVPE_OPT_CONV_DTYPE, PD_RMVPE_OPT_GRU_DTYPE
 };
 
 namespace {
@@ -539,12 +680,12 @@ const char* const TAG_CONVT[6] = {"rmvpe_convT_l0", "rmvpe_convT_l1", "rmvpe_con
 
 int launch_conv(const ConvW& cw, const float* src0, int c0, const float* src1, int c1, int B, int H, int W,
                 bool stuffed, const Block* sc, float* sc_out, const float* resid, float* out, hipStream_t st,
-                int lvl, const RowFrames& rf) {
+                int lvl, const RowFrames& rf, bool bf) {
   ConvArgs a{};
   a.rf = rf; a.lvl = lvl;
   a.src0 = src0; a.src1 = src1 ? src1 : src0; a.c0 = c0; a.c1 = src1 ? c1 : 0;
   a.H = H; a.W = W; a.stuffed = stuffed ? 1 : 0;
-  a.wp = cw.w; a.bias = cw.b; a.relu = 1;
+  a.wp = bf ? (const void*)cw.wb : (const void*)cw.w; a.bias = cw.b; a.relu = 1;
   a.resid = resid; a.out = out; a.cout = cw.cout;
   a.tc = W >= 16 ? 16 : (W >= 8 ? 8 : 4);   // a narrower image leaves tile columns unused
   a.tr = CV_PIX / a.tc;
@@ -553,13 +694,19 @@ int launch_conv(const ConvW& cw, const float* src0, int c0, const float* src1, i
     set_error("rmvpe: conv shape the kernel does not take");
     return PD_ERR_ARG;
   }
+  if (bf && (!cw.wb || (sc && !sc->wsb))) {
+    set_error("rmvpe: the conv has no bf16 weights");
+    return PD_ERR_HIP;
+  }
   const dim3 grid(a.tiles_x * cdiv(H, a.tr), ctiles(cw.cout), B);
   ProfScope ps((stuffed ? TAG_CONVT : sc ? TAG_CONV_SC : TAG_CONV)[lvl], st);
   if (sc) {
-    a.wsp = sc->ws; a.bsc = sc->bs; a.sc_out = sc_out;
-    hipLaunchKernelGGL(conv3x3_kernel<true>, grid, dim3(256), 0, st, a);
+    a.wsp = bf ? (const void*)sc->wsb : (const void*)sc->ws; a.bsc = sc->bs; a.sc_out = sc_out;
+    if (bf) hipLaunchKernelGGL((conv3x3_kernel<true, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(conv3x3_kernel<true>, grid, dim3(256), 0, st, a);
   } else {
-    hipLaunchKernelGGL(conv3x3_kernel<false>, grid, dim3(256), 0, st, a);
+    if (bf) hipLaunchKernelGGL((conv3x3_kernel<false, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(conv3x3_kernel<false>, grid, dim3(256), 0, st, a);
   }
   PD_LAUNCH_CHECK();
   return PD_OK;
@@ -567,13 +714,13 @@ int launch_conv(const ConvW& cw, const float* src0, int c0, const float* src1, i
 
 // ConvBlockRes: x (c0 [+ c1 from x1] channels) -> out; h1 and scb are scratch, none of the four may alias
 int run_block(const Block& bk, const float* x, int c0, const float* x1, int c1, int B, int H, int W, float* h1,
-              float* scb, float* out, hipStream_t st, int lvl, const RowFrames& rf) {
+              float* scb, float* out, hipStream_t st, int lvl, const RowFrames& rf, bool bf) {
   if (bk.sc) {
-    PD_TRY(launch_conv(bk.c1, x, c0, x1, c1, B, H, W, false, &bk, scb, nullptr, h1, st, lvl, rf));
-    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, out, st, lvl, rf));
+    PD_TRY(launch_conv(bk.c1, x, c0, x1, c1, B, H, W, false, &bk, scb, nullptr, h1, st, lvl, rf, bf));
+    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, out, st, lvl, rf, bf));
   } else {
-    PD_TRY(launch_conv(bk.c1, x, c0, nullptr, 0, B, H, W, false, nullptr, nullptr, nullptr, h1, st, lvl, rf));
-    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, x, out, st, lvl, rf));
+    PD_TRY(launch_conv(bk.c1, x, c0, nullptr, 0, B, H, W, false, nullptr, nullptr, nullptr, h1, st, lvl, rf, bf));
+    PD_TRY(launch_conv(bk.c2, h1, bk.cout, nullptr, 0, B, H, W, false, nullptr, nullptr, x, out, st, lvl, rf, bf));
   }
   return PD_OK;
 }
@@ -583,6 +730,7 @@ int run_block(const Block& bk, const float* x, int c0, const float* x1, int c1, 
 void add_weights(pd_rmvpe* h, ParamView& pv, hipStream_t st) {
   const pd_rmvpe_dims& d = h->d;
   WeightPool& wp = h->weights;
+  WeightPool& gp = h->gemm_weights;
   const int L = d.en_de_layers, c0 = d.en_out_channels;
   struct Bn { const float *g, *beta, *mean, *var; };   // weight, bias, running_mean, running_var
   auto next_bn = [&]() { return Bn{pv.next(), pv.next(), pv.next(), pv.next()}; };
@@ -656,14 +804,14 @@ void add_weights(pd_rmvpe* h, ParamView& pv, hipStream_t st) {
     const float* g[2][4];
     for (int dir = 0; dir < 2; ++dir)
       for (int k = 0; k < 4; ++k) g[dir][k] = pv.next();
-    auto add_dirs = [&](float** slot, size_t per, int k) {
-      wp.add(slot, 2 * per, [=](float* dst) {
+    auto add_dirs = [&](WeightPool& pool, float** slot, size_t per, int k) {
+      pool.add(slot, 2 * per, [=](float* dst) {
         for (int dir = 0; dir < 2; ++dir) PD_TRY(copy_f32(dst + dir * per, g[dir][k], per, st));
         return PD_OK;
       });
     };
-    add_dirs(&h->w_ih, (size_t)3 * GRU_H * feat_c, 0);
-    add_dirs(&h->b_ih, 3 * GRU_H, 2);
+    add_dirs(gp, &h->w_ih, (size_t)3 * GRU_H * feat_c, 0);
+    add_dirs(gp, &h->b_ih, 3 * GRU_H, 2);
     const size_t whh = (size_t)3 * GRU_H * GRU_H;
     wp.add(&h->w_hh, 2 * whh, [=](float* dst) {
       for (int dir = 0; dir < 2; ++dir) {
@@ -672,13 +820,13 @@ void add_weights(pd_rmvpe* h, ParamView& pv, hipStream_t st) {
       }
       return PD_OK;
     });
-    add_dirs(&h->b_hh, 3 * GRU_H, 3);
+    add_dirs(wp, &h->b_hh, 3 * GRU_H, 3);
     h->fc_in = 2 * GRU_H;
   } else {
     h->fc_in = feat_c;
   }
-  wp.add_copy(&h->w_fc, (size_t)d.n_class * h->fc_in, pv.next());
-  wp.add_copy(&h->b_fc, d.n_class, pv.next());
+  gp.add_copy(&h->w_fc, (size_t)d.n_class * h->fc_in, pv.next());
+  gp.add_copy(&h->b_fc, d.n_class, pv.next());
 }
 
 }  // namespace
@@ -707,11 +855,40 @@ int pd_rmvpe_create(const pd_rmvpe_dims* dims, const float* const* params, int d
   add_weights(h.get(), pv, st);
   PD_TRY(pv.done("pd_rmvpe"));
   PD_TRY(h->weights.commit(st, "rmvpe"));
+  PD_TRY(h->gemm_weights.commit(st, "rmvpe"));
   *out = h.release();
   return PD_OK;
 }
 
 void pd_rmvpe_destroy(pd_rmvpe* h) { delete h; }
+
+int pd_rmvpe_set_option(pd_rmvpe* h, int option, int value, void* stream) {
+  PD_CHECK_ARG(h, "null handle");
+  PD_CHECK_ARG(option == PD_RMVPE_OPT_CONV_DTYPE || option == PD_RMVPE_OPT_GRU_DTYPE, "unknown pd_rmvpe option");
+  PD_CHECK_ARG(value == PD_DTYPE_F32 || value == PD_DTYPE_BF16, "a pd_rmvpe dtype option takes PD_DTYPE_F32 or PD_DTYPE_BF16");
+  if (value == PD_DTYPE_BF16 && !h->mirrored) {
+    // the first switch: the pool's bf16 mirror (the conv tiles and the W_hh pack rounded once more, to nearest even),
+    // made on the stream
+    if (!h->weights.bf16()) PD_TRY(h->weights.mirror_bf16((hipStream_t)stream));
+    bool ok = true;
+    auto point = [&](ConvW& cw) { if (cw.w) { cw.wb = lookup_bf16(cw.w); ok = ok && cw.wb; } };
+    auto stage = [&](std::vector<Block>& v) {
+      for (Block& bk : v) {
+        point(bk.c1); point(bk.c2);
+        if (bk.ws) { bk.wsb = lookup_bf16(bk.ws); ok = ok && bk.wsb; }
+      }
+    };
+    for (auto& v : h->enc) stage(v);
+    for (auto& v : h->inter) stage(v);
+    for (auto& v : h->dec) stage(v);
+    for (ConvW& cw : h->up) point(cw);
+    if (h->w_hh) { h->w_hh_b = lookup_bf16(h->w_hh); ok = ok && h->w_hh_b; }
+    if (!ok) { set_error("rmvpe: a weight lies outside the bf16 mirror"); return PD_ERR_HIP; }
+    h->mirrored = true;
+  }
+  (option == PD_RMVPE_OPT_CONV_DTYPE ? h->bf_conv : h->bf_gru) = value == PD_DTYPE_BF16;
+  return PD_OK;
+}
 
 size_t pd_rmvpe_workspace_size(const pd_rmvpe* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) return 0;
@@ -746,6 +923,7 @@ int forward_impl(const pd_rmvpe* h, const float* mel, const int* frames, float* 
   float* h1 = ws + wsp.tmp[2];
   float* scb = ws + wsp.tmp[3];
   float* featb = feat ? feat : ws + wsp.feat;
+  const bool bf = h->bf_conv;
 
   // ---- encoder
   const float* cur = nullptr;   // the level's input (after the pool), in ping or pong
@@ -763,9 +941,9 @@ int forward_impl(const pd_rmvpe* h, const float* mel, const int* frames, float* 
                              h->ws_in, h->bs_in, h1, scb, H, W, cout, total, rf);
           PD_LAUNCH_CHECK();
         }
-        PD_TRY(launch_conv(lv[0].c2, h1, cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, dst, st, i, rf));
+        PD_TRY(launch_conv(lv[0].c2, h1, cout, nullptr, 0, B, H, W, false, nullptr, nullptr, scb, dst, st, i, rf, bf));
       } else {
-        PD_TRY(run_block(lv[j], cur, lv[j].cin, nullptr, 0, B, H, W, h1, scb, dst, st, i, rf));
+        PD_TRY(run_block(lv[j], cur, lv[j].cin, nullptr, 0, B, H, W, h1, scb, dst, st, i, rf, bf));
       }
       cur = dst;
     }
@@ -785,7 +963,7 @@ int forward_impl(const pd_rmvpe* h, const float* mel, const int* frames, float* 
       for (int j = 0; j < d.n_blocks; ++j) {
         const Block& bk = h->inter[i][j];
         float* dst = cur == ping ? pong : ping;
-        PD_TRY(run_block(bk, cur, bk.cin, nullptr, 0, B, H, W, h1, scb, dst, st, L, rf));
+        PD_TRY(run_block(bk, cur, bk.cin, nullptr, 0, B, H, W, h1, scb, dst, st, L, rf, bf));
         cur = dst;
       }
   }
@@ -794,13 +972,13 @@ int forward_impl(const pd_rmvpe* h, const float* mel, const int* frames, float* 
     const int lvl = L - 1 - i, H = T >> lvl, W = F >> lvl, cout = c0 << lvl;
     float* upb = cur == ping ? pong : ping;
     PD_TRY(launch_conv(h->up[i], cur, 2 * cout, nullptr, 0, B, H, W, true, nullptr, nullptr, nullptr, upb, st,
-                       lvl, rf));
+                       lvl, rf, bf));
     cur = upb;
     for (int j = 0; j < d.n_blocks; ++j) {
       const Block& bk = h->dec[i][j];
       float* dst = cur == ping ? pong : ping;
-      if (j == 0) PD_TRY(run_block(bk, cur, cout, skip[lvl], cout, B, H, W, h1, scb, dst, st, lvl, rf));
-      else PD_TRY(run_block(bk, cur, cout, nullptr, 0, B, H, W, h1, scb, dst, st, lvl, rf));
+      if (j == 0) PD_TRY(run_block(bk, cur, cout, skip[lvl], cout, B, H, W, h1, scb, dst, st, lvl, rf, bf));
+      else PD_TRY(run_block(bk, cur, cout, nullptr, 0, B, H, W, h1, scb, dst, st, lvl, rf, bf));
       cur = dst;
     }
   }
@@ -823,10 +1001,21 @@ int forward_impl(const pd_rmvpe* h, const float* mel, const int* frames, float* 
     PD_TRY((launch_gemm<1, 2, 4, 1, EPI_STORE, U_RMVPE_XPROJ>(g, st, "rmvpe_gru_xproj")));
     GruArgs ga{xp, h->w_hh, h->b_hh, go, B, T, rf};
     {
-      ProfScope ps("rmvpe_gru", st);
-      if (frames) hipLaunchKernelGGL(gru_kernel<true>, dim3(2, cdiv(B, GRU_ROWS)), dim3(512), 0, st, ga);
-      else hipLaunchKernelGGL(gru_kernel<false>, dim3(2, cdiv(B, GRU_ROWS)), dim3(512), 0, st, ga);
-      PD_LAUNCH_CHECK();
+      const dim3 grid(2, cdiv(B, GRU_ROWS));
+      if (h->bf_gru) {
+        if (!h->w_hh_b) { set_error("rmvpe: the recurrence has no bf16 weights"); return PD_ERR_HIP; }
+        PD_TRY(raise_dynamic_lds<&gru_bf16_kernel<true>>((int)GRU_BF_LDS, "rmvpe gru"));
+        PD_TRY(raise_dynamic_lds<&gru_bf16_kernel<false>>((int)GRU_BF_LDS, "rmvpe gru"));
+        ProfScope ps("rmvpe_gru", st);
+        if (frames) hipLaunchKernelGGL(gru_bf16_kernel<true>, grid, dim3(512), GRU_BF_LDS, st, ga, h->w_hh_b);
+        else hipLaunchKernelGGL(gru_bf16_kernel<false>, grid, dim3(512), GRU_BF_LDS, st, ga, h->w_hh_b);
+        PD_LAUNCH_CHECK();
+      } else {
+        ProfScope ps("rmvpe_gru", st);
+        if (frames) hipLaunchKernelGGL(gru_kernel<true>, grid, dim3(512), 0, st, ga);
+        else hipLaunchKernelGGL(gru_kernel<false>, grid, dim3(512), 0, st, ga);
+        PD_LAUNCH_CHECK();
+      }
     }
     fc_src = go;
   }

@@ -1,6 +1,8 @@
 """RMVPE pitch extraction on the GPU: the reference's modules/rmvpe (``E2E0``, ``MelSpectrogram``,
 ``to_local_average_f0``) and component/pe/rmvpe.py (``RMVPE``) on pd_rmvpe, the centred pd_mel and pd_resample
-(include/prodiff_hip.h, "pitch extraction").  No librosa, no torchaudio.
+(include/prodiff_hip.h, "pitch extraction").  No librosa, no torchaudio.  fp32 is the default;
+``E2E0.set_compute_dtype("bf16")`` runs the 3x3 convs and the recurrent product on the bf16 MFMA
+(pd_rmvpe_set_option), all else staying fp32.
 """
 from __future__ import annotations
 
@@ -67,6 +69,19 @@ class E2E0(nn.Module):
             self.param_keys.append(key)
         self._native = _lib.NativeHandle("E2E0", "pd_rmvpe_create", "pd_rmvpe_destroy", num_params="pd_rmvpe_num_params")
         self._ws = _lib.Workspace()
+        self._compute_dtype = ("fp32", "fp32")      # (convs, recurrence)
+        self._applied = None      # (handle, compute dtypes) of the last pd_rmvpe_set_option pair
+
+    def set_compute_dtype(self, dtype, recurrence=None):
+        """"fp32" (default) or "bf16".  ``dtype`` governs the 3x3 convs' operands (every conv but the first and
+        ``cnn``), ``recurrence`` (default: ``dtype``) the GRU's recurrent product; activations, the gates, the input
+        projection, the head and the decode stay fp32.  Takes effect at the next call; the handle is not rebuilt."""
+        recurrence = dtype if recurrence is None else recurrence
+        for v in (dtype, recurrence):
+            if not isinstance(v, str) or v not in ("fp32", "bf16"):
+                raise ValueError(f"E2E0: compute dtype must be 'fp32' or 'bf16', got {v!r}")
+        self._compute_dtype = (dtype, recurrence)
+        return self
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         kept = {k: v for k, v in state_dict.items() if not synth.rmvpe_key_is_skipped(k)}
@@ -84,11 +99,19 @@ class E2E0(nn.Module):
 
     def handle(self):
         ps = self.ordered_params()
-        return self._native.get(self._native.signature(ps),
-                                lambda: (self.dims(), [p.detach().float().contiguous() for p in ps]))
+        h = self._native.get(self._native.signature(ps),
+                             lambda: (self.dims(), [p.detach().float().contiguous() for p in ps]))
+        want = (h.value, self._compute_dtype)
+        if self._applied != want and (self._applied is not None or self._compute_dtype != ("fp32", "fp32")):
+            L, st = _lib.lib(), _lib.stream_ptr(ps[0].device)
+            for opt, v in zip((_lib.PD_RMVPE_OPT_CONV_DTYPE, _lib.PD_RMVPE_OPT_GRU_DTYPE), self._compute_dtype):
+                _lib.check(L.pd_rmvpe_set_option(h, opt, _lib.PD_DTYPE_BF16 if v == "bf16" else _lib.PD_DTYPE_F32, st))
+        self._applied = want
+        return h
 
     def close(self):
         self._native.close()
+        self._applied = None
 
     @torch.no_grad()
     def forward_time_major(self, mel_tm, return_feat=False, frames=None):
@@ -396,9 +419,9 @@ def stack_waveforms(waveforms, lens, device):
 @register_pe
 class RMVPE:
     """component/pe/rmvpe.py:13-72.  ``model_path=None`` with no ``pe_ckpt`` in hparams builds the model without
-    weights (load them with ``self.model.load_state_dict``)."""
+    weights (load them with ``self.model.load_state_dict``).  ``compute_dtype``: ``E2E0.set_compute_dtype``."""
 
-    def __init__(self, hparams, model_path=None, hop_length=160):
+    def __init__(self, hparams, model_path=None, hop_length=160, compute_dtype="fp32"):
         self.hparams = hparams
         self.resample_kernel = {}
         self.device = "cuda"
@@ -409,6 +432,12 @@ class RMVPE:
             ckpt = torch.load(model_path, map_location=self.device)
             self.model.load_state_dict(ckpt["model"], strict=False)
         self.mel_extractor = MelSpectrogram(N_MELS, SAMPLE_RATE, WINDOW_LENGTH, hop_length, None, MEL_FMIN, MEL_FMAX)
+        self.set_compute_dtype(compute_dtype)
+
+    def set_compute_dtype(self, dtype, recurrence=None):
+        """``E2E0.set_compute_dtype`` of the model; returns self."""
+        self.model.set_compute_dtype(dtype, recurrence)
+        return self
 
     @torch.no_grad()
     def mel2hidden(self, mel, frames=None):

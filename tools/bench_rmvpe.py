@@ -6,8 +6,18 @@ table from pd_profile_*; the front end (centred mel) and the decode beside it; a
 with torch ops (F.conv2d, F.batch_norm, F.conv_transpose2d, nn.GRU) in eager mode on the same GPU.  Prints one
 JSON line.
 
-    python tools/bench_rmvpe.py [--calls 100] [--warmup 5] [--batch 8] [--seconds 10] [--no-torch]
-    python tools/bench_rmvpe.py --ragged N [--calls 30]
+    python tools/bench_rmvpe.py [--calls 100] [--warmup 5] [--batch 8] [--seconds 10] [--no-torch] [--dtype bf16]
+    python tools/bench_rmvpe.py --ragged N [--calls 30] [--dtype bf16]
+    python tools/bench_rmvpe.py --check clip.wav [--ckpt model.pt]
+
+--dtype bf16 adds, beside the fp32 figures, the same call in the bf16 mode (``E2E0.set_compute_dtype("bf16")``: "bf16"
+in the JSON line, with its own per-kernel table) and with each of the two options switched alone ("bf16_convs_only",
+"bf16_recurrence_only"); with --ragged it adds the ragged call's bf16 line.
+
+--check runs one clip (any sample rate, mono or the first channel) through the extractor in fp32 and in the three bf16
+modes and prints, per mode against fp32: rel-L2 of ``hidden``, the frames whose argmax or voicing flag differ, the f0
+difference in cents (max and median over the commonly voiced frames) and the smallest top-two salience margin of the
+fp32 run.  Without --ckpt the weights are synthetic, whose margins are far smaller than a trained model's.
 
 --ragged N times ``RMVPE.get_pitch_batch`` (44.1 kHz audio to f0 on the mel grid, hop 512) on clips of the first N
 lengths of tests/golden/ds_lengths.json three ways: (a) one ragged call on the list of clips, (b) one call per clip
@@ -108,6 +118,93 @@ def torch_e2e0(P, model, mel, gru):
     return torch.sigmoid(F.linear(gru(x)[0], P["fc.1.weight"], P["fc.1.bias"]))
 
 
+def measure_network(net, mel, a, T):
+    """median / min / p90 of one forward call, the per-kernel table and what follows from it"""
+    out = {}
+    med, best, p90 = time_calls(lambda: net.forward_time_major(mel), a.calls, a.warmup)
+    out.update(native_ms_median=round(med, 3), native_ms_min=round(best, 3), native_ms_p90=round(p90, 3))
+    n_prof = 5
+    _lib.profile_enable(True)
+    for _ in range(n_prof):
+        net.forward_time_major(mel)
+    torch.cuda.synchronize()
+    prof = _lib.profile_summary()
+    _lib.profile_enable(False)
+    out["kernels_ms_per_call"] = {k: [c // n_prof, round(t / n_prof, 4)] for k, (c, t) in sorted(prof.items())}
+    out["conv_ms"] = round(sum(t for k, (c, t) in prof.items() if k.startswith("rmvpe_conv")) / n_prof, 3)
+    lvl = {}
+    for k, (c, t) in prof.items():
+        if k.startswith("rmvpe_conv") and k[-2] == "l" and k[-1].isdigit():
+            lvl[k[-2:]] = lvl.get(k[-2:], 0.0) + t / n_prof
+    out["conv_ms_per_level"] = {k: round(v, 3) for k, v in sorted(lvl.items())}
+    if "rmvpe_gru" in prof:
+        out["gru_us_per_step"] = round(prof["rmvpe_gru"][1] / n_prof / T * 1e3, 3)
+    return out
+
+
+def load_wav(path):
+    """-> (float32 mono [n], sample rate) of a PCM or float .wav, without torchaudio"""
+    import wave
+    try:
+        with wave.open(path, "rb") as w:
+            sr, ch, width, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
+            raw = w.readframes(n)
+        if width == 2:
+            x = np.frombuffer(raw, "<i2").astype(np.float32) / 32768.0
+        elif width == 4:
+            x = np.frombuffer(raw, "<i4").astype(np.float32) / 2147483648.0
+        elif width == 3:
+            b = np.frombuffer(raw, np.uint8).reshape(-1, 3).astype(np.int32)
+            x = ((b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) << 8 >> 8).astype(np.float32) / 8388608.0
+        else:
+            x = (np.frombuffer(raw, np.uint8).astype(np.float32) - 128.0) / 128.0
+        return np.ascontiguousarray(x.reshape(-1, ch)[:, 0]), sr
+    except wave.Error:
+        from scipy.io import wavfile          # float .wav files
+        sr, x = wavfile.read(path)
+        x = x if x.ndim == 1 else x[:, 0]
+        return np.ascontiguousarray(x, np.float32), int(sr)
+
+
+def check_clip(a):
+    dev = torch.device("cuda:0")
+    audio, sr = load_wav(a.check)
+    pe = RM.RMVPE({}, model_path=a.ckpt)
+    if a.ckpt is None:
+        pe.model.load_state_dict({k: torch.from_numpy(v) for k, v in
+                                  synth.synth_rmvpe_params(synth.rmvpe_param_shapes(**FULL), a.seed).items()})
+    pe.model.to(dev)
+    wav = torch.from_numpy(audio)[None].to(dev)
+    thred = 0.03
+
+    def run(conv, gru):
+        hidden = pe.set_compute_dtype(conv, gru)._hidden_from_audio(wav, sr)[0].clone()
+        return hidden.double().cpu().numpy(), RM.to_local_average_f0(hidden[None], thred=thred)[0].double().cpu().numpy()
+
+    h32, f32_ = run("fp32", "fp32")
+    top = np.sort(h32, axis=-1)
+    line = {"bench": "rmvpe_check", "clip": os.path.basename(a.check), "sr": sr, "frames": int(h32.shape[0]),
+            "weights": "checkpoint" if a.ckpt else "synthetic", "voiced_fp32": int((f32_ > 0).sum()),
+            "top_two_margin_fp32": {"min": float((top[:, -1] - top[:, -2]).min()),
+                                    "median": float(np.median(top[:, -1] - top[:, -2]))}}
+    for key, conv, gru in (("bf16", "bf16", "bf16"), ("bf16_convs_only", "bf16", "fp32"),
+                           ("bf16_recurrence_only", "fp32", "bf16")):
+        h, f = run(conv, gru)
+        both = (f > 0) & (f32_ > 0)
+        c = 1200.0 * np.abs(np.log2(f[both] / f32_[both])) if both.any() else np.zeros(1)
+        line[key] = {"hidden_rel_l2": float(np.linalg.norm(h - h32) / np.linalg.norm(h32)),
+                     "argmax_differs": int((h.argmax(-1) != h32.argmax(-1)).sum()),
+                     "voicing_differs": int(((f > 0) != (f32_ > 0)).sum()),
+                     "f0_cents_max": float(c.max()), "f0_cents_median": float(np.median(c))}
+        print(f"{key:>22}: hidden rel-L2 {line[key]['hidden_rel_l2']:.3e}, argmax differs on "
+              f"{line[key]['argmax_differs']} and voicing on {line[key]['voicing_differs']} of {h.shape[0]} frames, f0 "
+              f"{line[key]['f0_cents_max']:.4f} cents max / {line[key]['f0_cents_median']:.4f} median over "
+              f"{int(both.sum())} voiced frames", flush=True)
+    print(json.dumps(line), flush=True)
+    pe.model.close()
+    pe.mel_extractor.close()
+
+
 def bench_ragged(a):
     dev = torch.device("cuda:0")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -146,6 +243,22 @@ def bench_ragged(a):
     for key, fn in (("ragged", ragged), ("single_calls", one_by_one), ("padded", padded_call)):
         med, best, p90 = time_calls(fn, a.calls, a.warmup)
         line[key + "_ms"] = {"median": round(med, 3), "min": round(best, 3), "p90": round(p90, 3)}
+    if a.dtype == "bf16":
+        for key, conv, gru in (("ragged_bf16", "bf16", "bf16"), ("ragged_bf16_convs_only", "bf16", "fp32"),
+                               ("ragged_bf16_recurrence_only", "fp32", "bf16")):
+            pe.set_compute_dtype(conv, gru)
+            med, best, p90 = time_calls(ragged, a.calls, a.warmup)
+            line[key + "_ms"] = {"median": round(med, 3), "min": round(best, 3), "p90": round(p90, 3)}
+            if key == "ragged_bf16":
+                _lib.profile_enable(True)
+                for _ in range(5):
+                    ragged()
+                torch.cuda.synchronize()
+                prof = _lib.profile_summary()
+                _lib.profile_enable(False)
+                line["ragged_bf16_kernels_ms_per_call"] = {k: [c // 5, round(t / 5, 4)] for k, (c, t) in sorted(prof.items())
+                                                           if k.startswith("rmvpe")}
+        pe.set_compute_dtype("fp32")
     print(json.dumps(line), flush=True)
     pe.model.close()
     pe.mel_extractor.close()
@@ -160,7 +273,12 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--seed", type=int, default=44)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--check", metavar="CLIP.wav")
+    ap.add_argument("--ckpt", metavar="MODEL.pt")
     a = ap.parse_args()
+    if a.check:
+        return check_clip(a)
     if a.ragged:
         return bench_ragged(a)
     dev = torch.device("cuda:0")
@@ -180,8 +298,8 @@ def main():
     hidden = net.forward_time_major(mel)
     line = {"bench": "rmvpe", "B": B, "samples": Lw, "frames": frames, "T": T, "calls": a.calls,
             "device": torch.cuda.get_device_name(0), "lib": _lib.lib().pd_build_config().decode()}
-    med, best, p90 = time_calls(lambda: net.forward_time_major(mel), a.calls, a.warmup)
-    line.update(native_ms_median=round(med, 3), native_ms_min=round(best, 3), native_ms_p90=round(p90, 3))
+    line.update(measure_network(net, mel, a, T))
+    conv_ms = line["conv_ms"]
     line["mel_ms_median"] = round(time_calls(lambda: ms_.forward_time_major(wav), a.calls, a.warmup)[0], 4)
     line["decode_ms_median"] = round(time_calls(lambda: RM.to_local_average_f0(hidden), a.calls, a.warmup)[0], 4)
     # the same call from one captured graph
@@ -190,22 +308,20 @@ def main():
         out = net.forward_time_major(mel)
     gm, gb, _ = time_calls(graph.replay, a.calls, a.warmup)
     line.update(graph_ms_median=round(gm, 3), graph_ms_min=round(gb, 3), graph_equals_eager=bool(torch.equal(out, hidden)))
-    # per kernel
-    n_prof = 5
-    _lib.profile_enable(True)
-    for _ in range(n_prof):
-        net.forward_time_major(mel)
-    torch.cuda.synchronize()
-    prof = _lib.profile_summary()
-    _lib.profile_enable(False)
-    line["kernels_ms_per_call"] = {k: [c // n_prof, round(t / n_prof, 4)] for k, (c, t) in sorted(prof.items())}
-    conv_ms = sum(t for k, (c, t) in prof.items() if k.startswith("rmvpe_conv")) / n_prof
     flop = conv_flop(shapes, FULL, B, T)
-    line.update(conv_gflop=round(flop / 1e9, 1), conv_ms=round(conv_ms, 3),
+    line.update(conv_gflop=round(flop / 1e9, 1),
                 conv_f32_mfma_peak_fraction=round(flop / (conv_ms * 1e-3) / F32_MFMA_PEAK, 4),
                 conv_floor_ms_at_peak=round(flop / F32_MFMA_PEAK * 1e3, 3))
-    if "rmvpe_gru" in prof:
-        line["gru_us_per_step"] = round(prof["rmvpe_gru"][1] / n_prof / T * 1e3, 3)
+    if a.dtype == "bf16":
+        for key, conv, gru in (("bf16", "bf16", "bf16"), ("bf16_convs_only", "bf16", "fp32"),
+                               ("bf16_recurrence_only", "fp32", "bf16")):
+            hb = net.set_compute_dtype(conv, gru).forward_time_major(mel)
+            line[key] = measure_network(net, mel, a, T)
+            line[key]["hidden_rel_l2_to_fp32"] = float((hb - hidden).norm() / hidden.norm())
+            if key != "bf16":
+                del line[key]["kernels_ms_per_call"]
+        net.set_compute_dtype("fp32")
+        line["fp32_bit_equal_after_the_switches"] = bool(torch.equal(net.forward_time_major(mel), hidden))
     if not a.no_torch:
         try:
             P = {k: torch.from_numpy(v).to(dev) for k, v in host.items()}
