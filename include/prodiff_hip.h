@@ -1056,6 +1056,69 @@ int pd_curves_forward_ragged(const pd_curves* h, const float* sp, const float* a
                              float db_min, float db_max, float* voicing, float* breath, float* tension, float* base,
                              const int* rows, int B, int L, int T_f0, void* workspace, size_t ws_bytes, void* stream);
 
+/* ================================================================ FastDiff analysis
+ * process_utterance (utils/data_gen_utils.py:95-149), the analysis half of the FastDiff vocoder
+ * (component/vocoder/fastdiff.py:128-145): an optional loudness normalisation (pyloudnorm's ITU-R BS.1770 meter),
+ * librosa.stft centred with pad_mode="constant", a linear-magnitude Slaney mel (logged only for vocoder='pwg') and
+ * the waveform padded to T hop samples.
+ *
+ * pd_mel_create_centered_zero -- a third constructor of pd_mel: zero padding of nf/2 samples on both sides,
+ * T = 1 + L / hn frames, frame t centred on sample t hn, min_samples 1.  out_mode selects what pd_mel_forward
+ * writes: out_scale * log(max(mel, clip_val)) as the other constructors (PD_MEL_OUT_LN), out_scale * mel
+ * (PD_MEL_OUT_LINEAR, vocoder='fastdiff') or out_scale * log10(max(mel, clip_val)) (PD_MEL_OUT_LOG10, 'pwg' with
+ * clip_val = eps).  Window, key shift, bins, basis, spec_out and lens are as pd_mel_create; what a row holds past
+ * lens[b] is never read. */
+#define PD_MEL_OUT_LN 0
+#define PD_MEL_OUT_LINEAR 1
+#define PD_MEL_OUT_LOG10 2
+int pd_mel_create_centered_zero(const pd_mel_dims* dims, const float* mel_basis, int out_mode, void* stream,
+                                pd_mel** out);
+/* return_linear's spectrum (utils/audio.py:51-56): out[i] = (20 log10(max(1e-5, spec[i])) - min_level_db) /
+ * (-min_level_db), i < n, in f32; min_level_db < 0.  out may alias spec. */
+int pd_mel_normalize_spec(const float* spec, float min_level_db, float* out, size_t n, void* stream);
+
+/* pd_loudness -- Meter(rate).integrated_loudness and normalize.loudness of pyloudnorm, mono, with the peak step of
+ * process_utterance :121-122.  The K-weighting is two biquads (a high shelf, then a high pass) whose coefficients
+ * the caller designs in double (prodiff_amd.analysis.kweighting_coefficients) and passes normalised (a[0] = 1);
+ * they run as scipy.signal.lfilter's direct form II transposed, in fp64, each row cut into chunks of
+ * pd_loudness_chunk() samples: a chunk's zero-state response, a scan of the chunks' end states with the four
+ * states' transition over one chunk, then each chunk again from its true initial state.  Block j covers the
+ * samples [bounds[j][0], min(bounds[j][1], L_b)); its energy is the sum of y^2 in double times 1 / (0.4 rate).
+ * The gates: l_j = -0.691 + 10 log10 z_j; absolute l_j >= -70; relative l_j > G_r and l_j > -70 with
+ * G_r = -0.691 + 10 log10(mean z over the absolute gate) - 10; the loudness is -0.691 + 10 log10(mean z over both
+ * gates), -inf when no block passes.  Every sum's order is fixed by the chunk size, the bounds and the row's own
+ * length: row b of a batch equals that row run alone, bit for bit.  Samples must be finite. */
+typedef struct pd_loudness pd_loudness;
+
+typedef struct {
+  int rate;             /* Hz, in [1000, 768000]                                      */
+  double shelf_b[3];    /* high shelf: +4 dB, Q = 1/sqrt(2), 1500 Hz                  */
+  double shelf_a[3];    /* a[0] = 1                                                   */
+  double pass_b[3];     /* high pass: Q = 0.5, 38 Hz                                  */
+  double pass_a[3];     /* a[0] = 1                                                   */
+} pd_loudness_dims;
+
+/* Nothing is allocated on the device.  Unstable or unnormalised coefficients return PD_ERR_ARG. */
+int pd_loudness_create(const pd_loudness_dims* dims, void* stream, pd_loudness** out);
+void pd_loudness_destroy(pd_loudness* h);
+/* Samples per chunk of the recurrence. */
+int pd_loudness_chunk(void);
+/* ceil(0.4 rate): pyloudnorm refuses a shorter signal. */
+int pd_loudness_min_samples(const pd_loudness* h);
+size_t pd_loudness_workspace_size(const pd_loudness* h, int B, int L, int n_blocks);
+/* wav [B][L], lens int32 [B] or NULL -> loud_out double [B]; peak_out float [B] = max |x| of each row, or NULL;
+ * wav_out [B][L_out] or NULL = f32(10^((target - loudness) / 20)) * x in f32, divided by its own maximum when
+ * that exceeds 1, and 0 from the row's length up to L_out (librosa_pad_lr and the trim to T hop when L_out is
+ * (1 + L / hop) hop).  bounds: device int32 [n_blocks][2], the block bounds the host evaluated; counts: device
+ * int32 [B], the blocks of each row (<= n_blocks).  The caller checks on the host that every row holds at least
+ * pd_loudness_min_samples; the kernels clamp lens, counts and bounds so that every access stays inside the row.
+ * L < pd_loudness_min_samples returns PD_ERR_ARG.  Six launches, stream-ordered, no allocation. */
+int pd_loudness_forward(const pd_loudness* h, const float* wav, const int* lens, const int* bounds, const int* counts,
+                        int n_blocks, double target, double* loud_out, float* peak_out, float* wav_out, int B, int L,
+                        int L_out, void* workspace, size_t ws_bytes, void* stream);
+/* out [B][L_out] = the row's first min(lens[b], L) samples, then zeros: the padding alone (loud_norm off). */
+int pd_loudness_pad(const float* wav, const int* lens, float* out, int B, int L, int L_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,9 @@ Drop-in replacements for the reference hot path (see DESIGN.md / INTEGRATION.md)
     SinusoidalSmoothingConv1d / VarianceCurves / isolate_parts (variance curves and k-th harmonic isolation on the GPU)
         <- component/binarizer/binarizer_utils.py, modules/commons/common_layers.py, librosa.feature.rms,
            librosa.amplitude_to_db
+  * prodiff_amd.analysis.process_utterance / integrated_loudness / normalize_loudness; vocoder.FastDiff.wav2mel /
+    wav2wav (FastDiff's analysis half on the GPU: BS.1770 loudness, zero-padded centred STFT, linear mel)
+        <- utils/data_gen_utils.py:process_utterance, pyloudnorm.Meter / normalize.loudness, librosa.stft
 All compute runs in libprodiff_hip.so (hand-written gfx950 HIP kernels).
 """
 from .prodiff import GaussianDiffusion, WaveNet  # noqa: F401
@@ -43,10 +46,11 @@ from .rmvpe import (E2E0, RMVPE, MelSpectrogram, align_f0, to_local_average_f0, 
 from .vr import CascadedNet, extract_harmonic_aperiodic, load_sep_model  # noqa: F401
 from .curves import (SinusoidalSmoothingConv1d, VarianceCurves, get_breath, get_energy, get_kth_harmonic,  # noqa: F401
                      get_tension, get_voicing, isolate_parts)
+from .analysis import integrated_loudness, normalize_loudness, process_utterance  # noqa: F401
 
 __all__ = ["WaveNet", "GaussianDiffusion", "FastDiff", "sampling_given_noise_schedule", "RectifiedFlow",
            "PitchRectifiedFlow", "NsfGenerator", "NsfHifiGAN", "ProDiffTeacher", "PitchPredictor", "DurPredictor",
            "STFT", "mel_filterbank", "Resample", "KAISER_BEST", "sinc_resample_kernel64", "E2E0", "RMVPE",
            "MelSpectrogram", "to_local_average_f0", "viterbi_path", "to_viterbi_f0", "align_f0", "CascadedNet",
            "load_sep_model", "extract_harmonic_aperiodic", "SinusoidalSmoothingConv1d", "VarianceCurves", "get_energy", "get_voicing", "get_breath", "get_kth_harmonic",
-           "get_tension", "isolate_parts"]
+           "get_tension", "isolate_parts", "integrated_loudness", "normalize_loudness", "process_utterance"]

@@ -114,6 +114,13 @@ class pd_curves_dims(C.Structure):
     _fields_ = [("samplerate", C.c_int), ("win_size", C.c_int), ("hop_size", C.c_int), ("half_width", C.c_float)]
 
 
+class pd_loudness_dims(C.Structure):
+    _fields_ = [("rate", C.c_int), ("shelf_b", C.c_double * 3), ("shelf_a", C.c_double * 3),
+                ("pass_b", C.c_double * 3), ("pass_a", C.c_double * 3)]
+
+
+PD_MEL_OUT_LN, PD_MEL_OUT_LINEAR, PD_MEL_OUT_LOG10 = 0, 1, 2   # pd_mel_create_centered_zero
+
 _VP = C.c_void_p
 _SIGS = {
     "pd_last_error": (C.c_char_p, []),
@@ -242,6 +249,16 @@ _SIGS = {
     "pd_curves_forward_ragged": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_int,
                                            C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
                                            _VP, C.c_size_t, _VP]),
+    "pd_mel_create_centered_zero": (C.c_int, [C.POINTER(pd_mel_dims), _VP, C.c_int, _VP, C.POINTER(_VP)]),
+    "pd_mel_normalize_spec": (C.c_int, [_VP, C.c_float, _VP, C.c_size_t, _VP]),
+    "pd_loudness_create": (C.c_int, [C.POINTER(pd_loudness_dims), _VP, C.POINTER(_VP)]),
+    "pd_loudness_destroy": (None, [_VP]),
+    "pd_loudness_chunk": (C.c_int, []),
+    "pd_loudness_min_samples": (C.c_int, [_VP]),
+    "pd_loudness_workspace_size": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
+    "pd_loudness_forward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_double, _VP, _VP, _VP, C.c_int, C.c_int,
+                                      C.c_int, _VP, C.c_size_t, _VP]),
+    "pd_loudness_pad": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -287,9 +304,11 @@ class NativeHandle:
     again.  ``create`` / ``destroy`` / ``set_option`` / ``num_params`` name library functions (looked
     up on first use, so building a module does not load the library)."""
 
-    def __init__(self, name, create, destroy, set_option=None, option_ids=None, num_params=None, plain_create=False):
+    def __init__(self, name, create, destroy, set_option=None, option_ids=None, num_params=None, plain_create=False,
+                 create_extra=()):
         self.name = name
-        self._plain_create = plain_create   # create(dims, tensor..., stream, out): no parameter list, no dtype
+        self._plain_create = plain_create   # create(dims, tensor..., extra..., stream, out): no parameter list, no dtype
+        self._create_extra = tuple(create_extra)
         self._create, self._destroy, self._set_option, self._num_params = create, destroy, set_option, num_params
         self.option_ids = option_ids or {}
         self.dtype = "fp32"
@@ -347,7 +366,7 @@ class NativeHandle:
 
     def _call_create(self, create, dims, tensors, stream, h):
         if self._plain_create:
-            return create(C.byref(dims), *[fptr(t) for t in tensors], stream, C.byref(h))
+            return create(C.byref(dims), *[fptr(t) for t in tensors], *self._create_extra, stream, C.byref(h))
         arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
         dt = PD_DTYPE_BF16 if self.dtype == "bf16" else PD_DTYPE_F32
         return create(C.byref(dims), arr, dt, stream, C.byref(h))
@@ -375,12 +394,13 @@ class HandleCache:
     curves), one per (key, device): ``handles`` maps key + (device,) to its NativeHandle, oldest first; at
     ``limit`` entries the oldest is closed and dropped."""
 
-    def __init__(self, name, create, destroy, limit=None):
+    def __init__(self, name, create, destroy, limit=None, create_extra=()):
         self.name, self._create, self._destroy, self.limit = name, create, destroy, limit
+        self._create_extra = create_extra   # scalar arguments of the create between the tensors and the stream
         self.handles = {}
 
     def _new(self):
-        return NativeHandle(self.name, self._create, self._destroy, plain_create=True)
+        return NativeHandle(self.name, self._create, self._destroy, plain_create=True, create_extra=self._create_extra)
 
     def get(self, device, key, build):
         """The C handle for ``key`` (a tuple) on ``device``; ``build(device) -> (dims struct, tensors)`` is

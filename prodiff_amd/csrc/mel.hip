@@ -24,6 +24,7 @@
 // B-fragment read touches fall into 32 different even banks and the two k halves into the odd ones beside
 // them (with the plain segment every frame would start in the same bank whenever hn is a multiple of 64).
 #include <cmath>
+#include <string>
 
 #include "../../include/prodiff_hip.h"
 #include "common.h"
@@ -53,6 +54,7 @@ struct MelPlan {
   int padw, stride, nq;   // LDS segment: nq rows of hn samples, stride hn + padw
   int n_mels, mt, mp;     // mel bins, 32-mel tiles, mt * 32
   float mag_scale, clip;
+  int out_mode;           // PD_MEL_OUT_*: what the epilogue of the zero-padded framing writes
   int seg_floats;         // nq * stride rounded up to 4
   size_t lds_bytes;
 };
@@ -84,6 +86,14 @@ __global__ __launch_bounds__(256) void mel_basis_pack_kernel(const float* __rest
   bt[idx] = (k < nb && m < n_mels) ? basis[(long long)m * size + k] : 0.f;
 }
 
+// audio.amp_to_db then audio.normalize (utils/audio.py:51-56): (20 log10(max(1e-5, |X|)) - min_db) / (-min_db)
+// (out may be spec itself: no __restrict__)
+__global__ __launch_bounds__(256) void mel_normalize_spec_kernel(const float* spec, float min_db, float* out,
+                                                                 long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    out[i] = (20.f * log10f(fmaxf(1e-5f, spec[i])) - min_db) / -min_db;
+}
+
 // ---------------------------------------------------------------- forward
 struct MelArgs {
   const float* wav;   // [B][L]
@@ -98,7 +108,9 @@ struct MelArgs {
   MelPlan p;
 };
 
-template <int MT>
+// ZP: the zero-padded framing of pd_mel_create_centered_zero (samples outside the row read as 0, the epilogue
+// follows p.out_mode); the reflect framings' instance is the kernel as it was.
+template <int MT, bool ZP>
 __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];   // the segment, then red[MT * 32][33]
   const MelPlan& p = a.p;
@@ -115,7 +127,13 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
     const int nlog = (MEL_TF - 1) * hn + nf, total = p.nq * hn;
     for (int idx = tid; idx < total; idx += MEL_NT) {
       const int q = idx / hn, r = idx - q * hn;
-      const float v = wrow[reflect_index(p0 + idx, Lb)];
+      float v;
+      if (ZP) {
+        const long long s = p0 + idx;
+        v = s >= 0 && s < Lb ? wrow[s] : 0.f;
+      } else {
+        v = wrow[reflect_index(p0 + idx, Lb)];
+      }
       smem[q * stride + r] = idx < nlog ? v : 0.f;
     }
   }
@@ -222,8 +240,14 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
   const int n_mels = p.n_mels;
   for (int idx = tid; idx < MEL_TF * n_mels; idx += MEL_NT) {
     const int tt = idx / n_mels, m = idx - tt * n_mels;
-    if (t0 + tt < a.T)
-      a.out[((long long)b * a.T + t0 + tt) * n_mels + m] = a.out_scale * logf(fmaxf(red[m * MEL_RED_LD + tt], p.clip));
+    if (t0 + tt < a.T) {
+      const float mel = red[m * MEL_RED_LD + tt];
+      float v;
+      if (ZP && p.out_mode == PD_MEL_OUT_LINEAR) v = a.out_scale * mel;
+      else if (ZP && p.out_mode == PD_MEL_OUT_LOG10) v = a.out_scale * log10f(fmaxf(mel, p.clip));
+      else v = a.out_scale * logf(fmaxf(mel, p.clip));
+      a.out[((long long)b * a.T + t0 + tt) * n_mels + m] = v;
+    }
   }
   if (a.spec && p.nb < p.size) {   // the reference's zero padding of the bins a downward key shift lacks
     const int nz = p.size - p.nb;
@@ -234,11 +258,11 @@ __global__ __launch_bounds__(MEL_NT) void mel_forward_kernel(const MelArgs a) {
   }
 }
 
-template <int MT>
+template <int MT, bool ZP>
 int launch_mel(const MelArgs& a, int B, hipStream_t st) {
-  PD_TRY(raise_dynamic_lds<&mel_forward_kernel<MT>>((int)MEL_MAX_LDS, "mel"));
+  PD_TRY((raise_dynamic_lds<&mel_forward_kernel<MT, ZP>>((int)MEL_MAX_LDS, "mel")));
   ProfScope ps("mel_forward", st);
-  hipLaunchKernelGGL(mel_forward_kernel<MT>, dim3(cdiv(a.T, MEL_TF), B), dim3(MEL_NT), a.p.lds_bytes, st, a);
+  hipLaunchKernelGGL((mel_forward_kernel<MT, ZP>), dim3(cdiv(a.T, MEL_TF), B), dim3(MEL_NT), a.p.lds_bytes, st, a);
   PD_LAUNCH_CHECK();
   return PD_OK;
 }
@@ -299,23 +323,30 @@ struct pd_mel {
   WeightPool weights;   // the two DFT tables and the packed mel basis
   float *tc = nullptr, *ts = nullptr, *bt = nullptr;
   bool centered = false;   // torch.stft(center=True) framing (pd_mel_create_centered)
+  bool zero_pad = false;   // librosa.stft(pad_mode="constant") framing (pd_mel_create_centered_zero)
 };
 
 namespace {
 
-int mel_create(const pd_mel_dims* dims, const float* mel_basis, bool centered, void* stream, pd_mel** out) {
+int mel_create(const pd_mel_dims* dims, const float* mel_basis, bool centered, void* stream, pd_mel** out,
+               bool zero_pad = false, int out_mode = PD_MEL_OUT_LN) {
   PD_CHECK_ARG(dims && mel_basis && out, "null pointer");
+  PD_CHECK_ARG(out_mode >= PD_MEL_OUT_LN && out_mode <= PD_MEL_OUT_LOG10,
+               "out_mode must be 0 (ln), 1 (linear) or 2 (log10), got " + std::to_string(out_mode));
   MelPlan p;
   PD_TRY(make_plan(*dims, &p));
   if (centered) {   // reflect nf/2 on both sides: frame t is centred on sample t hn
     p.pad_l = p.pad_r = p.nf / 2;
     p.min_len = p.nf / 2 + 1;
   }
+  if (zero_pad) p.min_len = 1;   // zeros need no signal to mirror
+  p.out_mode = out_mode;
   hipStream_t st = (hipStream_t)stream;
   std::unique_ptr<pd_mel> h(new pd_mel());
   h->d = *dims;
   h->p = p;
   h->centered = centered;
+  h->zero_pad = zero_pad;
   WeightPool& wp = h->weights;
   const size_t tab = (size_t)p.nrows * p.nbp, nbt = (size_t)p.nbp * p.mp;
   pd_mel* hp = h.get();
@@ -350,6 +381,11 @@ int pd_mel_create_centered(const pd_mel_dims* dims, const float* mel_basis, void
   return mel_create(dims, mel_basis, true, stream, out);
 }
 
+int pd_mel_create_centered_zero(const pd_mel_dims* dims, const float* mel_basis, int out_mode, void* stream,
+                                pd_mel** out) {
+  return mel_create(dims, mel_basis, true, stream, out, true, out_mode);
+}
+
 void pd_mel_destroy(pd_mel* h) { delete h; }
 
 int pd_mel_min_samples(const pd_mel* h) { return h ? h->p.min_len : 0; }
@@ -377,12 +413,22 @@ int pd_mel_forward(const pd_mel* h, const float* wav, const int* lens, float out
   a.L = L; a.T = pd_mel_frames(h, L); a.out_scale = out_scale; a.p = h->p;
   PD_CHECK_ARG(a.T >= 1, "signal too long");
   hipStream_t st = (hipStream_t)stream;
-  switch (h->p.mt) {
-    case 1: return launch_mel<1>(a, B, st);
-    case 2: return launch_mel<2>(a, B, st);
-    case 3: return launch_mel<3>(a, B, st);
-    default: return launch_mel<4>(a, B, st);
-  }
+  int rc = PD_OK;
+  dispatch([&](auto MT, auto ZP) { rc = launch_mel<MT(), ZP()>(a, B, st); }, one_of<1, 2, 3, 4>(h->p.mt),
+           bool_of(h->zero_pad));
+  return rc;
+}
+
+int pd_mel_normalize_spec(const float* spec, float min_level_db, float* out, size_t n, void* stream) {
+  PD_CHECK_ARG(spec && out, "null pointer");
+  PD_CHECK_ARG(n >= 1 && n <= ((size_t)1 << 40), "n must lie in [1, 2^40]");
+  PD_CHECK_ARG(std::isfinite(min_level_db) && min_level_db < 0.f, "min_level_db must be negative");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("mel_normalize_spec", st);
+  hipLaunchKernelGGL(mel_normalize_spec_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535u * 16u)), dim3(256), 0,
+                     st, spec, min_level_db, out, (long long)n);
+  PD_LAUNCH_CHECK();
+  return PD_OK;
 }
 
 }  // extern "C"

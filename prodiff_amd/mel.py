@@ -79,12 +79,13 @@ class MelFrontEnd:
     in total (one per key shift, speed and device, oldest out first) and the pd_mel_forward call.  A subclass names
     its create function and states its minimum-length rule (``_min_samples``)."""
 
-    def _setup(self, name, create, basis, n_fft, win_size, hop_length, clip_val):
+    def _setup(self, name, create, basis, n_fft, win_size, hop_length, clip_val, create_extra=()):
         self._sizes = (n_fft, win_size, hop_length, basis.shape[0])
         self._clip = float(clip_val)
         self.mel_basis_host = torch.from_numpy(np.ascontiguousarray(basis))
         self.mel_basis = {}      # device -> tensor
-        self._cache = _lib.HandleCache(name, create, "pd_mel_destroy", limit=8)   # like the reference's window / basis dicts
+        # like the reference's window / basis dicts
+        self._cache = _lib.HandleCache(name, create, "pd_mel_destroy", limit=8, create_extra=create_extra)
         self.handles = self._cache.handles      # (keyshift, speed, device) -> NativeHandle
 
     def handle(self, keyshift, speed, device):

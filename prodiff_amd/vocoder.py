@@ -140,3 +140,25 @@ class FastDiff(BaseVocoder):
             "FastDiff.wav2spec is not implemented: the reference goes through process_utterance (a librosa STFT "
             "plus loudness normalisation, component/vocoder/fastdiff.py:128-142), which this library does not "
             "restate; NsfHifiGAN.wav2spec and prodiff_amd.STFT are the native analysis path")
+
+    @staticmethod
+    def wav2mel(wav_fn, hparams, return_linear=False, device=None):
+        """What the reference's ``wav2spec`` does (fastdiff.py:128-145), on prodiff_amd.analysis.process_utterance:
+        -> (wav [T hop], mel [T, bins]) or, with ``return_linear``, (wav, mel, spc [T, fft_size // 2 + 1]).  The
+        mel is linear in magnitude (vocoder='fastdiff'), the waveform loudness-normalised to -22 LUFS when
+        ``hparams['loud_norm']``."""
+        from .analysis import process_utterance
+        res = process_utterance(
+            wav_fn, fft_size=hparams["fft_size"], hop_size=hparams["hop_size"], win_length=hparams["win_size"],
+            num_mels=hparams["audio_num_mel_bins"], fmin=hparams["fmin"], fmax=hparams["fmax"],
+            sample_rate=hparams["audio_sample_rate"], loud_norm=hparams["loud_norm"],
+            min_level_db=hparams["min_level_db"], return_linear=return_linear, vocoder="fastdiff",
+            eps=float(hparams.get("wav2spec_eps", 1e-10)), device=device)
+        if return_linear:
+            return res[0], res[1].T, res[2].T
+        return res[0], res[1].T
+
+    def wav2wav(self, wav_fn, hparams=None, **kwargs):
+        """Copy synthesis: ``wav2mel`` of a file or clip, then ``spec2wav`` -> np [T hop]."""
+        _, mel = self.wav2mel(wav_fn, self.hparams if hparams is None else hparams, device=self.device)
+        return self.spec2wav(mel, **kwargs).reshape(-1)
