@@ -102,7 +102,7 @@ def ffn(x, w1, b1, w2, b2):
     xp = np.pad(x, ((0, 0), (p, p), (0, 0)))
     y = np.zeros((B, T, F))
     for j in range(k):
-        y += xp[:, j:j + T, :] @ w1[:, :, j].T
+        y += xp[:, j:j + T, :] @ np.ascontiguousarray(w1[:, :, j].T)   # a strided tap leaves BLAS
     y = gelu((y + b1) * k ** -0.5)
     return y @ w2.T + b2
 

@@ -601,6 +601,32 @@ def gen_fullsize_c5():
              wav_l2=np.linalg.norm(w64), wav_mean=w64.mean(), wav_absmax=np.abs(w64).max())
 
 
+# --------------------------------------------------------------------------
+# The condition stage at the dims tests/encoder_cases.py adds (the small cases: the row-count
+# cases and the 5,003-token call run the default dims): inputs and the reference teacher's
+# encoder output and condition, tests/golden/encdims_cond_<name>.npz
+# --------------------------------------------------------------------------
+def gen_encdims():
+    from modules.svs.prodiff_teacher import ProDiffTeacher
+    from tests import encoder_cases as EC
+    for name in EC.fixture_cases("cond"):
+        hp, P, x = EC.hp_of("cond", name), EC.params("cond", name), EC.inputs("cond", name)
+        m = ProDiffTeacher(EC.VOCAB, EC.teacher_hparams(hp)).eval()
+        sd = m.state_dict()
+        assert [k for k in sd if not k.startswith("diffusion") and k in P] == list(P), "state-dict order"
+        for k, v in P.items():
+            assert tuple(sd[k].shape) == v.shape, (k, sd[k].shape, v.shape)
+        missing, unexpected = m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()}, strict=False)
+        assert not unexpected and all(k.startswith("diffusion.") or k.endswith("_float_tensor") for k in missing)
+        t = {k: torch.from_numpy(v) for k, v in x.items()}
+        enc_out = {}
+        hook = m.encoder.register_forward_hook(lambda mod, inp, out: enc_out.setdefault("enc", out.detach().clone()))
+        with torch.no_grad():
+            cond = m.forward_condition(t.pop("txt_tokens"), t.pop("mel2ph"), t.pop("f0"), **t).numpy()
+        hook.remove()
+        save(f"encdims_cond_{name}", cond=cond, enc=enc_out["enc"].numpy(), **x)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:          # e.g. `gen_golden.py reflow` regenerates one family
         globals()["gen_" + sys.argv[1]]()

@@ -5,7 +5,8 @@ survey container, where ``/root/reference`` exists:
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden_variance.py
 
 Weights come from ``prodiff_amd.synth`` by seed (tests/variance_cases.py), so the files hold the inputs,
-the reference's outputs and its ordered state-dict key list only.
+the reference's outputs and its ordered state-dict key list only.  The small cases of tests/encoder_cases.py
+(other widths, head counts, kernel sizes and depths) are written the same way as encdims_pitch_* / encdims_dur_*.
 
 * pitch: ``cond`` is what PitchPredictor.forward hands to ``self.diffusion`` (pitch_predictor.py:118-120),
   captured by a forward pre-hook on it; it is deterministic (the draws happen inside the sampler).
@@ -27,6 +28,7 @@ sys.path.insert(0, REF)
 sys.modules.setdefault("chardet", types.ModuleType("chardet"))   # utils/__init__.py:6
 torch.set_num_threads(8)
 
+from tests import encoder_cases as EC  # noqa: E402
 from tests import golden_io as G  # noqa: E402
 from tests import variance_cases as VC  # noqa: E402
 from modules.variance_predictor.dur_predictor import DurPredictor  # noqa: E402
@@ -49,12 +51,28 @@ def tt(x):
     return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in x.items()}
 
 
-def gen_pitch():
+def pitch_cases():
+    """(fixture name, hp, params, inputs, seeds): tests/variance_cases.py, then the small cases of
+    tests/encoder_cases.py (encdims_pitch_<name>.npz)."""
     for name, c in VC.PITCH_CASES.items():
-        hp = VC.pitch_hp(name)
+        yield name, VC.pitch_hp(name), VC.pitch_params(name), VC.pitch_inputs(name), c
+    for name in EC.fixture_cases("pitch"):
+        yield (f"encdims_pitch_{name}", EC.hp_of("pitch", name), EC.params("pitch", name), EC.inputs("pitch", name),
+               dict(param_seed=EC.seed_of("pitch", name), input_seed=EC.seed_of("pitch", name) + 1))
+
+
+def dur_cases():
+    for name, c in VC.DUR_CASES.items():
+        yield name, VC.dur_hp(name), VC.dur_params(name), VC.dur_inputs(name), c
+    for name in EC.fixture_cases("dur"):
+        yield (f"encdims_dur_{name}", EC.hp_of("dur", name), EC.params("dur", name), EC.inputs("dur", name),
+               dict(param_seed=EC.seed_of("dur", name), input_seed=EC.seed_of("dur", name) + 1))
+
+
+def gen_pitch():
+    for name, hp, P, x, c in pitch_cases():
         m = PitchPredictor(VC.VOCAB, VC.reference_pitch_hparams(hp)).eval()
-        keys = load_params(m, VC.pitch_params(name))
-        x = VC.pitch_inputs(name)
+        keys = load_params(m, P)
         got = {}
         hk = m.diffusion.register_forward_pre_hook(lambda mod, a: got.setdefault("cond", a[0].detach().clone()))
         t = tt(x)
@@ -73,11 +91,9 @@ def gen_pitch():
 
 
 def gen_dur():
-    for name, c in VC.DUR_CASES.items():
-        hp = VC.dur_hp(name)
+    for name, hp, P, x, c in dur_cases():
         m = DurPredictor(VC.VOCAB, VC.reference_dur_hparams(hp)).eval()
-        keys = load_params(m, VC.dur_params(name))
-        x = VC.dur_inputs(name)
+        keys = load_params(m, P)
         got = {}
         hk = m.dur_pred.linear.register_forward_hook(lambda mod, a, out: got.setdefault("lin", out.detach().clone()))
         t = tt(x)

@@ -80,7 +80,7 @@ def conv1d_same(x, w, b):
     xp = np.pad(x, ((0, 0), (k // 2, k // 2), (0, 0)))
     y = np.zeros((B, T, w.shape[0]))
     for j in range(k):
-        y += xp[:, j:j + T, :] @ w[:, :, j].T
+        y += xp[:, j:j + T, :] @ np.ascontiguousarray(w[:, :, j].T)   # a strided tap leaves BLAS
     return y + b
 
 
